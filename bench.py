@@ -12,10 +12,21 @@ batch already resident in HBM: forward -> generator + label-smoothed loss (main 
 (d_model=512, 6 layers, 8 heads, d_ff=2048, |V|=3000, Q/H/C/T=20/128/40/20, 32 I3D(2048)+32 VGGish(128) frames); N = 1:
 32 samples (cfg2 = BASELINE configs[1], the configuration the metric is quoted on); N > 1: 64 samples PER GPU (cfg3 = BASELINE
 configs[2], weak scaling); bf16 compute with fp32 master weights / residual stream / statistics, dropout 0.1 on (in-kernel),
-random-init weights, synthetic data.  Rank 0 prints ONE JSON line — the TERSE form of the record (< 7 KB: the driver keeps an 8 KB tail of
-stdout; keys explained in README.md "Reading the bench line"; `--full-record PATH` writes the verbose form).  `value` comes from EXACTLY --steps steps between two
-barrier + synchronize brackets; four more windows of the same length are timed afterwards and reported beside it
-(config.window_ms_per_step, median) because one window of a 4-5 ms step is a short sample.
+random-init weights, synthetic data.  `value` comes from EXACTLY --steps steps between two barrier + synchronize brackets,
+after --warmup steps (at least one: the first step captures the graph).
+
+A plain run does only that: set up, warm up, time the steps, write the last step's outputs if `--dump-outputs DIR` is given,
+and print ONE JSON line with the headline figure (`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, ...).
+`--full` adds everything else the benchmark measures: four more windows of the same length timed after the one `value`
+comes from (config.window_ms_per_step, median: one window of a 4-5 ms step is a short sample), the roofline (launch census,
+measured MFMA / HBM ceilings), the CPU baseline and the secondary measurements.  Rank 0 then prints the TERSE form of the
+full record (< 7 KB: the driver keeps an 8 KB tail of stdout; keys explained in README.md "Reading the bench line");
+`--full-record PATH` (implies `--full`) writes the verbose form.
+
+`--dump-outputs DIR`: after the timed steps, what the last timed step computed, as float32 .npy files: `loss.npy` (the
+normalised loss the step returns), `params.npy` (the fp32 master weights after its update) and, when the optimiser state
+is whole on this rank, `adam_m.npy` / `adam_v.npy` (Adam's moments); the flat buffers hold ~10^8 values, so each is the
+same fixed, seeded sample of 2^22 positions (DUMP_SAMPLE).  Inputs are seeded: the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -33,6 +44,8 @@ PEAK_BF16_TFLOPS = 2500.0      # MI355X dense bf16 MFMA peak (MI355X_MICROARCH.m
 PEAK_FP32_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0
 SURVEY_GFLOP_PER_SAMPLE = {"cfg2": 15.90, "cfg3": 15.90, "cfg4": 33.22, "cfg1": 0.315}
+DUMP_SAMPLE = 1 << 22          # positions of a flat buffer written by --dump-outputs (16 MB per array in float32)
+DUMP_SEED = 20240601
 
 
 def parse():
@@ -46,22 +59,29 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--dropout", type=float, default=0.1)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="measure everything, not only the headline figure: extra timed windows, "
+                    "roofline (launch census, measured MFMA / HBM peaks), CPU baseline, secondary measurements; the line is then the "
+                    "terse form of the full record")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed "
+                    "(loss, a fixed sample of the updated weights and of Adam's moments) to DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=5)
     ap.add_argument("--bf16-grad-allreduce", action="store_true")
-    ap.add_argument("--windows", type=int, default=4, help="extra timed windows of --steps steps after the one `value` comes from")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (batch-64 figure, one-rank RCCL "
+    ap.add_argument("--windows", type=int, default=4, help="--full: extra timed windows of --steps steps after the one `value` comes from")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary measurements (batch-64 figure, one-rank RCCL "
                     "schedule and decode figures at N=1, exchange-free single-rank figure at N>1)")
     ap.add_argument("--pmc-calibration", action="store_true", help="after the timed steps, one whole-buffer mtn_adam_step over a scratch "
                     "buffer of 2^24 elements: a launch of exactly known HBM traffic (16 B read + 14 B written per element) for "
                     "tools/pmc_summary.py to calibrate the WRITE_SIZE counter on (the fused step itself no longer has one)")
-    ap.add_argument("--full-record", default=None, metavar="PATH", help="also write the VERBOSE record (every figure with its prose description, "
-                    "per-slice exchange timeline, full kernel tables) to PATH as JSON; the printed line is the terse form of it (README.md, "
+    ap.add_argument("--full-record", default=None, metavar="PATH", help="implies --full; also write the VERBOSE record (every figure with its prose "
+                    "description, per-slice exchange timeline, full kernel tables) to PATH as JSON; the printed line is the terse form of it (README.md, "
                     "\"Reading the bench line\")")
     ap.add_argument("--dp-one-rank-probe", action="store_true", help=argparse.SUPPRESS)     # child process of the N = 1 secondary measurement
     ap.add_argument("--no-record", action="store_true", help="development probe: allows MTN_DP_EMULATE_WORLD (a rank updates 1/N of "
                     "every slice as in an N-GPU job — WRONG parameters, timing only); the line is then marked \"record\": false")
     args = ap.parse_args()
+    if args.full_record:
+        args.full = True
     if args.workload is None:
         args.workload = "cfg2" if args.gpus == 1 else "cfg3"
     return args
@@ -579,6 +599,30 @@ def dp_one_rank_probe(args):
     dist.destroy_process_group()
 
 
+def dump_outputs(out_dir, step, model, loss, rank):
+    """--dump-outputs: what the last timed step computed (module docstring), as float32 .npy files in `out_dir`.  Every rank calls
+    it (bringing the fp32 masters of the data-parallel schedule up to date is a collective); rank 0 writes."""
+    import numpy as np
+    if model._master_sync is not None:
+        model._master_sync()
+    flat = model.flat_buffers()[0]
+    n = flat.numel()
+    idx = None
+    if n > DUMP_SAMPLE:              # one position per stride of the flat buffer, at a seeded offset inside it: the same sample every run
+        stride = n // DUMP_SAMPLE
+        off = np.random.default_rng(DUMP_SEED).integers(0, stride, DUMP_SAMPLE)
+        idx = torch.from_numpy(np.arange(DUMP_SAMPLE, dtype=np.int64) * stride + off).to(flat.device)
+    pick = lambda t: (t.detach().reshape(-1) if idx is None else t.detach().reshape(-1)[idx]).float().cpu().numpy()
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy(), "params": pick(flat)}
+    adam = step.opt.optimizer
+    if step.sharded is None and getattr(adam, "m", None) is not None:      # (sharded: this rank's moments cover its own shard only)
+        arrays["adam_m"], arrays["adam_v"] = pick(adam.m), pick(adam.v)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 KERNEL_COLS = ["launches_per_step", "avg_us", "achieved_TFLOPs", "achieved_GBps_algorithmic", "avg_workgroups"]
 
 
@@ -675,6 +719,22 @@ def terse_line(full):
     return line
 
 
+def headline(args, cfg, B, world, elapsed, loss_val):
+    """The line of a plain run: the headline figure over the `value` window and what it was measured on.  `--full` extends this
+    dict into the full record (same keys, same meaning)."""
+    return {"metric": "train-step samples/sec (d_model=512, 6L MTN)", "value": round(world * B * args.steps / elapsed, 2), "unit": "samples/s",
+            **({"record": False} if args.no_record else {}),
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": f"{args.workload}: d_model={cfg['d_model']} N={cfg['N']} h={cfg['h']} d_ff={cfg['d_ff']} |V|={cfg['vocab']} "
+                                   f"Q/H/C/T={cfg['Q']}/{cfg['H']}/{cfg['C']}/{cfg['T']} frames={cfg['frames']} ft={cfg['ft_sizes']}",
+                       "batch_per_gpu": B, "global_batch": B * world, "parallelism": f"dp{world}",
+                       "dropout": args.dropout, "attn_dropout": 0.1 if args.dropout > 0 else 0.0, "hip_graph": not args.no_graph,
+                       "rccl_ranks": torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1,
+                       "dist_backend": torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
+                       "normalised_loss_last_step": round(loss_val, 4)}}
+
+
 def main():
     args = parse()
     if args.dp_one_rank_probe:
@@ -747,12 +807,15 @@ def main():
         loss = step()
     elapsed, ev_total_ms, loss = timed_window(step, args.steps)              # <- `value`
     loss_val = float(loss.item())            # TrainStep returns the normalised loss: sum of the three KL terms per target / query token
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step, model, loss, rank)
+    # everything below up to the line is --full only
     windows = [elapsed / args.steps * 1e3]
-    for _ in range(max(0, args.windows)):
+    for _ in range(max(0, args.windows) if args.full else 0):
         windows.append(timed_window(step, args.steps)[0] / args.steps * 1e3)
     # secondary measurements (never `value`)
     secondary = {}
-    if not args.no_secondary and args.workload in ("cfg2", "cfg3"):
+    if args.full and not args.no_secondary and args.workload in ("cfg2", "cfg3"):
         try:
             if world == 1 and B != 64:
                 # BASELINE configs[2] / north_star quote the utilisation target at batch 64 per GPU: the same step at that batch
@@ -845,6 +908,8 @@ def main():
             secondary["error"] = str(e)
 
     if rank == 0:
+        line = headline(args, cfg, B, world, elapsed, loss_val)
+    if rank == 0 and args.full:
         ms = elapsed / args.steps * 1e3
         value = world * B * args.steps / elapsed
         gflop_formula = flops_per_sample(**cfg) / 1e9
@@ -932,25 +997,14 @@ def main():
         except Exception as e:  # pragma: no cover
             roof = {"bound": "mfma", "achieved": round(step_tf, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(step_tf / peak, 5),
                     "traffic": None, "error": str(e), "step": step_info}
-        line = {"metric": "train-step samples/sec (d_model=512, 6L MTN)", "value": round(value, 2), "unit": "samples/s",
-                **({"record": False} if args.no_record else {}),
-                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
-                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-                "config": {"workload": f"{args.workload}: d_model={cfg['d_model']} N={cfg['N']} h={cfg['h']} d_ff={cfg['d_ff']} |V|={cfg['vocab']} "
-                                       f"Q/H/C/T={cfg['Q']}/{cfg['H']}/{cfg['C']}/{cfg['T']} frames={cfg['frames']} ft={cfg['ft_sizes']}",
-                           "batch_per_gpu": B, "global_batch": B * world, "parallelism": f"dp{world}",
-                           "dropout": args.dropout, "attn_dropout": 0.1 if args.dropout > 0 else 0.0,
-                           "hip_graph": not args.no_graph, "weights": "random-init (xavier), fp32 master + bf16 compute copy",
-                           "rccl_ranks": torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1,
-                           "dist_backend": torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
-                           "window_ms_per_step": [round(w, 4) for w in windows],
-                           "median_window_ms_per_step": round(sorted(windows)[len(windows) // 2], 4),
-                           "normalised_loss_last_step": round(loss_val, 4),
-                           **({"per_gpu_work": f"{B} samples per GPU at every N > 1 (BASELINE configs[2] = cfg3: 64 per GPU); the N = 1 default line is "
-                                               "configs[1] (cfg2, batch 32): the single-GPU figure of THIS per-GPU batch is secondary.one_rank_no_exchange "
-                                               "(same job) / the N = 1 line's secondary.batch64_one_gpu"} if world > 1 else {}),
-                           "secondary": secondary},
-                "roofline": roof}
+        line["config"].update({"weights": "random-init (xavier), fp32 master + bf16 compute copy",
+                               "window_ms_per_step": [round(w, 4) for w in windows],
+                               "median_window_ms_per_step": round(sorted(windows)[len(windows) // 2], 4),
+                               **({"per_gpu_work": f"{B} samples per GPU at every N > 1 (BASELINE configs[2] = cfg3: 64 per GPU); the N = 1 default line is "
+                                                   "configs[1] (cfg2, batch 32): the single-GPU figure of THIS per-GPU batch is secondary.one_rank_no_exchange "
+                                                   "(same job) / the N = 1 line's secondary.batch64_one_gpu"} if world > 1 else {}),
+                               "secondary": secondary})
+        line["roofline"] = roof
         if world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(model, cfg, B, args.cpu_steps)
@@ -976,7 +1030,7 @@ def main():
         if args.full_record:
             with open(args.full_record, "w") as f:
                 json.dump(line, f, indent=1)
-        print(json.dumps(terse_line(line), separators=(",", ":")), flush=True)
+        print(json.dumps(terse_line(line) if args.full else line, separators=(",", ":")), flush=True)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
 

@@ -6,6 +6,7 @@ inputs are regenerated bit-identically on both sides from the formulas below
 """
 from __future__ import annotations
 
+import os
 import zlib
 from typing import Dict, List, Sequence, Tuple
 
@@ -94,6 +95,42 @@ GOLDEN_CONFIGS: Dict[str, dict] = {
     "small_diffall": dict(vocab=60, N=1, d_model=64, d_ff=128, h=2, ft_sizes=[96], B=2, Q=7, H=5, C=13, T=6,
                           frames=[9], diff_encoder=True, diff_embed=True, diff_gen=True, auto_encoder_ft="summary"),
 }
+
+GOLDEN_PART_BYTES = 1 << 20          # no committed file may exceed 1 MiB: a golden set is split into <name>.npz, <name>.1.npz, ...
+
+
+def save_golden(path: str, arrays: Dict[str, np.ndarray]) -> List[str]:
+    """Write ``arrays`` to ``path`` (``<dir>/<name>.npz``) and, where they hold more than GOLDEN_PART_BYTES, to the parts
+    ``<name>.1.npz``, ``<name>.2.npz``, ... in order: each part holds at most that many uncompressed bytes (unless a single
+    array does).  Returns the files written; stale parts of an earlier, larger set are removed."""
+    parts: List[Dict[str, np.ndarray]] = [{}]
+    size = 0
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        if parts[-1] and size + v.nbytes > GOLDEN_PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += v.nbytes
+    stem = path[:-4]
+    files = [path] + [f"{stem}.{i}.npz" for i in range(1, len(parts))]
+    for f, p in zip(files, parts):
+        np.savez_compressed(f, **p)
+    i = len(parts)
+    while os.path.exists(f"{stem}.{i}.npz"):
+        os.remove(f"{stem}.{i}.npz")
+        i += 1
+    return files
+
+
+def load_golden(path: str) -> Dict[str, np.ndarray]:
+    """The arrays ``save_golden`` wrote to ``path`` and its parts, as one dict."""
+    out = dict(np.load(path, allow_pickle=False))
+    i = 1
+    while os.path.exists(f"{path[:-4]}.{i}.npz"):
+        out.update(np.load(f"{path[:-4]}.{i}.npz", allow_pickle=False))
+        i += 1
+    return out
 
 
 def state_shapes(vocab: int, N: int, d_model: int, d_ff: int, ft_sizes: Sequence[int], diff_encoder: bool,

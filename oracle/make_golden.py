@@ -26,7 +26,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
-from oracle.fixtures import GOLDEN_CONFIGS, PAD, UNK, SOS, EOS, det_batch, det_state_dict  # noqa: E402
+from oracle.fixtures import GOLDEN_CONFIGS, PAD, UNK, SOS, EOS, det_batch, det_state_dict, save_golden  # noqa: E402
 
 REF = "/root/reference"
 
@@ -170,8 +170,8 @@ def run_config(name, c, ref_mtn, ref_du, ref_ls):
     for k, v in out.items():
         npz[k] = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v
     path = os.path.join(ROOT, "tests", "golden", name + ".npz")
-    np.savez_compressed(path, **npz)
-    print(f"{name}: {len(npz)} arrays, loss={float(out['loss']):.6f}, {os.path.getsize(path) / 1e6:.2f} MB")
+    files = save_golden(path, npz)
+    print(f"{name}: {len(npz)} arrays in {len(files)} file(s), loss={float(out['loss']):.6f}, {sum(map(os.path.getsize, files)) / 1e6:.2f} MB")
 
 
 def run_batch_assembly():

@@ -34,7 +34,7 @@ def test_beam_search_matches_reference_nbest(dev, name, use_graph, kv_cache):
     per token, the cache rows following their parent hypotheses)."""
     from mtn_amd.decode import beam_search_decode
     c = fx.GOLDEN_CONFIGS[name]
-    g = dict(np.load(os.path.join(GOLD, name + ".npz")))
+    g = fx.load_golden(os.path.join(GOLD, name + ".npz"))
     model = build_model(c, torch.float32, dev).eval()
     b = dev_batch(one_dialogue(c), dev)
     nbest, best = beam_search_decode(model, b, 8, fx.SOS, fx.UNK, fx.EOS, fx.PAD, use_graph=use_graph, kv_cache=kv_cache)
@@ -109,7 +109,7 @@ def test_beam_search_many_dialogues_equals_one_by_one(dev):
     model = build_model(c, torch.float32, dev).eval()
     raws = [one_dialogue(c, seed=2), one_dialogue(c, seed=5), one_dialogue(c, seed=8)]
     singles = [beam_search_decode(model, dev_batch(r, dev), 8, fx.SOS, fx.UNK, fx.EOS, fx.PAD) for r in raws]
-    g = dict(np.load(os.path.join(GOLD, name + ".npz")))
+    g = fx.load_golden(os.path.join(GOLD, name + ".npz"))
     assert [list(t) for t, _ in singles[0][0]] == [list(g[f"beam.tokens.{i}"]) for i in range(int(g["beam.n"]))]
     # make the batch ragged: cut the 2nd dialogue's history/caption and pad
     raws[1]["his"][:, 11:] = fx.PAD
@@ -283,7 +283,7 @@ def test_persistent_decode_beam_search_equals_launch_pass(dev):
     from mtn_amd import decode as D
     name = "cfg1_query"
     c = fx.GOLDEN_CONFIGS[name]
-    g = dict(np.load(os.path.join(GOLD, name + ".npz")))
+    g = fx.load_golden(os.path.join(GOLD, name + ".npz"))
     model = build_model(c, torch.bfloat16, dev).eval()
     b = dev_batch(one_dialogue(c), dev)
     D._SESSIONS.clear()

@@ -142,7 +142,7 @@ def test_model_forward_matches_reference_golden(dev, dtype, name):
     """encode outputs, every sublayer output of layer 0, final (out, [ae]) and generator log-probs against the outputs the
     REFERENCE produced for the same weights/inputs (ragged batch: padded tails, empty history row, padded frames)."""
     c = fx.GOLDEN_CONFIGS[name]
-    g = dict(np.load(os.path.join(GOLD, name + ".npz")))
+    g = fx.load_golden(os.path.join(GOLD, name + ".npz"))
     model = build_model(c, dtype, dev).eval()
     b = dev_batch(raw_batch(c), dev)
     taps = {}
@@ -173,7 +173,7 @@ def test_model_forward_matches_reference_golden(dev, dtype, name):
 def test_model_loss_and_grads_match_reference_golden(dev, dtype, name):
     from mtn_amd import LabelSmoothing, SimpleLossCompute
     c = fx.GOLDEN_CONFIGS[name]
-    g = dict(np.load(os.path.join(GOLD, name + ".npz")))
+    g = fx.load_golden(os.path.join(GOLD, name + ".npz"))
     model = build_model(c, dtype, dev).eval()        # eval(): dropout off, as in the golden run
     b = dev_batch(raw_batch(c), dev)
     crit = LabelSmoothing(c["vocab"], fx.PAD, 0.1)
@@ -220,7 +220,7 @@ def test_two_fused_adam_steps_match_reference_golden(dev, dtype):
     from mtn_amd import FusedAdam, LabelSmoothing, NoamOpt, SimpleLossCompute
     name = "cfg1_query"
     c = fx.GOLDEN_CONFIGS[name]
-    g = dict(np.load(os.path.join(GOLD, name + ".npz")))
+    g = fx.load_golden(os.path.join(GOLD, name + ".npz"))
     model = build_model(c, dtype, dev).eval()
     b = dev_batch(raw_batch(c), dev)
     opt = NoamOpt(c["d_model"], 1, 10, FusedAdam(model))

@@ -18,7 +18,7 @@ TOL = 2e-5      # fp32 CPU vs fp32 CPU, different op order only
 
 
 def load(name):
-    return dict(np.load(os.path.join(GOLD, name + ".npz"), allow_pickle=False))
+    return fx.load_golden(os.path.join(GOLD, name + ".npz"))
 
 
 def close(a, b, tol=TOL):

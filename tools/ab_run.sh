@@ -11,7 +11,7 @@ shift
 cd "${GRAFT_REPO_ROOT:-.}"
 for i in 1 2; do
   for v in "$@"; do
-    env $v timeout 300 python bench.py --no-cpu-baseline --no-secondary --windows 4 --steps 30 "${ARGS[@]}" 2>/dev/null | \
+    env $v timeout 300 python bench.py --full --no-cpu-baseline --no-secondary --windows 4 --steps 30 "${ARGS[@]}" 2>/dev/null | \
       python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', d['ms_per_step'], d['config']['median_window_ms_per_step'], d['roofline'].get('avg_us_per_launch'))"
   done
 done | tee "gpurun_out/$OUT"
