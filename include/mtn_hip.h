@@ -42,7 +42,8 @@ const char* mtn_last_error(void);
  * 112 (round 5): new entry points only (mtn_measure_mfma_peak_shapes, ...: see INTEGRATION.md); mtn_measure_mfma_peak now reports
  * the better of two MFMA shapes.
  * 113 (round 6): mtn_decode_args gained the trailing field `max_m`; mtn_decode_step takes W <= 16 rows, clamps `grid` to the device's
- * compute-unit count and bounds its polls in time (see there). */
+ * compute-unit count and bounds its polls in time (see there).
+ * 114: mtn_assemble_tokens_desc gained the trailing field `row_len` (NULL = no cut; a zeroed struct keeps meaning that). */
 int mtn_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -526,6 +527,8 @@ int mtn_adam_step_chunks(int dtype, int n_chunks, const long* off, const int* le
  * the list of item ids (`ids`, device int32[B]; NULL = items 0..B-1).
  *   tokens  : out[b,l] = l < len ? flat[start+l] : pad; mask[b,l] = (out != pad); std_mask[b,i,j] = (out[b,j] != pad) &
  *             (j <= i) (optional, data_utils.py:48-54); *n_nonpad += #non-pad (optional, data_utils.py:45; zero it first).
+ *             len = min(item length, L, row_len[b] if row_len and row_len[b] >= 0): row_len cuts rows short (the reference's
+ *             random answer truncation, data_handler.py:255-260); out, mask, std_mask and n_nonpad all follow that len.
  *   features: frames start, start+skip, ...; out[b,v,:] = frame if it exists and has any element != 1, else 0;
  *             mask[b,v] = that validity (the reference pads with ones, detects all-ones frames, then zeroes them).
  * ------------------------------------------------------------------------------------------ */
@@ -541,6 +544,7 @@ typedef struct {
     uint8_t* mask;        /* [B, L] or NULL */
     uint8_t* std_mask;    /* [B, L, L] or NULL */
     int64_t* n_nonpad;    /* scalar accumulator or NULL */
+    const int32_t* row_len; /* [B] cap of each row's length (< 0: no cap), or NULL (since version 114) */
 } mtn_assemble_tokens_desc;
 int mtn_assemble_tokens(int count, const mtn_assemble_tokens_desc* descs /* host array */, void* stream);
 typedef struct {

@@ -6,6 +6,7 @@
 //   tokens  : out[b, l] = l < len ? flat[start + l] : pad ; mask[b, l] = out != pad      (data_utils.py:33-37)
 //             optional std_mask[b, i, j] = (out[b, j] != pad) & (j <= i)                    (data_utils.py:48-54)
 //             optional count of non-pad tokens (ntokens, data_utils.py:45)
+//             optional per-row cap of len (row_len[b] >= 0): the random answer truncation of --cut-a (data_handler.py:255-260)
 //   features: frames every `skip`-th, rows past the end padded with ones, a frame is valid iff any element != 1, and
 //             invalid frames are zeroed                                                      (data_utils.py:27-30)
 // Integer / copy work: bit-exact against the numpy restatement in oracle/.
@@ -21,7 +22,11 @@ __global__ __launch_bounds__(256) void assemble_tokens_kernel(const TokGroup grp
     const int b = (int)blockIdx.x - grp.block_start[g];          // one workgroup per sample
     const int item = D.ids ? D.ids[b] : b;
     const long start = D.start[item];
-    const int len = D.len[item] < D.L ? D.len[item] : D.L;
+    int len = D.len[item] < D.L ? D.len[item] : D.L;
+    if (D.row_len) {
+        const int cap = D.row_len[b];                             // < 0: this row is not cut
+        if (cap >= 0 && cap < len) len = cap;
+    }
     int nonpad = 0;
     for (int l = threadIdx.x; l < D.L; l += 256) {
         const long v = l < len ? D.flat[start + l] : D.pad;

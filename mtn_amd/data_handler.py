@@ -9,7 +9,9 @@ host, `np.load`s the feature files, uploads, and derives masks with several torc
 * ``DeviceCorpus`` uploads the corpus ONCE: each token field as one flat int64 buffer + per-item start/length tables, each
   feature type as one flat [frames, F] float buffer + per-video tables;
 * ``make_batch`` describes a batch by the ids of its items (one small H2D copy) and builds all padded tensors AND their
-  masks with two grouped HIP launches (csrc/assemble.hip) — no host padding, no per-step file I/O, no mask passes.
+  masks with two grouped HIP launches (csrc/assemble.hip) — no host padding, no per-step file I/O, no mask passes;
+  ``cut_a=True`` draws the reference's random answer truncation on the host (``draw_cuts``, from host copies of the
+  answer lengths) and the same launch cuts the answer rows short (``row_len``).
 
 ``get_vocabulary`` / ``load`` read the DSTC7-AVSD json + per-video .npy features into that layout (host work, once per run;
 reference data_handler.py:45-148): ``data`` is the dict the reference's ``load`` returns, except that the feature values are
@@ -181,6 +183,8 @@ class DeviceCorpus:
         by_id = sorted(dialogs, key=lambda d: d[1])
         assert [d[1] for d in by_id] == list(range(self.n_dialogs)), "qa ids must be 0..n-1 (data_handler.py:134)"
         self.tok: Dict[str, tuple] = {}
+        self.host_tok: Dict[str, tuple] = {}
+        self._cut_a_checked = False
         for name, col in _FIELDS:
             if col == 6 and not self.has_caption:
                 continue
@@ -189,6 +193,8 @@ class DeviceCorpus:
             start = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.int64)]).astype(np.int64)
             flat = np.concatenate(seqs) if len(seqs) else np.zeros(0, np.int64)
             self.tok[name] = tuple(torch.from_numpy(a).to(self.device) for a in (flat, start, lens))
+            if name in ("trg", "trg_y"):
+                self.host_tok[name] = (flat, start, lens)       # host copies: the cut draws never read the device
         self.vid_index: Dict[object, int] = {}
         self.feat: List[tuple] = []
         if data.get("features"):
@@ -208,13 +214,63 @@ class DeviceCorpus:
         n = sum(t.numel() * t.element_size() for f in self.tok.values() for t in f)
         return n + sum(t.numel() * t.element_size() for f in self.feat for t in f[:3])
 
+    def answer_lengths(self) -> np.ndarray:
+        """Host int32 [n_dialogs]: len(answer_in) of every qa id (what the cut draws need)."""
+        return self.host_tok["trg"][2]
+
+    def check_cut_a(self):
+        """Once per corpus: a cut row is both answer fields cut to the same length e, which is the reference's cut
+        (answer_out = answer_in[1:e+1], data_handler.py:259) only if answer_in[1:] == answer_out[:len(answer_in)-1] —
+        true of what ``load`` builds (answers[:-1], answers[1:]).  Raise rather than train on other targets."""
+        if self._cut_a_checked:
+            return
+        fi, si, li = self.host_tok["trg"]
+        fo, so, lo = self.host_tok["trg_y"]
+        m = np.maximum(li.astype(np.int64) - 1, 0)
+        bad = np.flatnonzero(lo < m)
+        if not bad.size:
+            rows = np.repeat(np.arange(self.n_dialogs), m)
+            off = np.arange(int(m.sum())) - np.repeat(np.cumsum(m) - m, m)
+            bad = np.unique(rows[fi[si[rows] + 1 + off] != fo[so[rows] + off]])
+        if bad.size:
+            raise ValueError("cut_a: answer_out is not answer_in shifted by one token for qa id(s) %s%s; the truncation of "
+                             "data_handler.py:255-260 cannot be applied to this corpus"
+                             % (bad[:8].tolist(), " ..." if bad.size > 8 else ""))
+        self._cut_a_checked = True
+
+
+def cut_a_stream(seed: int, rank: int = 0) -> np.random.RandomState:
+    """The draw stream of --cut-a for one data-parallel rank: rank 0 draws from RandomState(seed), which is the stream the
+    reference's np.random.seed(seed) (train.py:109) gives its make_batch; rank r > 0 from its own stream derived from (seed, r)."""
+    return np.random.RandomState(seed) if rank == 0 else np.random.RandomState([seed, rank])
+
+
+def draw_cuts(answer_len, qa_ids, cut_a_p: float = 0.5, rng=None) -> np.ndarray:
+    """The reference's per-sample truncation draws (data_handler.py:255-260), in its order and with its calls, so that the
+    stream is consumed identically: for each qa id, one uniform; if it is >= 1 - cut_a_p, the cut end e = choice(range(1,
+    len(answer_in)), 1)[0] — the row keeps answer_in[:e] and answer_out[:e].  ``rng``: a numpy RandomState, None = the global
+    np.random (as the reference).  Returns int32 [len(qa_ids)]: e, or -1 for a row that is not cut."""
+    rng = np.random if rng is None else rng
+    row_len = np.full(len(qa_ids), -1, dtype=np.int32)
+    for i, q in enumerate(qa_ids):
+        pr = rng.uniform()
+        if pr >= (1 - cut_a_p):
+            n = int(answer_len[q])
+            if n < 2:
+                raise ValueError(f"cut_a: qa id {q} has an answer_in of {n} token(s); a cut needs at least 2 "
+                                 "(the reference fails here too: choice on an empty range)")
+            row_len[i] = rng.choice(range(1, n), 1)[0]
+    return row_len
+
 
 def make_batch(corpus: DeviceCorpus, index, vocab, separate_caption: bool = False, skip: Sequence[int] = (1, 1, 1),
-               out: Batch = None) -> Batch:
+               out: Batch = None, cut_a: bool = False, cut_a_p: float = 0.5, rng=None) -> Batch:
     """data_handler.py:219-274 on the device: ``index`` is one entry of make_batch_indices; ``vocab`` the vocabulary dict
     (its '<blank>' is the pad id) or the pad id itself.  Returns the same Batch the reference builds (fields, shapes,
     dtypes, mask semantics), with the masks' kernel images already attached.  ``out``: a Batch made by an earlier call with
-    the same padded lengths and size — its tensors are refilled in place (what a captured hipGraph keeps reading)."""
+    the same padded lengths and size — its tensors are refilled in place (what a captured hipGraph keeps reading).
+    ``cut_a`` / ``cut_a_p``: the reference's random answer truncation (``draw_cuts`` with ``rng``, None = the global
+    np.random); padded lengths stay those of ``index``, only the answer rows, their masks and ntokens change."""
     pad = int(vocab["<blank>"]) if isinstance(vocab, dict) else int(vocab)
     if separate_caption:
         x_len, h_len, q_len, a_len, c_len, n = index[2:]
@@ -223,7 +279,16 @@ def make_batch(corpus: DeviceCorpus, index, vocab, separate_caption: bool = Fals
         c_len = None
     dev = corpus.device
     lib = L.load()
-    ids = torch.tensor(list(index[1]), dtype=torch.int32).to(dev, non_blocking=True)
+    row_len = None
+    if cut_a:
+        corpus.check_cut_a()
+        staged = np.empty(2 * n, dtype=np.int32)                      # ids and cut lengths in one H2D copy
+        staged[:n] = index[1]
+        staged[n:] = draw_cuts(corpus.answer_lengths(), index[1], cut_a_p, rng)
+        staged = torch.from_numpy(staged).to(dev, non_blocking=True)
+        ids, row_len = staged[:n], staged[n:]
+    else:
+        ids = torch.tensor(list(index[1]), dtype=torch.int32).to(dev, non_blocking=True)
     plan = [("query", q_len), ("his", h_len), ("trg", a_len), ("trg_y", a_len)] + ([("cap", c_len)] if separate_caption else [])
     descs = (L.AssembleTokensDesc * len(plan))()
     reuse = out
@@ -253,6 +318,8 @@ def make_batch(corpus: DeviceCorpus, index, vocab, separate_caption: bool = Fals
             D.std_mask = std.data_ptr()
         if name == "trg_y":
             D.n_nonpad = ntok.data_ptr()
+        if row_len is not None and name in ("trg", "trg_y"):
+            D.row_len = row_len.data_ptr()
     L.check(lib.mtn_assemble_tokens(len(plan), descs, L.stream_ptr()))
     fts = fts_mask = None
     if corpus.feat:

@@ -166,7 +166,8 @@ GEMM_MAX_GROUP = 16
 _P = C.c_void_p
 class AssembleTokensDesc(C.Structure):
     _fields_ = [("flat", C.c_void_p), ("start", C.c_void_p), ("len", C.c_void_p), ("ids", C.c_void_p), ("B", C.c_int), ("L", C.c_int),
-                ("pad", C.c_int64), ("out", C.c_void_p), ("mask", C.c_void_p), ("std_mask", C.c_void_p), ("n_nonpad", C.c_void_p)]
+                ("pad", C.c_int64), ("out", C.c_void_p), ("mask", C.c_void_p), ("std_mask", C.c_void_p), ("n_nonpad", C.c_void_p),
+                ("row_len", C.c_void_p)]          # NULL (a zeroed struct): no row is cut
 
 
 class AssembleFeaturesDesc(C.Structure):

@@ -33,7 +33,9 @@ def parse(argv=None):
         p.add_argument(f, default="", type=str)
     p.add_argument("--include-caption", default="none", type=str)
     p.add_argument("--separate-caption", default=1, type=int)
-    p.add_argument("--cut-a", default=0, type=int)
+    p.add_argument("--cut-a", default=0, type=int,
+                   help="1: randomly truncate answers as the reference's training recipe does (data_handler.py:255-260), training "
+                        "and validation batches, draws from numpy RandomState(--rand-seed) — corpus mode only")
     p.add_argument("--merge-source", default=0, type=int)
     p.add_argument("--exclude-video", action="store_true")
     p.add_argument("--fixed-word-emb", default=0, type=int)
@@ -70,7 +72,8 @@ def parse(argv=None):
                         "after every epoch and the best model is kept as <model>_best (train.py:201-224)")
     p.add_argument("--resume", default="", type=str,
                    help="corpus mode: checkpoint prefix to continue from (<prefix>.pth.tar = model state_dict in the reference's key "
-                        "schema, <prefix>_opt.pth.tar = optimiser moments + schedule state)")
+                        "schema, <prefix>_opt.pth.tar = optimiser moments + schedule state); the --cut-a draw stream restarts "
+                        "from --rand-seed")
     p.add_argument("--eager", action="store_true", help="corpus mode: one eager step per batch instead of captured graphs per padded shape")
     p.add_argument("--bucket", default=8, type=int, help="corpus mode: batch lengths are rounded up to multiples of this")
     p.add_argument("--corpus-max-answer", default=18, type=int, help="synthetic corpus: longest answer (AVSD's reach 52 tokens)")
@@ -102,9 +105,20 @@ def synthetic_corpus(n_videos, vocab, ft_sizes, seed, turns=10, max_answer=18, m
     return {"dialogs": dialogs, "features": feats, "vocab": {"<blank>": 1}}
 
 
-def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng):
+def cut_a_applies(args) -> bool:
+    """--cut-a truncates the answers of corpus-mode batches (--train-set or --corpus-videos); the fixed synthetic batch of
+    throughput runs is never truncated, which a warning says."""
+    corpus_mode = bool(args.train_set) or args.corpus_videos > 0
+    if args.cut_a and not corpus_mode:
+        logging.warning("--cut-a %d is ignored: answer truncation applies to corpus mode only (--train-set or --corpus-videos), "
+                        "not to the fixed synthetic batch", args.cut_a)
+    return bool(args.cut_a) and corpus_mode
+
+
+def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=None):
     """The same epoch on captured graphs (train_step.BucketedTrainer): lengths rounded up to the bucket, one graph per padded
-    shape, batches assembled in place on the device; the host only syncs at the report interval."""
+    shape, batches assembled in place on the device; the host only syncs at the report interval.  ``cut``: the --cut-a
+    RandomState (None = no truncation).  Returns (mean loss per token, target tokens of the epoch over all ranks)."""
     order = list(range(len(indices)))
     rng.shuffle(order)
     dev = trainer.corpus.device
@@ -112,7 +126,7 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng):
     tok_sum = torch.zeros((), device=dev, dtype=torch.int64)
     t0, tok0 = time.time(), 0
     for j, k in enumerate(order):
-        loss, b = trainer.step(indices[k])
+        loss, b = trainer.step(indices[k], cut_a=cut is not None, rng=cut)
         # the step's loss is already divided by the token count of the step over ALL ranks (train.py:36; dp.py): weight it
         # with that same count; the ranks' sums add up to the epoch mean of the global batches
         n_glob = b._norms_global[0].to(torch.int64)
@@ -125,11 +139,13 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng):
             t0, tok0 = time.time(), ntok
     if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
         torch.distributed.all_reduce(loss_sum)
-    return float(loss_sum) / max(1, int(tok_sum))
+    ntok = int(tok_sum)
+    return float(loss_sum) / max(1, ntok), ntok
 
 
-def validate(corpus, indices, model, criterion, ae_ft, lam):
-    """train.py:201-210: the epoch loop with the model in eval() mode and no optimiser — mean loss per target token."""
+def validate(corpus, indices, model, criterion, ae_ft, lam, cut=None):
+    """train.py:201-210: the epoch loop with the model in eval() mode and no optimiser — mean loss per target token.  ``cut``:
+    the --cut-a RandomState; the reference truncates validation answers too (train.py:30 passes cut_a to every run_epoch)."""
     from .data_handler import make_batch
     from .data_utils import SimpleLossCompute
     lc = SimpleLossCompute(model.generator, model.auto_encoder_generator, criterion, opt=None, l=lam, sync=False)
@@ -139,7 +155,7 @@ def validate(corpus, indices, model, criterion, ae_ft, lam):
     tokens = torch.zeros((), device=corpus.device, dtype=torch.int64)
     with torch.no_grad():
         for ix in indices:
-            b = make_batch(corpus, ix, 1, separate_caption=True)
+            b = make_batch(corpus, ix, 1, separate_caption=True, cut_a=cut is not None, rng=cut)
             out, ae_out = model.forward(b)
             ae_y = b.cap if ae_ft in ("caption", "summary") else b.query
             total += lc(out, b.trg_y, b.ntokens, ae_out, ae_y, (ae_y != 1).sum())
@@ -157,35 +173,39 @@ def global_norms(b, ae_y, sync):
     return norms, local_ntok
 
 
-def run_epoch(corpus, indices, model, loss_compute, ae_ft, epoch, report_interval, rank, rng):
+def run_epoch(corpus, indices, model, loss_compute, ae_ft, epoch, report_interval, rank, rng, cut=None):
     """train.py:23-50: shuffle the planned batches, assemble each on the device, forward, loss + backward + optimiser.
     Data parallel: the loss normalisers are the GLOBAL token counts of the step (all ranks' batches), so that the summed
-    gradients are those of one rank on the concatenated batch (dp.py) — as the captured schedule does (TrainStep._norms)."""
+    gradients are those of one rank on the concatenated batch (dp.py) — as the captured schedule does (TrainStep._norms).
+    ``cut``: the --cut-a RandomState (None = no truncation).  Returns (mean loss per token, target tokens over all ranks)."""
     from .data_handler import make_batch
     order = list(range(len(indices)))
     rng.shuffle(order)
-    t0, tokens, total_loss, total_tokens = time.time(), 0, 0.0, 0
+    t0, tokens, total_loss, total_tokens, global_tokens = time.time(), 0, 0.0, 0, 0
     sync = loss_compute.grad_sync
     for j, k in enumerate(order):
-        b = make_batch(corpus, indices[k], 1, separate_caption=True)
+        b = make_batch(corpus, indices[k], 1, separate_caption=True, cut_a=cut is not None, rng=cut)
         out, ae_out = model.forward(b)
         ae_y = b.cap if ae_ft in ("caption", "summary") else b.query
         norms, local_ntok = global_norms(b, ae_y, sync)
         loss = loss_compute(out, b.trg_y, norms[0], ae_out, ae_y, norms[1])     # = normalised loss x global target tokens
-        loss = loss * local_ntok / float(norms[0])                              # this rank's share, for the epoch mean below
+        n_glob = float(norms[0])
+        loss = loss * local_ntok / n_glob                                       # this rank's share, for the epoch mean below
         total_loss += loss
         total_tokens += int(b.ntokens)
+        global_tokens += int(round(n_glob))
         tokens += int(b.ntokens)
         if (j + 1) % report_interval == 0 and rank == 0:
             dt = time.time() - t0
             print("Epoch: %d Step: %d Loss: %f Tokens per Sec: %f" % (epoch + 1, j + 1, loss / float(b.ntokens), tokens / dt))
             t0, tokens = time.time(), 0
-    return total_loss / max(1, total_tokens)
+    return total_loss / max(1, total_tokens), global_tokens
 
 
 def main(argv=None):
     args = parse(argv)
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(asctime)s %(levelname)s: %(message)s")
+    cut_a = cut_a_applies(args)
     rank, world, local = dp.init_distributed()
     local = local % torch.cuda.device_count()      # (several ranks may share a GPU in a gloo dry run)
     dev = torch.device("cuda", local)
@@ -234,7 +254,7 @@ def main(argv=None):
         model.prepare()
     if args.corpus_videos > 0 or train_data is not None:
         import random
-        from .data_handler import DeviceCorpus, make_batch_indices
+        from .data_handler import DeviceCorpus, cut_a_stream, make_batch_indices
         from .data_utils import FusedAdam, LabelSmoothing, NoamOpt, SimpleLossCompute
         synthetic = train_data is None
         max_len = 256 if synthetic else args.max_length         # (run.sh passes 256, the parser's default is the reference's 20)
@@ -246,6 +266,9 @@ def main(argv=None):
         corpus = DeviceCorpus(data, dev)
         logging.info("corpus: %d dialogs in %d batches, %.1f MB resident on the device", n_samples, len(indices), corpus.nbytes() / 1e6)
         rng = random.Random(args.rand_seed)
+        # --cut-a: ONE stream for the run's training batches (in visiting order) and then each epoch's validation batches (in
+        # plan order), as the reference's global np.random after np.random.seed(--rand-seed) (train.py:109); per rank
+        cut = cut_a_stream(args.rand_seed, rank) if cut_a else None
         means = []
         if args.eager:
             opt = NoamOpt(args.d_model, 1, args.warmup_steps, FusedAdam(model))
@@ -270,10 +293,12 @@ def main(argv=None):
             logging.info("resumed from %s at optimiser step %d", args.resume, the_opt.step_count())
         for epoch in range(args.num_epochs):
             if args.eager:
-                mean = run_epoch(corpus, indices, model, lc, args.auto_encoder_ft, epoch, args.report_interval, rank, rng)
+                mean, ntok = run_epoch(corpus, indices, model, lc, args.auto_encoder_ft, epoch, args.report_interval, rank, rng, cut)
             else:
-                mean = run_epoch_graphed(trainer, indices, epoch, args.report_interval, rank, rng)
+                mean, ntok = run_epoch_graphed(trainer, indices, epoch, args.report_interval, rank, rng, cut)
             means.append(mean)
+            if rank == 0:
+                logging.info("epoch %d: %d target tokens trained%s", epoch + 1, ntok, " (answers cut at random)" if cut_a else "")
             if rank == 0:
                 print("epoch %d mean train loss per token: %f" % (epoch + 1, mean))
             if args.model:
@@ -289,7 +314,7 @@ def main(argv=None):
             if valid is not None:
                 best_state = model.state_dict() if args.model else None    # (collective) written by rank 0 alone if validation improves
                 from .data_utils import LabelSmoothing as _LS
-                vloss = validate(valid[0], valid[1], model, _LS(args.vocab_size, 1, 0.1), args.auto_encoder_ft, args.loss_l)
+                vloss = validate(valid[0], valid[1], model, _LS(args.vocab_size, 1, 0.1), args.auto_encoder_ft, args.loss_l, cut)
                 if rank == 0:
                     print("epoch: %d validation loss: %f" % (epoch + 1, vloss))          # train.py:210
                     if vloss < min_valid:

@@ -383,9 +383,10 @@ class BucketedTrainer:
         x_len, h_len, q_len, a_len, c_len, n = index[2:]
         return (index[0], index[1], [up(v) for v in x_len], up(h_len), up(q_len), up(a_len), up(c_len), n)
 
-    def step(self, index):
+    def step(self, index, cut_a: bool = False, rng=None):
         """One optimiser step on the batch described by ``index`` (an entry of data_handler.make_batch_indices with
-        separate_caption=True).  Returns (device loss tensor, the static Batch that now holds this batch)."""
+        separate_caption=True).  Returns (device loss tensor, the static Batch that now holds this batch).  ``cut_a``: the
+        reference's random answer truncation, drawn once per step from ``rng`` (data_handler.draw_cuts; None = np.random)."""
         from .data_handler import make_batch
         pidx = self._padded(index)
         key = (tuple(pidx[2]),) + tuple(pidx[3:])
@@ -393,12 +394,12 @@ class BucketedTrainer:
         if hit is None:
             if len(self.steps) >= self.max_shapes:
                 self.steps.pop(next(iter(self.steps)))
-            batch = make_batch(self.corpus, pidx, self.pad, separate_caption=True)
+            batch = make_batch(self.corpus, pidx, self.pad, separate_caption=True, cut_a=cut_a, rng=rng)
             ts = TrainStep(self.model, batch, self.vocab, pad=self.pad, lam=self.lam, grad_sync=self.grad_sync, opt=self.opt,
                            dynamic_norms=True)
             self.steps[key] = hit = (batch, ts)
         else:
-            make_batch(self.corpus, pidx, self.pad, separate_caption=True, out=hit[0])
+            make_batch(self.corpus, pidx, self.pad, separate_caption=True, out=hit[0], cut_a=cut_a, rng=rng)
         hit[1].refresh_norms_eager()
         hit[0]._norms_global = hit[1]._norms        # [target tokens, auto-encoder tokens] the step's loss is divided by (all ranks)
         return hit[1](), hit[0]
