@@ -493,10 +493,13 @@ class MegaDecodeSession(DecodeSession):
         return results
 
     def greedy(self, start):
-        """argmax decoding of the session's (one) dialogue as one graph replay: a beam of one that skips nothing and finishes nothing
-        (mtn_beam_advance with beam = k = 1, no <unk> / <eos>).  Returns the max_len - 1 generated tokens, or None (tie / not applicable)."""
+        """argmax decoding of every dialogue of the session as one graph replay: a beam of one per dialogue that skips nothing and
+        finishes nothing (mtn_beam_advance with beam = k = 1, no <unk> / <eos>; dialogue d's tokens are column d * width of the step
+        log).  Returns D lists of the max_len - 1 generated tokens, or None (tie / not applicable)."""
         log = self._search_log(1, 1, start, -1, -1, 0.0, self.max_len + 1, self.select[1] if self.select is not None else 0)
-        return None if log is None else [int(t) for t in log[1][:self.max_len - 1, 0]]
+        if log is None:
+            return None
+        return [[int(t) for t in log[1][:self.max_len - 1, d_ * self.width]] for d_ in range(self.D)]
 
     def _search_log(self, beam, k, start, unk, eos, penalty, min_len, extra_col):
         """A whole beam search (data_utils.py:188-242) for every dialogue of the session as ONE graph replay: max_len x [persistent decode
@@ -842,6 +845,7 @@ def _greedy(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache
     ys = [start_symbol]
     if isinstance(sess, MegaDecodeSession) and sess.select is not None:
         toks = sess.greedy(start_symbol)                   # the whole decode as one graph replay (None: a tie in some row's head)
+        toks = None if toks is None else toks[0]
         if toks is None:
             # step by step: the row's head (largest log-probability, its column) arrives in a pinned block — one replay and one
             # stream synchronisation per token, no argmax launch, no .item()
@@ -854,4 +858,40 @@ def _greedy(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache
     for _ in range(max_len - 1):
         nxt = int(sess.step([ys]).argmax(dim=-1)[0])
         ys.append(nxt)
+    return ys
+
+
+def greedy_decode_many(model, batch, max_len, start_symbol, pad_symbol=1, use_graph=True, kv_cache=None):
+    """greedy_decode for a Batch of D dialogues at once: (D, max_len) tokens incl. <sos>, row d equal to greedy_decode on
+    dialogue d alone.  On the persistent step the D argmax searches are ONE graph replay; otherwise the D rows are the batch
+    dimension of one target-stream pass per token."""
+    auto = kv_cache is None
+    ys = _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto)
+    if ys is None:                   # the persistent step timed out: the launch-per-sublayer pass
+        ys = _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, False)
+    return torch.tensor(ys, dtype=batch.query.dtype, device=batch.query.device)
+
+
+def _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto):
+    sess = _session(model, batch, max_len, 1, pad_symbol, use_graph, max_len > KV_CACHE_FROM if kv_cache is None else kv_cache,
+                    select=(2, 0) if auto else None, mega=auto)
+    D = sess.D
+    ys = [[start_symbol] for _ in range(D)]
+    if isinstance(sess, MegaDecodeSession) and sess.select is not None:
+        toks = sess.greedy(start_symbol)
+        if toks is None:
+            # a tie in some row's head: step by step, every dialogue's row head from the pinned block (row d = dialogue d at width 1)
+            rows = list(range(D))
+            for l in range(1, max_len):
+                sess.step_extend(l, rows, [y[-1] for y in ys], rows)
+                top = sess.top_host()
+                for d_ in rows:
+                    ys[d_].append(int(top[d_, 2]))
+        else:
+            ys = [[start_symbol] + t for t in toks]
+        return None if _mega_failed(sess) else ys
+    for _ in range(max_len - 1):
+        logp = torch.cat(sess.step_many([[y] for y in ys]), 0)
+        for y, nxt in zip(ys, logp.argmax(dim=-1).tolist()):
+            y.append(int(nxt))
     return ys

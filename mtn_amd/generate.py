@@ -1,0 +1,326 @@
+#!/usr/bin/env python
+"""Response generation with the reference's generate.py flags (generate.py:91-115), so that the `python generate.py ...` line of
+run.sh:156-168 (stage 3) decodes a test set on this implementation and writes the result JSON that stage 4 scores.
+
+The reference decodes one QA at a time, each at its own padded shape.  Here a search over D dialogues side by side costs about
+as much as a search over one, but decode sessions and their captured graphs are cached per padded shape (decode._session).  So
+the QAs are planned first:
+
+* every QA gets a bucket key: its frame counts rounded up to FRAME_STEP, its history / question / caption lengths rounded up to
+  TEXT_STEP (DESIGN.md §10 gives the grid and the bucket count it yields on the AVSD test lengths); a first turn's history (the
+  lone, masked <blank>) keeps its length of one;
+* each bucket is cut into groups of D QAs; the last group is padded with copies of its last QA (their results are dropped), so
+  every search of a bucket has one shape and reuses one session and one captured search graph;
+* buckets are decoded one after another (the session cache never thrashes), each group's Batch is assembled on the device by
+  make_batch into the same tensors (``out=``), and the results go back to qa_id order before output.
+
+Padding does not change a search: padded keys are masked to -1e9 and padded frames are zeroed and masked, as in the reference's
+own batches — except in a row whose keys are ALL masked, hence the exception above (tests/test_generate_gpu.py compares every QA with its own unpadded single-QA search).
+"""
+import argparse
+import copy
+import json
+import logging
+import pickle
+import time
+from collections import OrderedDict
+
+FRAME_STEP = 64          # bucket grid: frame counts of every feature type rounded up to a multiple of this
+TEXT_STEP = 32           # ... history, question and caption lengths to a multiple of this
+LAUNCH_PASS_D = 8        # dialogues per search where the persistent decode step does not apply (launch-per-sublayer pass)
+
+# the reference train.py's defaults (train.py:57-96) for fields a conf may lack (confs written by older versions)
+REFERENCE_TRAIN_DEFAULTS = dict(fea_type=None, include_caption="none", separate_caption=False, cut_a=0, merge_source=0,
+                                exclude_video=False, fixed_word_emb=0, nb_blocks=6, d_model=512, d_ff=2048, att_h=8, dropout=0.1,
+                                separate_his_embed=0, separate_cap_embed=0, diff_encoder=0, diff_embed=0, diff_gen=0,
+                                auto_encoder_ft=None, max_length=20, max_history_length=-1)
+
+
+def parse(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--gpu", "-g", default=0, type=int, help="GPU ID (negative value indicates CPU)")
+    p.add_argument("--test-path", default="", type=str, help="Path to test feature files")
+    p.add_argument("--test-set", default="", type=str, help="Filename of test data")
+    p.add_argument("--model-conf", default="", type=str, help="Attention model to be output")
+    p.add_argument("--model", "-m", default="", type=str, help="Attention model to be output")
+    p.add_argument("--maxlen", default=30, type=int, help="Max-length of output sequence")
+    p.add_argument("--beam", default=3, type=int, help="Beam width")
+    p.add_argument("--penalty", default=2.0, type=float, help="Insertion penalty")
+    p.add_argument("--nbest", default=5, type=int, help="Number of n-best hypotheses")
+    p.add_argument("--output", "-o", default="", type=str, help="Output generated responses in a json file")
+    p.add_argument("--verbose", "-v", default=0, type=int, help="verbose level")
+    p.add_argument("--decode-style", default="greedy", type=str, help="greedy or beam_search")
+    p.add_argument("--undisclosed-only", default=0, type=int, help="")
+    # (nargs="?": run.sh passes `--labeled-test ${labeled_test}` with labeled_test='' by default, i.e. the bare flag)
+    p.add_argument("--labeled-test", default=None, nargs="?", type=str, help="directory to labelled data")
+    # this implementation
+    p.add_argument("--compute-dtype", default="bf16", choices=["bf16", "fp32"])
+    p.add_argument("--dialogues-per-search", default=0, type=int,
+                   help="QAs decoded side by side in one search; 0 = the most the persistent decode step takes (16 rows: 16 // beam "
+                        "for beam search, 16 for greedy), %d where it does not apply" % LAUNCH_PASS_D)
+    p.add_argument("--no-buckets", action="store_true",
+                   help="one QA per search at its own padded shape, as the reference decodes (baseline / debugging)")
+    args = p.parse_args(argv)
+    args.undisclosed_only = bool(args.undisclosed_only)
+    if args.decode_style not in ("greedy", "beam_search"):
+        p.error("--decode-style must be greedy or beam_search")
+    return args
+
+
+# ---------------------------------------------------------------------------------------------------------------- model
+def load_conf(path):
+    """<model>.conf = pickled (vocab, argparse.Namespace), as the reference's or this project's train.py writes it.  Fields an
+    older conf lacks take the reference train.py's defaults."""
+    with open(path, "rb") as f:
+        vocab, train_args = pickle.load(f)
+    for k, v in REFERENCE_TRAIN_DEFAULTS.items():
+        if not hasattr(train_args, k):
+            setattr(train_args, k, v)
+    return vocab, train_args
+
+
+def load_state_dict(path):
+    """A state_dict in the reference's key schema.  The reference's own train.py pickles the whole nn.Module (train.py:183): that
+    needs the reference's classes to unpickle and is refused with a recipe to extract its state_dict."""
+    import torch
+    how = ("%s holds a pickled nn.Module (what the reference's train.py saves), not a state_dict.  Extract its state_dict where the "
+           "reference's mtn.py is importable:\n    python -c \"import torch; m = torch.load('%s', weights_only=False); "
+           "torch.save(m.state_dict(), '%s')\"\nand pass that file's prefix to --model." % (path, path, path))
+    try:
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+    except Exception as e:        # weights_only refuses any pickled class that is not a tensor container
+        raise SystemExit(how + "\n(torch.load: %s)" % str(e).splitlines()[0]) from None
+    if isinstance(sd, torch.nn.Module) or not isinstance(sd, dict) or not all(isinstance(v, torch.Tensor) for v in sd.values()):
+        raise SystemExit(how)
+    return sd
+
+
+def build_model(vocab, train_args, ft_sizes, state_dict, compute_dtype, device):
+    from . import make_model
+    a = train_args
+    model = make_model(len(vocab), len(vocab), N=a.nb_blocks, d_model=a.d_model, d_ff=a.d_ff, h=a.att_h, dropout=a.dropout,
+                       separate_his_embed=bool(a.separate_his_embed), separate_cap_embed=bool(a.separate_cap_embed),
+                       ft_sizes=ft_sizes, diff_encoder=bool(a.diff_encoder), diff_embed=bool(a.diff_embed), diff_gen=bool(a.diff_gen),
+                       auto_encoder_ft=a.auto_encoder_ft, compute_dtype=compute_dtype)
+    res = model.load_state_dict(state_dict, strict=False)
+    params = {n for n, _ in model.named_parameters()}
+    missing = [k for k in res.missing_keys if k in params]
+    if missing:
+        raise SystemExit("checkpoint does not fit the conf's model: %d parameter(s) missing, e.g. %s" % (len(missing), missing[:4]))
+    model.to(device).eval()
+    model.prepare()
+    return model
+
+
+# ---------------------------------------------------------------------------------------------------------------- planning
+def qa_lengths(data):
+    """Per qa_id: (frame counts per feature type, history, question, answer, caption) lengths of data_handler.load's items."""
+    out = []
+    for it in sorted(data["dialogs"], key=lambda d: d[1]):
+        vid = it[0]
+        x = tuple(len(f[vid]) if not isinstance(f[vid], tuple) else f[vid][1] for f in (data["features"] or []))
+        out.append((x, len(it[2]), len(it[3]), len(it[4]), len(it[6]) if len(it) > 6 else 0))
+    return out
+
+
+def _up(n, step):
+    return -(-int(n) // step) * step
+
+
+def bucket_key(lens, frame_step=FRAME_STEP, text_step=TEXT_STEP):
+    """(frames per feature type, history, question, caption), each rounded up to its grid step.  A history of one token is the
+    lone <blank> placeholder of a first turn (data_handler.load): every key of it is masked, and attention over a fully masked
+    row averages ALL its keys (the reference's softmax over -1e9 everywhere), so its length is kept exactly."""
+    x, h, q, _, c = lens
+    return tuple(_up(v, frame_step) for v in x), (h if h <= 1 else _up(h, text_step)), _up(q, text_step), _up(c, text_step)
+
+
+def plan_searches(lens, per_search, buckets=True, frame_step=FRAME_STEP, text_step=TEXT_STEP):
+    """Group the QAs (``lens`` = qa_lengths, indexed by qa_id) into searches.  ``per_search``: D, or a function of a bucket's
+    padded lengths -> D.  Returns [(qa_ids, n_real, (x_len, h, q, a, c))]: the first n_real ids are distinct QAs, the rest
+    copies of the last of them; every search of a bucket has the bucket's D and padded lengths.  ``buckets=False``: one QA per
+    search at its own lengths."""
+    if not buckets:
+        return [([i], 1, (list(l[0]), l[1], l[2], l[3], l[4])) for i, l in enumerate(lens)]
+    groups = OrderedDict()
+    for i, l in enumerate(lens):
+        groups.setdefault(bucket_key(l, frame_step, text_step), []).append(i)
+    out = []
+    for key in sorted(groups):
+        ids = groups[key]
+        x, h, q, c = key
+        shape = (list(x), h, q, max(lens[i][3] for i in ids), c)      # (answers: not read by a decode; the longest of the bucket)
+        D = max(1, int(per_search(shape) if callable(per_search) else per_search))
+        for s in range(0, len(ids), D):
+            chunk = ids[s:s + D]
+            out.append((chunk + [chunk[-1]] * (D - len(chunk)), len(chunk), shape))
+    return out
+
+
+def auto_dialogues(model, device, shape, maxlen, width):
+    """The most QAs side by side that the persistent decode step takes at this shape (D x width <= 16 rows, fewer at wide
+    feed-forwards), LAUNCH_PASS_D where it does not apply (fp32 models, unsupported widths)."""
+    import types
+    import torch
+    from .decode import MegaDecodeSession
+    x, h, q, _, c = shape
+    for D in range(MegaDecodeSession.MAX_W // width, 0, -1):
+        e = lambda n: torch.empty(D, max(1, n), device=device)
+        probe = types.SimpleNamespace(query=e(q), his=e(h), cap=e(c), fts=[torch.empty(D, max(1, v), 1, device=device) for v in x])
+        if MegaDecodeSession.supported(model, probe, maxlen, width):
+            return D
+    return LAUNCH_PASS_D
+
+
+# ---------------------------------------------------------------------------------------------------------------- output
+def detokenize(tokens, vocablist, eos):
+    """generate.py:59-64: words up to (not including) the first <eos>."""
+    words = []
+    for w in tokens:
+        if w == eos:
+            break
+        words.append(vocablist[w])
+    return " ".join(words)
+
+
+def greedy_text(ys, vocablist, eos):
+    """generate.py:71-77: greedy output without its leading <sos>, up to <eos>."""
+    return detokenize(list(ys)[1:], vocablist, eos)
+
+
+def build_result(original, undisclosed_only, answers):
+    """{'dialogs': [{'image_id', 'dialog'}]} in file order (generate.py:27-38): every turn, or the last one with undisclosed-only;
+    ``answers[qa_id]`` replaces the answer of the qa_id-th output turn."""
+    dialogs, qa = [], 0
+    for dialog in original["dialogs"]:
+        out = copy.deepcopy(dialog["dialog"][-1:] if undisclosed_only else dialog["dialog"])
+        for turn in out:
+            turn["answer"] = answers[qa]
+            qa += 1
+        dialogs.append({"image_id": dialog["image_id"], "dialog": out})
+    return {"dialogs": dialogs}
+
+
+# ---------------------------------------------------------------------------------------------------------------- decoding
+def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest):
+    """Run the planned searches; returns per qa_id the (n-best list, best score) of beam search or the greedy token list."""
+    from .data_handler import make_batch
+    from .decode import beam_search_decode_many, greedy_decode_many
+    sos, eos, unk, pad = vocab["<sos>"], vocab["<eos>"], vocab["<unk>"], vocab["<blank>"]
+    results = {}
+    batch, batch_shape = None, None
+    for ids, n_real, shape in searches:
+        x, h, q, a, c = shape
+        index = ([vids[i] for i in ids], ids, x, h, q, a, c, len(ids))
+        key = (tuple(x), h, q, a, c, len(ids))
+        batch = make_batch(corpus, index, pad, separate_caption=True, out=batch if key == batch_shape else None)
+        batch_shape = key
+        if decode_style == "beam_search":
+            res = beam_search_decode_many(model, batch, maxlen, sos, unk, eos, pad, beam=beam, penalty=penalty, nbest=nbest, min_len=1)
+        else:
+            res = greedy_decode_many(model, batch, maxlen, sos, pad).cpu().tolist()
+        for i, r in zip(ids[:n_real], res[:n_real]):
+            results[i] = r
+    return results
+
+
+def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0, nbest=5, decode_style="greedy", undisclosed_only=False,
+                      ref_data=None, dialogues_per_search=0, buckets=True):
+    """Decode every QA of ``data`` (data_handler.load) and return the reference's result dict, logging the reference's
+    QS / REF / HYP lines per QA."""
+    vocablist = sorted(vocab.keys(), key=lambda s: vocab[s])
+    eos = vocab["<eos>"]
+    lens = qa_lengths(data)
+    width = beam if decode_style == "beam_search" else 1
+    if dialogues_per_search > 0:
+        per = dialogues_per_search
+    else:
+        per = lambda shape: auto_dialogues(model, corpus.device, shape, maxlen, width)
+    searches = plan_searches(lens, per, buckets=buckets)
+    n_buckets = len({(tuple(s[2][0]),) + tuple(s[2][1:]) for s in searches})
+    logging.info("%d QAs in %d searches over %d padded shapes", len(lens), len(searches), n_buckets)
+    vids = {it[1]: it[0] for it in data["dialogs"]}
+    res = decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest)
+    answers = []
+    qa_id = 0
+    for idx, dialog in enumerate(data["original"]["dialogs"]):
+        vid = dialog["image_id"]
+        out = dialog["dialog"][-1:] if undisclosed_only else dialog["dialog"]
+        ref = None
+        if undisclosed_only and ref_data is not None:
+            rd = ref_data["dialogs"][idx]
+            assert rd["image_id"] == vid
+            ref = rd["dialog"][-1:]
+        for t, qa in enumerate(out):
+            logging.info("%d %s_%d" % (qa_id, vid, t))
+            logging.info("QS: " + qa["question"])
+            logging.info("REF: " + (ref[t]["answer"] if ref is not None else qa["answer"]))
+            r = res[qa_id]
+            if decode_style == "beam_search":
+                pred_out = r[0]
+                hyp = ""
+                for n in range(min(nbest, len(pred_out))):
+                    hypstr = detokenize(pred_out[n][0], vocablist, eos)
+                    logging.info("HYP[%d]: %s  ( %f )" % (n + 1, hypstr, pred_out[n][1]))
+                    if n == 0:
+                        hyp = hypstr
+            else:
+                hyp = greedy_text(r, vocablist, eos)
+                logging.info("HYP: {}".format(hyp))
+            answers.append(hyp)
+            logging.info("-----------------------")
+            qa_id += 1
+    return build_result(data["original"], undisclosed_only, answers)
+
+
+def main(argv=None):
+    args = parse(argv)
+    for arg in vars(args):
+        print("{}={}".format(arg, getattr(args, arg)))
+    logging.basicConfig(level=logging.DEBUG if args.verbose >= 1 else logging.INFO, format="%(asctime)s %(levelname)s: %(message)s")
+    import torch
+    from . import data_handler as dh
+    from . import lib
+    if not torch.cuda.is_available():
+        raise SystemExit("generate: the decode path runs on the GPU (HIP kernels); no GPU is available")
+    lib.load()
+    dev = torch.device("cuda", 0)                     # (as generate.py:133: --gpu is accepted and not used)
+    torch.cuda.set_device(dev)
+    logging.info("Loading model params from " + args.model)
+    vocab, train_args = load_conf(args.model_conf)
+    state = load_state_dict(args.model + ".pth.tar")
+    logging.info("#vocab = %d" % len(vocab))
+    logging.info("Loading test data from " + args.test_set)
+    test_data = dh.load(train_args.fea_type, args.test_path, args.test_set, vocab=vocab, include_caption=train_args.include_caption,
+                        separate_caption=bool(train_args.separate_caption), max_history_length=train_args.max_history_length,
+                        merge_source=bool(train_args.merge_source), undisclosed_only=args.undisclosed_only)
+    if not (len(test_data["dialogs"]) and len(test_data["dialogs"][0]) > 6):
+        raise SystemExit("generate: the model needs the caption as its own stream (a conf with separate_caption 1 and include_caption "
+                         "caption|summary|caption,summary, as run.sh trains it)")
+    model = build_model(vocab, train_args, dh.feature_shape(test_data), state, args.compute_dtype, dev)
+    corpus = dh.DeviceCorpus(test_data, dev)
+    logging.info("#test sample = %d" % len(test_data["dialogs"]))
+    logging.info("-----------------------generate--------------------------")
+    labeled_test = None
+    if args.undisclosed_only and args.labeled_test is not None:
+        with open(args.labeled_test, "r") as f:
+            labeled_test = json.load(f)
+    start_time = time.time()
+    result = generate_response(model, test_data, corpus, vocab, maxlen=args.maxlen, beam=args.beam, penalty=args.penalty, nbest=args.nbest,
+                               decode_style=args.decode_style, undisclosed_only=args.undisclosed_only, ref_data=labeled_test,
+                               dialogues_per_search=args.dialogues_per_search, buckets=not args.no_buckets)
+    wall = time.time() - start_time
+    n_qa = len(test_data["dialogs"])
+    logging.info("----------------")
+    logging.info("wall time = %f" % wall)
+    logging.info("%d QAs, %.1f QA/s" % (n_qa, n_qa / max(wall, 1e-9)))
+    if args.output:
+        logging.info("writing results to " + args.output)
+        with open(args.output, "w") as f:
+            json.dump(result, f, indent=4)
+    logging.info("done")
+    return result
+
+
+if __name__ == "__main__":
+    main()

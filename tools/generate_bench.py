@@ -1,0 +1,99 @@
+#!/usr/bin/env python
+"""QA/s of `python generate.py` (mtn_amd.generate) on a test-set-sized synthetic corpus: N undisclosed-only dialogues with the
+text lengths of the DSTC7-AVSD test set (history of up to 3 earlier turns, caption + summary), vggish (128) and i3d_flow (2048)
+features of 10-40 and 30-180 frames, run.sh's model (6 blocks, d_model 512, d_ff 2048, 8 heads; random weights), beam 5,
+penalty 1.0, maxlen 30.  Three settings: buckets with automatic D, --no-buckets (on the first --no-buckets-qas QAs: it
+captures graphs per QA shape), greedy.  Prints one JSON line.
+
+    python tools/generate_bench.py [--dialogs 1710] [--no-buckets-qas 300]
+"""
+import argparse
+import json
+import os
+import pickle
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def synth(root, n, seed=1):
+    rs = np.random.RandomState(seed)
+    words = ["w%d" % i for i in range(3000)]
+    sent = lambda lo, hi: " ".join(words[i] for i in rs.randint(0, len(words), size=rs.randint(lo, hi + 1)))
+    dialogs = []
+    for v in range(n):
+        turns = [{"question": sent(4, 14), "answer": sent(5, 16)} for _ in range(int(rs.randint(1, 11)))]
+        turns[-1]["answer"] = "__UNDISCLOSED__"
+        dialogs.append({"image_id": "v%05d" % v, "caption": sent(15, 35), "summary": sent(15, 40), "dialog": turns})
+    for ft, F, lo, hi in (("vggish", 128, 10, 40), ("i3d_flow", 2048, 30, 180)):
+        os.makedirs(os.path.join(root, ft))
+        for d in dialogs:
+            np.save(os.path.join(root, ft, d["image_id"] + ".npy"), rs.randn(rs.randint(lo, hi + 1), F).astype(np.float32))
+    path = os.path.join(root, "test_set.json")
+    json.dump({"dialogs": dialogs}, open(path, "w"))
+    vocab = {"<unk>": 0, "<blank>": 1, "<sos>": 2, "<eos>": 3}
+    for w in words:
+        vocab[w] = len(vocab)
+    return path, os.path.join(root, "<FeaType>", "<ImageID>.npy"), vocab
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dialogs", type=int, default=1710)
+    ap.add_argument("--no-buckets-qas", type=int, default=300)
+    ap.add_argument("--maxlen", type=int, default=30)
+    a = ap.parse_args()
+    import logging
+    import torch
+    from mtn_amd import data_handler as dh
+    from mtn_amd import generate as G
+    from mtn_amd import lib, make_model
+    logging.basicConfig(level=logging.WARNING)
+    lib.load()
+    dev = torch.device("cuda:0")
+    with tempfile.TemporaryDirectory() as root:
+        test_set, fea_path, vocab = synth(root, a.dialogs)
+        targs = argparse.Namespace(fea_type=["vggish", "i3d_flow"], include_caption="caption,summary", separate_caption=1,
+                                   max_history_length=3, merge_source=0, nb_blocks=6, d_model=512, d_ff=2048, att_h=8, dropout=0.2,
+                                   separate_his_embed=0, separate_cap_embed=0, diff_encoder=1, diff_embed=0, diff_gen=0,
+                                   auto_encoder_ft="query")
+        with open(os.path.join(root, "mtn.conf"), "wb") as f:
+            pickle.dump((vocab, targs), f, -1)
+        vocab, targs = G.load_conf(os.path.join(root, "mtn.conf"))
+        data = dh.load(targs.fea_type, fea_path, test_set, vocab, include_caption=targs.include_caption, separate_caption=True,
+                       max_history_length=targs.max_history_length, merge_source=False, undisclosed_only=True)
+        torch.manual_seed(1)
+        ft = dh.feature_shape(data)
+        sd = make_model(len(vocab), len(vocab), N=6, d_model=512, d_ff=2048, h=8, ft_sizes=ft, diff_encoder=True,
+                        auto_encoder_ft="query").state_dict()
+        model = G.build_model(vocab, targs, ft, sd, "bf16", dev)
+        corpus = dh.DeviceCorpus(data, dev)
+        lens = G.qa_lengths(data)
+        n = len(lens)
+        out = {"qas": n, "buckets": len({G.bucket_key(l) for l in lens}), "maxlen": a.maxlen, "beam": 5}
+
+        def timed(style, buckets, subset=None):
+            d = data if subset is None else dict(data, dialogs=data["dialogs"][:subset],
+                                                 original={"dialogs": data["original"]["dialogs"][:subset]})
+            torch.cuda.synchronize()
+            t0 = time.time()
+            G.generate_response(model, d, corpus, vocab, maxlen=a.maxlen, beam=5, penalty=1.0, nbest=5, decode_style=style,
+                                undisclosed_only=True, buckets=buckets)
+            torch.cuda.synchronize()
+            dt = time.time() - t0
+            return {"qas": len(d["dialogs"]), "seconds": round(dt, 2), "qa_per_s": round(len(d["dialogs"]) / dt, 1)}
+
+        out["beam5_buckets_auto_d"] = timed("beam_search", True)
+        out["greedy_buckets_auto_d"] = timed("greedy", True)
+        out["beam5_no_buckets"] = timed("beam_search", False, min(n, a.no_buckets_qas))
+        from mtn_amd.decode import MegaDecodeSession
+        out["persistent_step_fallbacks"] = MegaDecodeSession.FALLBACKS
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
