@@ -121,7 +121,8 @@ __global__ __launch_bounds__(256) void losshead_bwd_kernel(const mtn_losshead_ar
 
 extern "C" int mtn_losshead_fwd(const mtn_losshead_args* A, void* stream) {
     MTN_CHECK_ARG(A && A->n_seg >= 1 && A->n_seg <= MTN_LOSSHEAD_MAX_SEG, "bad segment count");
-    MTN_CHECK_ARG(A->V >= 4 && A->V % 4 == 0 && A->ldz % 4 == 0 && A->pad >= 0 && A->pad < A->V, "V and ldz must be multiples of 4");
+    MTN_CHECK_ARG(A->V >= 4 && A->V % 4 == 0 && A->ldz % 4 == 0 && A->ldz >= A->V, "V and ldz must be multiples of 4, ldz >= V >= 4");
+    MTN_CHECK_ARG(A->pad >= 0 && A->pad < A->V, "pad outside [0, V)");
     MTN_CHECK_ARG(A->logits && A->lse && A->rowloss, "null buffer");
     int total = 0;
     for (int s = 0; s < A->n_seg; ++s) { MTN_CHECK_ARG(A->rows[s] > 0 && A->target[s] && A->norm[s], "bad segment"); total += A->rows[s]; }
@@ -133,10 +134,12 @@ extern "C" int mtn_losshead_fwd(const mtn_losshead_args* A, void* stream) {
 extern "C" int mtn_losshead_bwd(int dtype, const mtn_losshead_args* A, void* stream) {
     MTN_CHECK_ARG(dtype == MTN_F32 || dtype == MTN_BF16, "bad dtype");
     MTN_CHECK_ARG(A && A->n_seg >= 1 && A->n_seg <= MTN_LOSSHEAD_MAX_SEG, "bad segment count");
-    MTN_CHECK_ARG(A->V % 4 == 0 && A->ldz % 4 == 0 && A->ldd % 4 == 0 && A->ldd >= A->V, "V, ldz, ldd must be multiples of 4");
+    MTN_CHECK_ARG(A->V >= 4 && A->V % 4 == 0 && A->ldz % 4 == 0 && A->ldz >= A->V, "V and ldz must be multiples of 4, ldz >= V >= 4");
+    MTN_CHECK_ARG(A->ldd % 4 == 0 && A->ldd >= A->V, "ldd must be a multiple of 4, ldd >= V");
+    MTN_CHECK_ARG(A->pad >= 0 && A->pad < A->V, "pad outside [0, V)");
     MTN_CHECK_ARG(A->logits && A->lse && A->gloss && A->dlogits, "null buffer");
     int total = 0;
-    for (int s = 0; s < A->n_seg; ++s) total += A->rows[s];
+    for (int s = 0; s < A->n_seg; ++s) { MTN_CHECK_ARG(A->rows[s] > 0 && A->target[s] && A->norm[s], "bad segment"); total += A->rows[s]; }
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MTN_BF16) hipLaunchKernelGGL((losshead_bwd_kernel<bf16_t>), dim3((total + 3) / 4), dim3(256), 0, st, *A, total);
     else hipLaunchKernelGGL((losshead_bwd_kernel<float>), dim3((total + 3) / 4), dim3(256), 0, st, *A, total);
