@@ -582,6 +582,35 @@ typedef struct {
     int* log_parent; int* log_tok; double* log_score; double* log_done; int* log_n_old; int* log_n_new;
 } mtn_beam_args;
 int mtn_beam_advance(const mtn_beam_args* args /* host */, void* stream);
+/* Sampling decode (version 115): one drawn token per row of logp [rows, V] (fp32 log-probabilities, row stride ldx; ldx = 0: every row
+ * reads the same distribution; V < 2^24), one workgroup per row.  With l = step[row], the row's position:
+ *   1. ban     the n_banned <= 4 ids in banned[], and eos while l < min_len, get probability 0;
+ *   2. T       p_i ~ exp((logp_i - max) / temperature), temperature > 0 (max over what is not banned);
+ *   3. top-k   top_k = 0 (or >= V): off; otherwise keep every token whose logp is >= the k-th largest — ties at the threshold are
+ *              all kept, so the kept set depends on no sort order; any k up to V;
+ *   4. top-p   top_p = 1: off; otherwise, over what top-k kept, keep { i : p_i >= t* }, t* the largest threshold whose kept mass is
+ *              >= top_p x the mass — ties all kept;
+ *   5. draw    u = (hash(seed, key[row], l) >> 8) / 2^24, a pure integer counter hash (csrc/sample.hip sample_hash); the token is the
+ *              first kept index, in vocabulary order, whose running kept mass exceeds u x kept mass.  The arg-max of what is not
+ *              banned is always kept, so a draw always exists.
+ * seed, key and step are DEVICE memory (kernel arguments are frozen into a captured graph; one graph serves every search of a shape).
+ * Per row the call logs, at [l][row] of the [L][rows] logs, the token, logp[token] (the model's log-probability, not the filtered
+ * one) and u, and sets step[row] = l + 1; a row whose step is outside [0, L) is left alone.  With tokens / pos / anc (as
+ * mtn_decode_args; each may be NULL) it also writes what the next mtn_decode_step reads: tokens[row] = the token,
+ * anc[row][l + 1] = row (identity ancestors), *pos = l + 1.  Rows go on after <eos>: the caller cuts there. */
+typedef struct {
+    int rows, V; long ldx;
+    const float* logp;
+    float temperature; int top_k; float top_p;
+    int n_banned; int banned[4]; int eos, min_len;
+    const long* seed;           /* device: 1 */
+    const long* key;            /* device: [rows] */
+    int* step;                  /* device: [rows] */
+    int L;
+    int* log_tok; float* log_logp; float* log_u;  /* device: [L][rows] */
+    long* tokens; int* pos; int* anc;             /* as mtn_decode_args, or NULL */
+} mtn_sample_args;
+int mtn_sample_rows(const mtn_sample_args* args /* host */, void* stream);
 /* Generator (mtn.py:62-69) at inference: out[row][c] = x[row][c] - logsumexp(x[row][0..V-1]) over logit rows x [rows, V] (row
  * strides ldx / ldo; out may be x).  The logits themselves are one mtn_gemm (x W^T + b, fp32 out). */
 int mtn_log_softmax_rows(const float* x, int rows, int V, long ldx, float* out, long ldo, void* stream);

@@ -582,6 +582,71 @@ class MegaDecodeSession(DecodeSession):
             return None
         return None if self._log_views[6][0] else self._log_views
 
+    def sample_log(self, start, seed, keys, params):
+        """A whole sampling search for every row of the session as ONE graph replay: max_len x [persistent decode step, generator,
+        mtn_sample_rows (csrc/sample.hip)] — no row heads, no hypothesis bookkeeping: every row starts at <sos>, draws its next token on the
+        device and keeps its own cache slots (identity ancestors).  seed and keys enter through one small pinned block (kernel arguments are
+        frozen into the graph, and one graph serves every search of the session's shape); the step log [token | logp[token] | u], each
+        (max_len, rows), is copied out at the end and the host synchronises once.  ``params``: the keyword arguments of ops.sample_args.
+        Returns the three host views, or None after a poll timeout (timed_out() tells)."""
+        import ctypes as C
+        import numpy as np
+        from . import lib as L
+        if not self.use_graph:
+            raise ValueError("the sampling search on the persistent step is a captured graph")
+        W, Lm = self._W, self.max_len
+        key = (start,) + tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in params.items()))
+        if getattr(self, "_sample_key", None) != key:
+            dev = self._x.device
+            # [seed (int64) | keys (W int64) | step (W int32)]: the pinned image the host fills per search, and its device copy
+            nst = 8 + 8 * W + 4 * W
+            self._sstate = torch.zeros(nst, device=dev, dtype=torch.uint8)
+            self._sstate_host = torch.zeros(nst, dtype=torch.uint8).pin_memory()
+            hs = self._sstate_host.numpy()
+            self._h_seed, self._h_keys = hs[:8].view(np.int64), hs[8:8 + 8 * W].view(np.int64)
+            blk = np.zeros(self._host.numel(), dtype=np.uint8)               # [tokens | pos | anc] before the first step: <sos> in every row
+            blk[:8 * W].view(np.int64)[:] = start
+            blk[self._off_anc:].view(np.int32).reshape(W, Lm)[:] = np.arange(W, dtype=np.int32)[:, None]
+            self._sblk_init = torch.from_numpy(blk).pin_memory()
+            self._slog = torch.zeros(3, Lm, W, device=dev, dtype=torch.int32)   # (the two float logs are viewed as such)
+            self._slog_host = torch.zeros(3, Lm, W, dtype=torch.int32).pin_memory()
+            hl = self._slog_host.numpy()
+            self._slog_views = (hl[0], hl[1].view(np.float32), hl[2].view(np.float32))
+            s0, p0 = self._sstate, self._devblk.data_ptr()
+            log = (self._slog[0], self._slog[1].view(torch.float32), self._slog[2].view(torch.float32))
+
+            def body():
+                self._devblk.copy_(self._sblk_init, non_blocking=True)
+                self._sstate.copy_(self._sstate_host, non_blocking=True)
+                g = self.model.generator._fused
+                for _ in range(Lm):
+                    L.check(L.load().mtn_decode_step(C.byref(self._args), self._stages_dev.data_ptr(), self._grid, L.stream_ptr()))
+                    logp = ops.generator_log_probs(self._out_lp, g["w_lp"], g["bias"])
+                    ops.sample_rows(logp, s0[:8].view(torch.int64), s0[8:8 + 8 * W].view(torch.int64), s0[8 + 8 * W:].view(torch.int32), log,
+                                    tokens=p0, pos=p0 + self._off_pos, anc=p0 + self._off_anc, **params)
+                self._slog_host.copy_(self._slog, non_blocking=True)
+
+            self._h_seed[0], self._h_keys[:] = 0, 0
+            with torch.no_grad():
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    body()
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                self._sample_graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self._sample_graph):
+                    body()
+            self._sample_key = key
+        self._h_seed[0] = seed
+        self._h_keys[:] = keys
+        self._sample_graph.replay()
+        self._prev = None
+        torch.cuda.current_stream().synchronize()
+        if self.timed_out():                 # the log is garbage: the caller sees timed_out() and falls back
+            return None
+        return self._slog_views
+
     def timed_out(self) -> bool:
         """True if a poll of any step since the session was built (or last recovered) timed out: the results since then are garbage."""
         return int(self._sync[1].item()) != 0
@@ -660,12 +725,14 @@ KV_CACHE_FROM = 32      # prefix K/V cache by default for searches longer than t
                         # pass is launch-latency-bound and as fast; the cache makes a token cost O(l) instead of O(l^2) work beyond it)
 
 
-def _session(model, batch, max_len, width, pad, use_graph, kv_cache=False, select=None, mega=False) -> DecodeSession:
+def _session(model, batch, max_len, width, pad, use_graph, kv_cache=False, select=None, mega=False, mode=None) -> DecodeSession:
     """Sessions are kept per (model, shapes): a dialogue with the shapes of an earlier one reuses its buffers and graph.
     The cache is dropped when the model's weights change (prepare() version) or it grows past a few shapes."""
     model.prepare()
     mega = bool(mega) and MegaDecodeSession.supported(model, batch, max_len, width)
     key = DecodeSession.signature(model, batch, max_len, width) + (bool(use_graph), bool(kv_cache), select, mega)
+    if mode is not None:             # (a sampling session is not a select session with select = None: its rows are samples, not hypotheses)
+        key += (mode,)
     ver = getattr(model, "_flat_version", None)
     hit = _SESSIONS.get(key)
     if hit is not None and hit[1] == ver and hit[0].model is model:
@@ -895,3 +962,79 @@ def _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_
         for y, nxt in zip(ys, logp.argmax(dim=-1).tolist()):
             y.append(int(nxt))
     return ys
+
+
+def sample_decode_many(model, batch, max_len, start, eos, pad, *, samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, keys=None,
+                       banned=(), min_len=1, penalty=0.0, use_graph=True, kv_cache=None, trace=None):
+    """Stochastic decoding of a Batch of D dialogues x ``samples`` draws each (temperature / top-k / nucleus; include/mtn_hip.h
+    mtn_sample_rows defines the filters).  Row d * samples + s draws with the random stream of key keys[d] * samples + s (keys: 0..D-1
+    by default) under ``seed``: a pure function of (seed, key, position), so a dialogue's samples do not depend on what it is batched with.
+    Every row starts at <sos> and is cut at its first <eos> (at max_len - 1 tokens without one); <eos> cannot be drawn before ``min_len``
+    tokens, ``banned`` ids never.
+    Returns per dialogue its (tokens up to <eos>, score) pairs, best first: score = sum of the drawn tokens' log-probabilities (the
+    model's, <eos> included) + penalty * (len + 1) — a finished beam hypothesis' formula.  temperature = 0 means top_k = 1.
+    On the persistent step (<= 16 rows, bf16) the whole search is one graph replay; elsewhere the launch-per-sublayer pass runs per token
+    and the same kernel draws from its rows.  ``trace``: a list that receives (row keys, tokens, log-probabilities, u), each log
+    (max_len, rows), of this search."""
+    D, S = batch.query.size(0), int(samples)
+    if S < 1 or len(banned) > 4:
+        raise ValueError("sample_decode_many: samples >= 1, at most 4 banned tokens")
+    if temperature == 0:
+        temperature, top_k = 1.0, 1
+    if not (temperature > 0 and top_k >= 0 and 0 < top_p <= 1):
+        raise ValueError("sample_decode_many: temperature >= 0, top_k >= 0, 0 < top_p <= 1")
+    keys = list(range(D)) if keys is None else [int(k) for k in keys]
+    if len(keys) != D:
+        raise ValueError("one key per dialogue")
+    row_keys = [k * S + s for k in keys for s in range(S)]
+    params = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), banned=tuple(int(b) for b in banned), eos=int(eos),
+                  min_len=int(min_len))
+    auto = kv_cache is None
+    log = _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, auto)
+    if log is None:                  # a poll of the persistent step timed out: the launch-per-sublayer pass
+        log = _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, False)
+    tok, lp, u = log
+    if trace is not None:
+        trace.append((list(row_keys), tok.copy(), lp.copy(), u.copy()))
+    results = []
+    for d in range(D):
+        hyps = []
+        for r in range(d * S, d * S + S):
+            col = [int(t) for t in tok[:, r]]
+            # tokens before <eos>; a row without one keeps max_len - 1 tokens, the longest a beam hypothesis (and the greedy output) gets
+            n = col.index(eos) if eos in col else len(col) - 1
+            used = n + 1 if eos in col else n
+            hyps.append((col[:n], float(lp[:used, r].astype("float64").sum()) + penalty * (n + 1)))
+        results.append(sorted(hyps, key=lambda h: -h[1]))
+    return results
+
+
+def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, mega):
+    """The step log (tokens, log-probabilities, u — numpy, (max_len, rows)) of one sampling search, or None after a persistent-step timeout."""
+    import numpy as np
+    sess = _session(model, batch, max_len, S, pad, use_graph, max_len > KV_CACHE_FROM if kv_cache is None else kv_cache, select=None,
+                    mega=mega and use_graph, mode="sample")
+    if isinstance(sess, MegaDecodeSession):
+        log = sess.sample_log(start, seed, row_keys, params)
+        if _mega_failed(sess):
+            return None
+        return log
+    W, D = sess.D * S, sess.D
+    dev = batch.query.device
+    st = getattr(sess, "_sample_state", None)
+    if st is None:                   # [seed | keys | step] and the log, per session
+        st = sess._sample_state = (torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(W, dtype=torch.int64, device=dev),
+                                   torch.zeros(W, dtype=torch.int32, device=dev),
+                                   (torch.zeros(max_len, W, dtype=torch.int32, device=dev), torch.zeros(max_len, W, device=dev),
+                                    torch.zeros(max_len, W, device=dev)))
+    seed_t, keys_t, step_t, log = st
+    seed_t.fill_(int(seed))
+    keys_t.copy_(torch.tensor(row_keys, dtype=torch.int64))
+    step_t.zero_()
+    prefixes = [[start] for _ in range(W)]
+    for l in range(max_len):
+        sess.step_many([prefixes[d * S:d * S + S] for d in range(D)])
+        ops.sample_rows(sess.logp, seed_t, keys_t, step_t, log, **params)      # the session's rows ARE d * S + s: all of them live
+        for p, t in zip(prefixes, log[0][l].tolist()):
+            p.append(int(t))
+    return tuple(t.cpu().numpy() for t in log)

@@ -27,6 +27,7 @@ from collections import OrderedDict
 
 FRAME_STEP = 64          # bucket grid: frame counts of every feature type rounded up to a multiple of this
 TEXT_STEP = 32           # ... history, question and caption lengths to a multiple of this
+MAX_SAMPLES = 16         # --samples: the samples of a QA ride in one search (decode.MegaDecodeSession.MAX_W rows)
 LAUNCH_PASS_D = 8        # dialogues per search where the persistent decode step does not apply (launch-per-sublayer pass)
 
 # the reference train.py's defaults (train.py:57-96) for fields a conf may lack (confs written by older versions)
@@ -49,7 +50,7 @@ def parse(argv=None):
     p.add_argument("--nbest", default=5, type=int, help="Number of n-best hypotheses")
     p.add_argument("--output", "-o", default="", type=str, help="Output generated responses in a json file")
     p.add_argument("--verbose", "-v", default=0, type=int, help="verbose level")
-    p.add_argument("--decode-style", default="greedy", type=str, help="greedy or beam_search")
+    p.add_argument("--decode-style", default="greedy", type=str, help="greedy, beam_search or sample")
     p.add_argument("--undisclosed-only", default=0, type=int, help="")
     # (nargs="?": run.sh passes `--labeled-test ${labeled_test}` with labeled_test='' by default, i.e. the bare flag)
     p.add_argument("--labeled-test", default=None, nargs="?", type=str, help="directory to labelled data")
@@ -57,13 +58,23 @@ def parse(argv=None):
     p.add_argument("--compute-dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--dialogues-per-search", default=0, type=int,
                    help="QAs decoded side by side in one search; 0 = the most the persistent decode step takes (16 rows: 16 // beam "
-                        "for beam search, 16 for greedy), %d where it does not apply" % LAUNCH_PASS_D)
+                        "for beam search, 16 for greedy, 16 // samples for sample), %d where it does not apply" % LAUNCH_PASS_D)
+    # --decode-style sample: stochastic decoding on the device (temperature / top-k / nucleus), --samples draws per QA, best first
+    p.add_argument("--temperature", default=1.0, type=float, help="sample: softmax temperature (0 = arg-max)")
+    p.add_argument("--top-k", default=0, type=int, help="sample: keep the k most probable tokens (ties kept; 0 = off)")
+    p.add_argument("--top-p", default=1.0, type=float, help="sample: nucleus, the smallest set of tokens with this mass (1 = off)")
+    p.add_argument("--samples", default=1, type=int, help="sample: responses drawn per QA (at most %d); the best-scoring one is the answer" % MAX_SAMPLES)
+    p.add_argument("--sample-seed", default=1, type=int, help="sample: seed of the random streams (a QA's stream depends on the seed and its qa_id only)")
     p.add_argument("--no-buckets", action="store_true",
                    help="one QA per search at its own padded shape, as the reference decodes (baseline / debugging)")
     args = p.parse_args(argv)
     args.undisclosed_only = bool(args.undisclosed_only)
-    if args.decode_style not in ("greedy", "beam_search"):
-        p.error("--decode-style must be greedy or beam_search")
+    if args.decode_style not in ("greedy", "beam_search", "sample"):
+        p.error("--decode-style must be greedy, beam_search or sample")
+    if not 1 <= args.samples <= MAX_SAMPLES:
+        p.error("--samples must be in [1, %d] (the rows of one persistent decode step)" % MAX_SAMPLES)
+    if args.temperature < 0 or args.top_k < 0 or not 0 < args.top_p <= 1:
+        p.error("--temperature >= 0, --top-k >= 0, 0 < --top-p <= 1")
     return args
 
 
@@ -202,8 +213,10 @@ def build_result(original, undisclosed_only, answers):
 
 
 # ---------------------------------------------------------------------------------------------------------------- decoding
-def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest):
-    """Run the planned searches; returns per qa_id the (n-best list, best score) of beam search or the greedy token list."""
+def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=None):
+    """Run the planned searches; returns per qa_id the (n-best list, best score) of beam search, the greedy token list, or the
+    samples' (tokens, score) pairs, best first (``sampling``: samples / temperature / top_k / top_p / seed)."""
+    from . import decode
     from .data_handler import make_batch
     from .decode import beam_search_decode_many, greedy_decode_many
     sos, eos, unk, pad = vocab["<sos>"], vocab["<eos>"], vocab["<unk>"], vocab["<blank>"]
@@ -217,6 +230,10 @@ def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, 
         batch_shape = key
         if decode_style == "beam_search":
             res = beam_search_decode_many(model, batch, maxlen, sos, unk, eos, pad, beam=beam, penalty=penalty, nbest=nbest, min_len=1)
+        elif decode_style == "sample":
+            # keys = qa_ids: a QA's random stream is the same in any bucket, at any D, with --no-buckets
+            res = decode.sample_decode_many(model, batch, maxlen, sos, eos, pad, keys=ids, banned=(unk, pad, sos), min_len=1, penalty=penalty,
+                                            **sampling)
         else:
             res = greedy_decode_many(model, batch, maxlen, sos, pad).cpu().tolist()
         for i, r in zip(ids[:n_real], res[:n_real]):
@@ -225,13 +242,15 @@ def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, 
 
 
 def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0, nbest=5, decode_style="greedy", undisclosed_only=False,
-                      ref_data=None, dialogues_per_search=0, buckets=True):
+                      ref_data=None, dialogues_per_search=0, buckets=True, sampling=None):
     """Decode every QA of ``data`` (data_handler.load) and return the reference's result dict, logging the reference's
     QS / REF / HYP lines per QA."""
     vocablist = sorted(vocab.keys(), key=lambda s: vocab[s])
     eos = vocab["<eos>"]
     lens = qa_lengths(data)
-    width = beam if decode_style == "beam_search" else 1
+    if decode_style == "sample":
+        sampling = dict(dict(samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=1), **(sampling or {}))
+    width = beam if decode_style == "beam_search" else (sampling["samples"] if decode_style == "sample" else 1)
     if dialogues_per_search > 0:
         per = dialogues_per_search
     else:
@@ -240,7 +259,7 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
     n_buckets = len({(tuple(s[2][0]),) + tuple(s[2][1:]) for s in searches})
     logging.info("%d QAs in %d searches over %d padded shapes", len(lens), len(searches), n_buckets)
     vids = {it[1]: it[0] for it in data["dialogs"]}
-    res = decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest)
+    res = decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=sampling)
     answers = []
     qa_id = 0
     for idx, dialog in enumerate(data["original"]["dialogs"]):
@@ -256,10 +275,10 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
             logging.info("QS: " + qa["question"])
             logging.info("REF: " + (ref[t]["answer"] if ref is not None else qa["answer"]))
             r = res[qa_id]
-            if decode_style == "beam_search":
-                pred_out = r[0]
+            if decode_style in ("beam_search", "sample"):
+                pred_out = r[0] if decode_style == "beam_search" else r          # (sample: every draw is logged, best first)
                 hyp = ""
-                for n in range(min(nbest, len(pred_out))):
+                for n in range(min(nbest, len(pred_out)) if decode_style == "beam_search" else len(pred_out)):
                     hypstr = detokenize(pred_out[n][0], vocablist, eos)
                     logging.info("HYP[%d]: %s  ( %f )" % (n + 1, hypstr, pred_out[n][1]))
                     if n == 0:
@@ -308,7 +327,9 @@ def main(argv=None):
     start_time = time.time()
     result = generate_response(model, test_data, corpus, vocab, maxlen=args.maxlen, beam=args.beam, penalty=args.penalty, nbest=args.nbest,
                                decode_style=args.decode_style, undisclosed_only=args.undisclosed_only, ref_data=labeled_test,
-                               dialogues_per_search=args.dialogues_per_search, buckets=not args.no_buckets)
+                               dialogues_per_search=args.dialogues_per_search, buckets=not args.no_buckets,
+                               sampling=dict(samples=args.samples, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+                                             seed=args.sample_seed))
     wall = time.time() - start_time
     n_qa = len(test_data["dialogs"])
     logging.info("----------------")

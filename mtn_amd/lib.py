@@ -155,6 +155,13 @@ class BeamArgs(C.Structure):
                 ("log_n_new", C.c_void_p)]
 
 
+class SampleArgs(C.Structure):
+    _fields_ = [("rows", C.c_int), ("V", C.c_int), ("ldx", C.c_long), ("logp", C.c_void_p), ("temperature", C.c_float), ("top_k", C.c_int),
+                ("top_p", C.c_float), ("n_banned", C.c_int), ("banned", C.c_int * 4), ("eos", C.c_int), ("min_len", C.c_int),
+                ("seed", C.c_void_p), ("key", C.c_void_p), ("step", C.c_void_p), ("L", C.c_int), ("log_tok", C.c_void_p),
+                ("log_logp", C.c_void_p), ("log_u", C.c_void_p), ("tokens", C.c_void_p), ("pos", C.c_void_p), ("anc", C.c_void_p)]
+
+
 class LnFinalizeDesc(C.Structure):
     _fields_ = [("partial", C.c_void_p), ("nparts", C.c_int), ("d", C.c_int), ("da2", C.c_void_p), ("db2", C.c_void_p)]
 
@@ -202,6 +209,7 @@ SYMBOLS = {
     "mtn_gemm_tt_table": (C.c_int, [C.c_int, C.c_int, C.POINTER(GemmProblem), _P]),
     "mtn_decode_step": (C.c_int, [C.POINTER(DecodeArgs), _P, C.c_int, _P]),
     "mtn_beam_advance": (C.c_int, [C.POINTER(BeamArgs), _P]),
+    "mtn_sample_rows": (C.c_int, [C.POINTER(SampleArgs), _P]),
     "mtn_debug_hold_cus": (C.c_int, [C.c_int, C.c_int, C.c_int, _P]),
     "mtn_gemm_tt_table_aux": (C.c_int, [C.c_int, C.c_int, C.POINTER(GemmProblem), C.POINTER(TtAux), _P]),
     "mtn_layernorm_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -925,6 +925,51 @@ def topk_rows(x, k, extra_col=-1):
     return out
 
 
+def sample_args(logp, seed, keys, step, log, *, temperature=1.0, top_k=0, top_p=1.0, banned=(), eos=-1, min_len=0, rows=None,
+                tokens=None, pos=None, anc=None):
+    """The argument block of mtn_sample_rows (include/mtn_hip.h) for logp (n, V) fp32: seed (1,) / keys (rows,) int64 and step (rows,)
+    int32 on the device, log = (tokens int32, log-probabilities fp32, u fp32), each (L, rows).  ``rows`` > n with n = 1 makes every
+    row read the one distribution (ldx = 0).  tokens / pos / anc: what the next persistent decode step reads, as pointers or tensors."""
+    _require_cuda(logp, seed, keys, step, *log)
+    if logp.dtype != torch.float32 or logp.stride(-1) != 1 or seed.dtype != torch.int64 or keys.dtype != torch.int64 or step.dtype != torch.int32:
+        raise ValueError("sample_rows: logp fp32 with unit column stride, seed / keys int64, step int32")
+    n, V = logp.shape
+    rows = n if rows is None else int(rows)
+    if rows != n and n != 1:
+        raise ValueError("sample_rows: rows differs from logp's only when one distribution serves every row")
+    banned = [int(b) for b in banned]
+    lt, ll, lu = log
+    if len(banned) > 4 or keys.numel() != rows or step.numel() != rows or seed.numel() != 1:
+        raise ValueError("sample_rows: at most 4 banned tokens; one key and one step per row, one seed")
+    if not (lt.dtype == torch.int32 and ll.dtype == lu.dtype == torch.float32 and lt.shape == ll.shape == lu.shape and lt.dim() == 2
+            and lt.size(1) == rows and all(t.is_contiguous() for t in (lt, ll, lu, keys, step))):
+        raise ValueError("sample_rows: the log is (int32, fp32, fp32), each contiguous (L, rows)")
+    a = L.SampleArgs()
+    a.rows, a.V, a.ldx, a.logp = rows, V, (0 if rows != n else (V if n == 1 else logp.stride(0))), logp.data_ptr()
+    a.temperature, a.top_k, a.top_p = float(temperature), int(top_k), float(top_p)
+    a.n_banned, a.eos, a.min_len = len(banned), int(eos), int(min_len)
+    for i, b in enumerate(banned):
+        a.banned[i] = b
+    a.seed, a.key, a.step, a.L = seed.data_ptr(), keys.data_ptr(), step.data_ptr(), lt.size(0)
+    a.log_tok, a.log_logp, a.log_u = lt.data_ptr(), ll.data_ptr(), lu.data_ptr()
+    as_ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+    a.tokens, a.pos, a.anc = as_ptr(tokens), as_ptr(pos), as_ptr(anc)
+    return a
+
+
+def sample_rows(logp, seed, keys, step, log=None, max_len=1, **kw):
+    """One drawn token per row of logp (n, V) fp32 log-probabilities (csrc/sample.hip; include/mtn_hip.h mtn_sample_rows gives the
+    definitions of ban / temperature / top-k / top-p / draw): row r draws with u = hash(seed, keys[r], step[r]), logs (token,
+    logp[token], u) at [step[r], r] of ``log`` (created as (max_len, rows) when None) and advances step[r].  Returns the log."""
+    rows = kw.get("rows") or logp.size(0)
+    if log is None:
+        log = (torch.zeros(max_len, rows, device=logp.device, dtype=torch.int32), torch.zeros(max_len, rows, device=logp.device),
+               torch.zeros(max_len, rows, device=logp.device))
+    a = sample_args(logp, seed, keys, step, log, **kw)
+    L.check(L.load().mtn_sample_rows(C.byref(a), L.stream_ptr()))
+    return log
+
+
 # ------------------------------------------------------------------------------------------ memory K/V, ahead of the layers
 def project_memories(items, lp_dtype, outs=None):
     """K|V projections (mtn.py:257-258) of CONSTANT memories for many sublayers at once: items = [(mem_lp (B,m,d) compute dtype,

@@ -2,8 +2,9 @@
 """QA/s of `python generate.py` (mtn_amd.generate) on a test-set-sized synthetic corpus: N undisclosed-only dialogues with the
 text lengths of the DSTC7-AVSD test set (history of up to 3 earlier turns, caption + summary), vggish (128) and i3d_flow (2048)
 features of 10-40 and 30-180 frames, run.sh's model (6 blocks, d_model 512, d_ff 2048, 8 heads; random weights), beam 5,
-penalty 1.0, maxlen 30.  Three settings: buckets with automatic D, --no-buckets (on the first --no-buckets-qas QAs: it
-captures graphs per QA shape), greedy.  Prints one JSON line.
+penalty 1.0, maxlen 30.  Settings: buckets with automatic D, --no-buckets (on the first --no-buckets-qas QAs: it
+captures graphs per QA shape), greedy, and --decode-style sample (1 and 4 samples per QA, next to greedy).  Prints one JSON line.
+--styles picks a subset (beam, greedy, no_buckets, sample).
 
     python tools/generate_bench.py [--dialogs 1710] [--no-buckets-qas 300]
 """
@@ -46,6 +47,7 @@ def main():
     ap.add_argument("--dialogs", type=int, default=1710)
     ap.add_argument("--no-buckets-qas", type=int, default=300)
     ap.add_argument("--maxlen", type=int, default=30)
+    ap.add_argument("--styles", default="beam,greedy,no_buckets,sample", help="comma-separated: beam, greedy, no_buckets, sample")
     a = ap.parse_args()
     import logging
     import torch
@@ -76,20 +78,34 @@ def main():
         n = len(lens)
         out = {"qas": n, "buckets": len({G.bucket_key(l) for l in lens}), "maxlen": a.maxlen, "beam": 5}
 
-        def timed(style, buckets, subset=None):
+        def timed(style, buckets, subset=None, sampling=None):
             d = data if subset is None else dict(data, dialogs=data["dialogs"][:subset],
                                                  original={"dialogs": data["original"]["dialogs"][:subset]})
             torch.cuda.synchronize()
             t0 = time.time()
             G.generate_response(model, d, corpus, vocab, maxlen=a.maxlen, beam=5, penalty=1.0, nbest=5, decode_style=style,
-                                undisclosed_only=True, buckets=buckets)
+                                undisclosed_only=True, buckets=buckets, sampling=sampling)
             torch.cuda.synchronize()
             dt = time.time() - t0
             return {"qas": len(d["dialogs"]), "seconds": round(dt, 2), "qa_per_s": round(len(d["dialogs"]) / dt, 1)}
 
-        out["beam5_buckets_auto_d"] = timed("beam_search", True)
-        out["greedy_buckets_auto_d"] = timed("greedy", True)
-        out["beam5_no_buckets"] = timed("beam_search", False, min(n, a.no_buckets_qas))
+        styles = set(a.styles.split(","))
+        if "beam" in styles:
+            out["beam5_buckets_auto_d"] = timed("beam_search", True)
+        if "greedy" in styles:
+            out["greedy_buckets_auto_d"] = timed("greedy", True)
+        if "sample" in styles:
+            # sampling next to greedy, twice each (the first pass of a style captures its graphs), then four samples per QA
+            smp = dict(temperature=1.0, top_k=40, top_p=0.9, seed=1)
+            timed("sample", True, sampling=dict(smp, samples=1))
+            out["greedy_buckets_auto_d_again"] = timed("greedy", True)
+            out["sample1_buckets_auto_d"] = timed("sample", True, sampling=dict(smp, samples=1))
+            out["sample1_plain_buckets_auto_d"] = timed("sample", True, sampling=dict(samples=1))
+            timed("sample", True, sampling=dict(smp, samples=4))
+            out["sample4_buckets_auto_d"] = timed("sample", True, sampling=dict(smp, samples=4))
+            out["sample_over_greedy"] = round(out["sample1_buckets_auto_d"]["qa_per_s"] / out["greedy_buckets_auto_d_again"]["qa_per_s"], 3)
+        if "no_buckets" in styles:
+            out["beam5_no_buckets"] = timed("beam_search", False, min(n, a.no_buckets_qas))
         from mtn_amd.decode import MegaDecodeSession
         out["persistent_step_fallbacks"] = MegaDecodeSession.FALLBACKS
     print(json.dumps(out))
