@@ -43,7 +43,8 @@ const char* mtn_last_error(void);
  * the better of two MFMA shapes.
  * 113 (round 6): mtn_decode_args gained the trailing field `max_m`; mtn_decode_step takes W <= 16 rows, clamps `grid` to the device's
  * compute-unit count and bounds its polls in time (see there).
- * 114: mtn_assemble_tokens_desc gained the trailing field `row_len` (NULL = no cut; a zeroed struct keeps meaning that). */
+ * 114: mtn_assemble_tokens_desc gained the trailing field `row_len` (NULL = no cut; a zeroed struct keeps meaning that).
+ * 115: new entry point mtn_sample_rows.  116: new entry point mtn_score_rows. */
 int mtn_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -611,6 +612,27 @@ typedef struct {
     long* tokens; int* pos; int* anc;             /* as mtn_decode_args, or NULL */
 } mtn_sample_args;
 int mtn_sample_rows(const mtn_sample_args* args /* host */, void* stream);
+/* Candidate scoring (version 116): how likely the model finds GIVEN tokens.  logits [n_seq * L, ldz] (fp32, row stride ldz >= V; columns
+ * V..ldz-1 are never read; 2 <= V < 2^24) are the generator's rows of a teacher-forced pass, target [n_seq, L] the token each position
+ * should produce.  One launch, no atomics; per position (s, l), with z its row and t = target[s][l]:
+ *   tok_logp[s][l] = z[t] - logsumexp(z[0..V-1])     (max-shifted, fp32)
+ *   tok_rank[s][l] = #{c : z[c] > z[t]} + #{c < t : z[c] == z[t]}     (0: t is the arg-max; equal values rank by ascending column, the
+ *                    order mtn_topk_rows documents)
+ * A position whose target is `pad`, or lies outside [0, V), gets tok_logp = 0, tok_rank = -1 and is not counted.  Per sequence:
+ *   seq_logp[s] = sum of tok_logp[s][0..L-1] in ascending position, accumulated in double by one lane (the same bits in every run)
+ *   seq_len[s]  = number of counted positions
+ * A finished beam hypothesis' score (mtn_beam_args log_done; data_utils.py:211-215) is seq_logp + penalty * seq_len when target is the
+ * hypothesis followed by <eos>. */
+typedef struct {
+    int n_seq, L, V, pad; long ldz;
+    const float* logits;        /* [n_seq * L][ldz] */
+    const long* target;         /* [n_seq][L] */
+    float* tok_logp;            /* [n_seq][L] */
+    int* tok_rank;              /* [n_seq][L] */
+    double* seq_logp;           /* [n_seq] */
+    int* seq_len;               /* [n_seq] */
+} mtn_score_args;
+int mtn_score_rows(const mtn_score_args* args /* host */, void* stream);
 /* Generator (mtn.py:62-69) at inference: out[row][c] = x[row][c] - logsumexp(x[row][0..V-1]) over logit rows x [rows, V] (row
  * strides ldx / ldo; out may be x).  The logits themselves are one mtn_gemm (x W^T + b, fp32 out). */
 int mtn_log_softmax_rows(const float* x, int rows, int V, long ldx, float* out, long ldo, void* stream);

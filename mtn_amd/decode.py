@@ -15,6 +15,10 @@ the dialogue (query/caption, video), never on the target prefix.  Here:
   a cross-attention over the cache (keys 0..l enabled); a beam step re-orders hypotheses, so the cache rows follow their
   parents by one gather per token.  Same n-best lists as the full-prefix pass (tested), O(l) instead of O(l^2) work per token;
 * hypothesis bookkeeping stays on the host exactly as in the reference (same candidate order, same tie behaviour).
+
+The opposite question — how likely does the model find a GIVEN response — is ``score_candidates``: the same loaded session, the
+candidates as the rows of ONE teacher-forced pass (``DecodeSession._pass_score``: the generator's logits at every position, then
+csrc/score.hip: per-token log-probability and rank, per-row float64 sum), scored as the beam search scores a finished hypothesis.
 """
 from __future__ import annotations
 
@@ -305,6 +309,61 @@ class DecodeSession:
                         self._pass()
                 self._graph.replay()
         return [self.logp[d * self.width:d * self.width + len(p)] for d, p in enumerate(prefix_lists)]
+
+    def _pass_score(self):
+        """_pass for scoring: the same target-stream pass, but the generator runs at EVERY position — logits only — and
+        mtn_score_rows (csrc/score.hip) reads the targets' log-probabilities and ranks off them: no (rows, V) log-softmax."""
+        m = self.model
+        cap_mask, his_mask, q_mask = self.masks
+        x = m.embed_target(self.tokens)
+        m.attach_memory_kv(self._kv_pairs)
+        try:
+            for k, layer in enumerate(m.decoder.layers):
+                x = layer.forward_target(x, self.cp, cap_mask, self.hs, his_mask, self.q, q_mask, self.trg_mask, self.aes[k],
+                                         m.auto_encoder_ft)
+        finally:
+            m.clear_memory_kv()
+        x = m.decoder.norm(x)
+        z = m.generator.logits(x)                                   # (D * width, max_len, V) fp32
+        ops.score_rows(z.view(-1, z.size(-1)), self._score_target, self.pad, out=self._score_out)
+
+    def score(self, rows_tokens: Sequence[Sequence[int]], start: int, eos: int):
+        """Teacher-forced scores of D * width token lists (row d * width + i belongs to dialogue d; no <sos> / <eos> in them, at most
+        max_len - 1 tokens each): the pass reads [<sos>, c...] and is scored against [c..., <eos>], both padded to max_len.  One
+        pass, captured as a graph of its own.  Returns (tok_logp (rows, max_len), tok_rank, seq_logp (rows,) float64, seq_len) as
+        numpy arrays on the host (include/mtn_hip.h mtn_score_rows defines them)."""
+        W, Lm = self.D * self.width, self.max_len
+        if len(rows_tokens) != W or any(len(c) + 1 > Lm for c in rows_tokens):
+            raise ValueError("one token list per row of the session, each at most max_len - 1 tokens")
+        dev = self.tokens.device
+        if getattr(self, "_score_out", None) is None:
+            self._score_target = torch.full((W, Lm), self.pad, dtype=torch.long, device=dev)
+            self._score_out = (torch.zeros(W, Lm, device=dev), torch.zeros(W, Lm, dtype=torch.int32, device=dev),
+                               torch.zeros(W, dtype=torch.float64, device=dev), torch.zeros(W, dtype=torch.int32, device=dev))
+            self._score_graph = None
+        host = torch.full((2, W, Lm), self.pad, dtype=torch.long)
+        for r, c in enumerate(rows_tokens):
+            c = [int(t) for t in c]
+            host[0, r, :len(c) + 1] = torch.tensor([start] + c, dtype=torch.long)
+            host[1, r, :len(c) + 1] = torch.tensor(c + [eos], dtype=torch.long)
+        self.tokens.copy_(host[0])
+        self._score_target.copy_(host[1])
+        with torch.no_grad():
+            if not self.use_graph:
+                self._pass_score()
+            else:
+                if self._score_graph is None:
+                    side = torch.cuda.Stream()
+                    side.wait_stream(torch.cuda.current_stream())
+                    with torch.cuda.stream(side):
+                        self._pass_score()
+                    torch.cuda.current_stream().wait_stream(side)
+                    torch.cuda.synchronize()
+                    self._score_graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(self._score_graph):
+                        self._pass_score()
+                self._score_graph.replay()
+        return tuple(t.cpu().numpy() for t in self._score_out)
 
 
 class MegaDecodeSession(DecodeSession):
@@ -1038,3 +1097,47 @@ def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params,
         for p, t in zip(prefixes, log[0][l].tolist()):
             p.append(int(t))
     return tuple(t.cpu().numpy() for t in log)
+
+
+def score_candidates(model, batch, candidates, start, eos, pad, *, penalty=0.0, max_len=None, width=None, use_graph=True):
+    """Teacher-forced log-likelihood of GIVEN responses: candidates[d] is a list of token-id lists (no <sos> / <eos>; empty lists
+    allowed; counts may differ) for dialogue d of ``batch``.  The encoder side and the auto-encoder chains run once per call
+    (DecodeSession.load); the candidates are the rows of one teacher-forced pass per ``width`` of them — input [<sos>, c...], target
+    [c..., <eos>] — whose logits mtn_score_rows (csrc/score.hip) turns into per-token log-probabilities and ranks.  ``max_len``: longest
+    candidate + 1 rounded up to a multiple of 8 by default (a candidate that does not fit an explicit one raises ValueError);
+    ``width``: min(most candidates of a dialogue, 32) by default; more candidates run as further passes of the same loaded session, and
+    short rows are filled with copies of the dialogue's last candidate and dropped.
+    Returns per dialogue, in input order, dict(logp, n_tokens, score, token_logp, token_rank): logp = sum of the tokens'
+    log-probabilities, <eos> included (n_tokens counts it), score = logp + penalty * n_tokens — what the beam search assigns the same
+    tokens as a finished hypothesis (data_utils.py:211-215).  token_rank: 0 where the token is the model's arg-max.
+    Launch-per-sublayer pass for both compute dtypes; the persistent step is not involved."""
+    D = batch.query.size(0)
+    if len(candidates) != D:
+        raise ValueError("score_candidates: one candidate list per dialogue of the batch")
+    cands = [[[int(t) for t in c] for c in cs] for cs in candidates]
+    longest = max((len(c) for cs in cands for c in cs), default=0)
+    if max_len is None:
+        max_len = -(-(longest + 1) // 8) * 8
+    elif longest + 1 > max_len:
+        raise ValueError(f"score_candidates: a candidate of {longest} tokens (+ <eos>) does not fit max_len = {max_len}")
+    most = max(len(cs) for cs in cands)
+    results = [[] for _ in range(D)]
+    if most == 0:
+        return results
+    width = min(most, 32) if width is None else int(width)
+    if width < 1:
+        raise ValueError("score_candidates: width >= 1")
+    sess = _session(model, batch, max_len, width, pad, use_graph, False, select=None, mega=False, mode="score")
+    for c0 in range(0, most, width):
+        rows = []
+        for cs in cands:
+            chunk = cs[c0:c0 + width]
+            rows += chunk + [cs[-1] if cs else []] * (width - len(chunk))
+        tok_logp, tok_rank, seq_logp, seq_len = sess.score(rows, start, eos)
+        for d, cs in enumerate(cands):
+            for i, c in enumerate(cs[c0:c0 + width]):
+                r, n = d * width + i, len(c) + 1
+                lp, counted = float(seq_logp[r]), int(seq_len[r])
+                results[d].append(dict(logp=lp, n_tokens=counted, score=lp + penalty * counted,
+                                       token_logp=[float(v) for v in tok_logp[r, :n]], token_rank=[int(v) for v in tok_rank[r, :n]]))
+    return results

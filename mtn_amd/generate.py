@@ -16,6 +16,11 @@ the QAs are planned first:
 
 Padding does not change a search: padded keys are masked to -1e9 and padded frames are zeroed and masked, as in the reference's
 own batches — except in a row whose keys are ALL masked, hence the exception above (tests/test_generate_gpu.py compares every QA with its own unpadded single-QA search).
+
+``--decode-style score`` rides in the same buckets but generates nothing: every QA's candidate responses (``--candidates FILE``; its
+own answer without an entry) are scored by decode.score_candidates — one encoder-side pass per QA, the candidates as rows of a
+teacher-forced pass, csrc/score.hip — logged best first, written into the result JSON as "scores", and summed up as corpus
+perplexity and, where the file names the ground truth, MRR / R@k / mean rank (score_metrics).
 """
 import argparse
 import copy
@@ -50,7 +55,7 @@ def parse(argv=None):
     p.add_argument("--nbest", default=5, type=int, help="Number of n-best hypotheses")
     p.add_argument("--output", "-o", default="", type=str, help="Output generated responses in a json file")
     p.add_argument("--verbose", "-v", default=0, type=int, help="verbose level")
-    p.add_argument("--decode-style", default="greedy", type=str, help="greedy, beam_search or sample")
+    p.add_argument("--decode-style", default="greedy", type=str, help="greedy, beam_search, sample or score")
     p.add_argument("--undisclosed-only", default=0, type=int, help="")
     # (nargs="?": run.sh passes `--labeled-test ${labeled_test}` with labeled_test='' by default, i.e. the bare flag)
     p.add_argument("--labeled-test", default=None, nargs="?", type=str, help="directory to labelled data")
@@ -65,12 +70,18 @@ def parse(argv=None):
     p.add_argument("--top-p", default=1.0, type=float, help="sample: nucleus, the smallest set of tokens with this mass (1 = off)")
     p.add_argument("--samples", default=1, type=int, help="sample: responses drawn per QA (at most %d); the best-scoring one is the answer" % MAX_SAMPLES)
     p.add_argument("--sample-seed", default=1, type=int, help="sample: seed of the random streams (a QA's stream depends on the seed and its qa_id only)")
+    # --decode-style score: nothing is generated — given responses are scored (teacher-forced log-likelihood) and ranked
+    p.add_argument("--candidates", default=None, type=str,
+                   help='score: JSON {"<image_id>_<turn>": {"candidates": ["text", ...], "gt_index": k}} (gt_index optional); a QA '
+                        "without an entry, and every QA without this flag, is scored on its own answer")
     p.add_argument("--no-buckets", action="store_true",
                    help="one QA per search at its own padded shape, as the reference decodes (baseline / debugging)")
     args = p.parse_args(argv)
     args.undisclosed_only = bool(args.undisclosed_only)
-    if args.decode_style not in ("greedy", "beam_search", "sample"):
-        p.error("--decode-style must be greedy, beam_search or sample")
+    if args.decode_style not in ("greedy", "beam_search", "sample", "score"):
+        p.error("--decode-style must be greedy, beam_search, sample or score")
+    if args.candidates is not None and args.decode_style != "score":
+        p.error("--candidates goes with --decode-style score")
     if not 1 <= args.samples <= MAX_SAMPLES:
         p.error("--samples must be in [1, %d] (the rows of one persistent decode step)" % MAX_SAMPLES)
     if args.temperature < 0 or args.top_k < 0 or not 0 < args.top_p <= 1:
@@ -199,23 +210,105 @@ def greedy_text(ys, vocablist, eos):
     return detokenize(list(ys)[1:], vocablist, eos)
 
 
-def build_result(original, undisclosed_only, answers):
+def build_result(original, undisclosed_only, answers, scores=None):
     """{'dialogs': [{'image_id', 'dialog'}]} in file order (generate.py:27-38): every turn, or the last one with undisclosed-only;
-    ``answers[qa_id]`` replaces the answer of the qa_id-th output turn."""
+    ``answers[qa_id]`` replaces the answer of the qa_id-th output turn; ``scores[qa_id]`` (--decode-style score) becomes its "scores"."""
     dialogs, qa = [], 0
     for dialog in original["dialogs"]:
         out = copy.deepcopy(dialog["dialog"][-1:] if undisclosed_only else dialog["dialog"])
         for turn in out:
             turn["answer"] = answers[qa]
+            if scores is not None:
+                turn["scores"] = scores[qa]
             qa += 1
         dialogs.append({"image_id": dialog["image_id"], "dialog": out})
     return {"dialogs": dialogs}
 
 
+# ---------------------------------------------------------------------------------------------------------------- scoring
+def tokenize_answer(text, vocab):
+    """An answer's token ids as data_handler.words2ids gives them, without its <sos> / <eos>: unknown words -> <unk>."""
+    from .data_handler import words2ids
+    return [int(t) for t in words2ids(text, vocab)[1:-1]]
+
+
+def qa_keys(original, undisclosed_only):
+    """Per qa_id (the order of data_handler.load): ("<image_id>_<turn>", the turn's dict) — the key is what the per-QA log line prints."""
+    out = []
+    for dialog in original["dialogs"]:
+        turns = dialog["dialog"][-1:] if undisclosed_only else dialog["dialog"]
+        out += [("%s_%d" % (dialog["image_id"], t), qa) for t, qa in enumerate(turns)]
+    return out
+
+
+def load_candidates(spec, original, vocab, undisclosed_only=False, ref_data=None):
+    """What --decode-style score scores, per qa_id: dict(key, texts, tokens, gt_index, ranked).  ``spec``: the --candidates JSON (a dict,
+    a path to one, or None).  A QA with an entry gets its candidates and its gt_index (None without one; not an index into the
+    candidates: ValueError); every other QA is scored on its own answer (ref_data's with undisclosed-only and a labelled test set),
+    which is then its ground truth but takes no part in the ranking metrics (``ranked`` False)."""
+    if isinstance(spec, str):
+        with open(spec, "r") as f:
+            spec = json.load(f)
+    spec = spec or {}
+    out, per_dialog = [], []                                # per_dialog[qa_id]: the index of its dialogue
+    for idx, dialog in enumerate(original["dialogs"]):
+        per_dialog += [idx] * (1 if undisclosed_only else len(dialog["dialog"]))
+    keys = qa_keys(original, undisclosed_only)
+    unknown = set(spec) - {k for k, _ in keys}
+    if unknown:
+        raise ValueError("candidates: no QA is called %s" % sorted(unknown)[:4])
+    for qa_id, (key, turn) in enumerate(keys):
+        entry = spec.get(key)
+        if entry is None:
+            own = turn["answer"]
+            if undisclosed_only and ref_data is not None:
+                rd = ref_data["dialogs"][per_dialog[qa_id]]
+                assert rd["image_id"] == original["dialogs"][per_dialog[qa_id]]["image_id"]
+                own = rd["dialog"][-1]["answer"]
+            texts, gt, ranked = [own], 0, False
+        else:
+            texts = entry.get("candidates") if isinstance(entry, dict) else None
+            if not isinstance(texts, list) or not texts or not all(isinstance(t, str) for t in texts):
+                raise ValueError("candidates: %s needs a non-empty list of strings under \"candidates\"" % key)
+            gt = entry.get("gt_index")
+            if gt is not None and (isinstance(gt, bool) or not isinstance(gt, int) or not 0 <= gt < len(texts)):
+                raise ValueError("candidates: gt_index of %s is not an index into its %d candidates" % (key, len(texts)))
+            ranked = gt is not None
+        out.append(dict(key=key, texts=list(texts), tokens=[tokenize_answer(t, vocab) for t in texts], gt_index=gt, ranked=ranked))
+    return out
+
+
+def score_metrics(qas):
+    """The corpus numbers of a scoring run.  ``qas``: per QA dict(score=[...], logp=[...], n_tokens=[...], gt_index=k or None,
+    ranked=bool), candidates in input order.  perplexity = exp(-sum logp / sum n_tokens) over the ground-truth answers (every QA with a
+    gt_index); over the ``ranked`` QAs, with rank = 1 + the candidates that score higher than the ground truth + the EARLIER ones that
+    score the same (ties keep input order): mrr, r@1 / r@5 / r@10 (share of ranks <= k) and mean_rank.  None where nothing counts."""
+    import math
+    lp = sum(q["logp"][q["gt_index"]] for q in qas if q["gt_index"] is not None)
+    nt = sum(q["n_tokens"][q["gt_index"]] for q in qas if q["gt_index"] is not None)
+    ranks = []
+    for q in qas:
+        if q.get("ranked") and q["gt_index"] is not None:
+            g, s = q["gt_index"], q["score"]
+            ranks.append(1 + sum(1 for j, v in enumerate(s) if v > s[g] or (v == s[g] and j < g)))
+    n = len(ranks)
+    share = lambda k: sum(1 for r in ranks if r <= k) / n if n else None
+    return dict(perplexity=math.exp(-lp / nt) if nt else None, n_answers=sum(1 for q in qas if q["gt_index"] is not None), n_tokens=nt,
+                n_ranked=n, ranks=ranks, mrr=sum(1.0 / r for r in ranks) / n if n else None, r1=share(1), r5=share(5), r10=share(10),
+                mean_rank=sum(ranks) / n if n else None)
+
+
+def candidate_order(scores):
+    """Candidate indices, best score first; equal scores keep input order."""
+    return sorted(range(len(scores)), key=lambda j: (-scores[j], j))
+
+
 # ---------------------------------------------------------------------------------------------------------------- decoding
-def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=None):
-    """Run the planned searches; returns per qa_id the (n-best list, best score) of beam search, the greedy token list, or the
-    samples' (tokens, score) pairs, best first (``sampling``: samples / temperature / top_k / top_p / seed)."""
+def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=None, scoring=None):
+    """Run the planned searches; returns per qa_id the (n-best list, best score) of beam search, the greedy token list, the
+    samples' (tokens, score) pairs, best first (``sampling``: samples / temperature / top_k / top_p / seed), or the candidates'
+    score dicts in input order (``scoring``: tokens = per qa_id its candidates' token lists, max_len, width — one session shape
+    per bucket)."""
     from . import decode
     from .data_handler import make_batch
     from .decode import beam_search_decode_many, greedy_decode_many
@@ -234,6 +327,10 @@ def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, 
             # keys = qa_ids: a QA's random stream is the same in any bucket, at any D, with --no-buckets
             res = decode.sample_decode_many(model, batch, maxlen, sos, eos, pad, keys=ids, banned=(unk, pad, sos), min_len=1, penalty=penalty,
                                             **sampling)
+        elif decode_style == "score":
+            # (a padding copy of the last QA rides with one candidate: its rows are dropped)
+            cands = [scoring["tokens"][i] if k < n_real else scoring["tokens"][i][:1] for k, i in enumerate(ids)]
+            res = decode.score_candidates(model, batch, cands, sos, eos, pad, penalty=penalty, max_len=scoring["max_len"], width=scoring["width"])
         else:
             res = greedy_decode_many(model, batch, maxlen, sos, pad).cpu().tolist()
         for i, r in zip(ids[:n_real], res[:n_real]):
@@ -242,25 +339,39 @@ def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, 
 
 
 def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0, nbest=5, decode_style="greedy", undisclosed_only=False,
-                      ref_data=None, dialogues_per_search=0, buckets=True, sampling=None):
+                      ref_data=None, dialogues_per_search=0, buckets=True, sampling=None, candidates=None):
     """Decode every QA of ``data`` (data_handler.load) and return the reference's result dict, logging the reference's
-    QS / REF / HYP lines per QA."""
+    QS / REF / HYP lines per QA.  decode_style "score" generates nothing: every QA's ``candidates`` (load_candidates' ``spec``; its
+    own answer without one) are scored and logged as CAND lines, best first; the answer is the best-scoring candidate, every turn
+    gains "scores" in input order, and the corpus perplexity and ranking metrics (score_metrics) are logged at the end.  Candidates
+    are scored whole: ``maxlen`` does not cut them."""
     vocablist = sorted(vocab.keys(), key=lambda s: vocab[s])
     eos = vocab["<eos>"]
     lens = qa_lengths(data)
     if decode_style == "sample":
         sampling = dict(dict(samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=1), **(sampling or {}))
     width = beam if decode_style == "beam_search" else (sampling["samples"] if decode_style == "sample" else 1)
+    cands = scoring = None
+    if decode_style == "score":
+        cands = load_candidates(candidates, data["original"], vocab, undisclosed_only, ref_data)
+        assert len(cands) == len(lens)
+        # one pass shape for the whole run: the longest candidate + <eos> rounded up to 8 positions, the most candidates of a QA (<= 32) rows
+        longest = max(len(t) for c in cands for t in c["tokens"])
+        scoring = dict(tokens=[c["tokens"] for c in cands], max_len=_up(longest + 1, 8), width=min(32, max(len(c["tokens"]) for c in cands)))
     if dialogues_per_search > 0:
         per = dialogues_per_search
+    elif decode_style == "score":
+        per = LAUNCH_PASS_D              # (scoring runs on the launch-per-sublayer pass)
     else:
         per = lambda shape: auto_dialogues(model, corpus.device, shape, maxlen, width)
     searches = plan_searches(lens, per, buckets=buckets)
     n_buckets = len({(tuple(s[2][0]),) + tuple(s[2][1:]) for s in searches})
     logging.info("%d QAs in %d searches over %d padded shapes", len(lens), len(searches), n_buckets)
     vids = {it[1]: it[0] for it in data["dialogs"]}
-    res = decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=sampling)
+    res = decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=sampling,
+                          scoring=scoring)
     answers = []
+    scores = [] if decode_style == "score" else None
     qa_id = 0
     for idx, dialog in enumerate(data["original"]["dialogs"]):
         vid = dialog["image_id"]
@@ -275,7 +386,14 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
             logging.info("QS: " + qa["question"])
             logging.info("REF: " + (ref[t]["answer"] if ref is not None else qa["answer"]))
             r = res[qa_id]
-            if decode_style in ("beam_search", "sample"):
+            if decode_style == "score":
+                texts = cands[qa_id]["texts"]
+                order = candidate_order([c["score"] for c in r])
+                for n, j in enumerate(order):
+                    logging.info("CAND[%d]: %s  ( %f, %f, %d )" % (n + 1, texts[j], r[j]["score"], r[j]["logp"], r[j]["n_tokens"]))
+                hyp = texts[order[0]]
+                scores.append([dict(candidate=texts[j], score=c["score"], logp=c["logp"], n_tokens=c["n_tokens"]) for j, c in enumerate(r)])
+            elif decode_style in ("beam_search", "sample"):
                 pred_out = r[0] if decode_style == "beam_search" else r          # (sample: every draw is logged, best first)
                 hyp = ""
                 for n in range(min(nbest, len(pred_out)) if decode_style == "beam_search" else len(pred_out)):
@@ -289,7 +407,15 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
             answers.append(hyp)
             logging.info("-----------------------")
             qa_id += 1
-    return build_result(data["original"], undisclosed_only, answers)
+    if decode_style == "score":
+        m = score_metrics([dict(score=[c["score"] for c in res[i]], logp=[c["logp"] for c in res[i]], n_tokens=[c["n_tokens"] for c in res[i]],
+                                gt_index=cands[i]["gt_index"], ranked=cands[i]["ranked"]) for i in range(len(cands))])
+        if m["perplexity"] is not None:
+            logging.info("perplexity = %.10g  ( %d answers, %d tokens incl. <eos> )" % (m["perplexity"], m["n_answers"], m["n_tokens"]))
+        if m["n_ranked"]:
+            logging.info("MRR = %.6f  R@1 = %.6f  R@5 = %.6f  R@10 = %.6f  mean rank = %.4f  ( %d QAs with gt_index )"
+                         % (m["mrr"], m["r1"], m["r5"], m["r10"], m["mean_rank"], m["n_ranked"]))
+    return build_result(data["original"], undisclosed_only, answers, scores)
 
 
 def main(argv=None):
@@ -329,7 +455,7 @@ def main(argv=None):
                                decode_style=args.decode_style, undisclosed_only=args.undisclosed_only, ref_data=labeled_test,
                                dialogues_per_search=args.dialogues_per_search, buckets=not args.no_buckets,
                                sampling=dict(samples=args.samples, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-                                             seed=args.sample_seed))
+                                             seed=args.sample_seed), candidates=args.candidates)
     wall = time.time() - start_time
     n_qa = len(test_data["dialogs"])
     logging.info("----------------")

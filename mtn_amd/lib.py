@@ -162,6 +162,11 @@ class SampleArgs(C.Structure):
                 ("log_logp", C.c_void_p), ("log_u", C.c_void_p), ("tokens", C.c_void_p), ("pos", C.c_void_p), ("anc", C.c_void_p)]
 
 
+class ScoreArgs(C.Structure):
+    _fields_ = [("n_seq", C.c_int), ("L", C.c_int), ("V", C.c_int), ("pad", C.c_int), ("ldz", C.c_long), ("logits", C.c_void_p),
+                ("target", C.c_void_p), ("tok_logp", C.c_void_p), ("tok_rank", C.c_void_p), ("seq_logp", C.c_void_p), ("seq_len", C.c_void_p)]
+
+
 class LnFinalizeDesc(C.Structure):
     _fields_ = [("partial", C.c_void_p), ("nparts", C.c_int), ("d", C.c_int), ("da2", C.c_void_p), ("db2", C.c_void_p)]
 
@@ -210,6 +215,7 @@ SYMBOLS = {
     "mtn_decode_step": (C.c_int, [C.POINTER(DecodeArgs), _P, C.c_int, _P]),
     "mtn_beam_advance": (C.c_int, [C.POINTER(BeamArgs), _P]),
     "mtn_sample_rows": (C.c_int, [C.POINTER(SampleArgs), _P]),
+    "mtn_score_rows": (C.c_int, [C.POINTER(ScoreArgs), _P]),
     "mtn_debug_hold_cus": (C.c_int, [C.c_int, C.c_int, C.c_int, _P]),
     "mtn_gemm_tt_table_aux": (C.c_int, [C.c_int, C.c_int, C.POINTER(GemmProblem), C.POINTER(TtAux), _P]),
     "mtn_layernorm_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -510,6 +510,15 @@ class Generator(nn.Module):
             return ops.generator_log_probs(x, f["w_lp"], f["bias"])
         return F.log_softmax(self.proj(x), dim=-1)
 
+    def logits(self, x):
+        """The inference branch of forward up to the GEMM: x W^T + b as fp32 logits, without the row log-softmax (candidate scoring reads
+        the logits: ops.score_rows).  Inference only, on the HIP path only — there is no composed fallback behind it."""
+        f = self._fused
+        if f is None or not x.is_cuda or self.training or f["w_lp"].device != x.device or x.size(-1) % 8:
+            raise RuntimeError("Generator.logits: an eval() model prepared on the GPU (model.prepare()), d_model a multiple of 8")
+        f["prepare"]()
+        return ops.generator_logits(x, f["w_lp"], f["bias"])
+
 
 # ------------------------------------------------------------------------------------------ top level
 # which transposed weight copies (besides W_o^T) the flat layout keeps: see EncoderDecoder._flatten

@@ -895,12 +895,10 @@ class SublayerGroupFn(torch.autograd.Function):
         return (None, *grads_out)
 
 
-def generator_log_probs(x, w_lp, bias):
-    """Generator.forward at inference (mtn.py:68-69: log_softmax(proj(x))) on the HIP path: x (..., d) fp32 or compute dtype ->
-    (..., V) fp32 log-probabilities.  One grouped-GEMM launch (x W^T + b, fp32 logits) and one row kernel (csrc/select.hip) —
-    no vendor BLAS / softmax kernels in a decode step.  No autograd: training goes through GeneratorLossFn (fused loss head)."""
+def generator_logits(x, w_lp, bias):
+    """The projection of Generator.forward alone (mtn.py:68: proj(x)): x (..., d) fp32 or compute dtype -> (..., V) fp32 logits, one
+    grouped-GEMM launch (x W^T + b).  What score_rows reads: log-probabilities of chosen columns need no (rows, V) log-softmax."""
     _require_cuda(x, w_lp)
-    lib = L.load()
     lp = w_lp.dtype
     V, d = w_lp.shape
     a = x.reshape(-1, d)
@@ -911,7 +909,47 @@ def generator_log_probs(x, w_lp, bias):
     pr.A, pr.B, pr.lda, pr.ldb, pr.M, pr.N, pr.K = a.data_ptr(), w_lp.data_ptr(), d, d, rows, V, d
     pr.bias, pr.gate_scale, pr.out_f32, pr.ldc = bias.data_ptr(), 1.0, out.data_ptr(), V
     gemm(L.dtype_code(lp), [pr])
-    L.check(lib.mtn_log_softmax_rows(out.data_ptr(), rows, V, V, out.data_ptr(), V, L.stream_ptr()))
+    return out.view(*x.shape[:-1], V)
+
+
+def score_rows(logits, target, pad, out=None):
+    """Per-token log-probability and rank of ``target`` (n_seq, L) int64 under ``logits`` (n_seq * L, V) or (n_seq, L, V) fp32 (unit
+    column stride; a row stride >= V), and their per-sequence sums (csrc/score.hip; include/mtn_hip.h mtn_score_rows gives the
+    definitions) -> (tok_logp (n_seq, L) fp32, tok_rank (n_seq, L) int32, seq_logp (n_seq,) float64, seq_len (n_seq,) int32).
+    ``pad`` positions (and ids outside the vocabulary) give 0 / -1 and are not counted.  ``out``: the four tensors to write into."""
+    _require_cuda(logits, target)
+    if target.dim() != 2 or target.dtype != torch.int64 or not target.is_contiguous():
+        raise ValueError("score_rows: target is a contiguous (n_seq, L) int64 tensor")
+    n_seq, Ls = target.shape
+    if logits.dim() == 3 and logits.is_contiguous():
+        logits = logits.view(-1, logits.size(-1))
+    if (logits.dim() != 2 or logits.dtype != torch.float32 or logits.size(0) != n_seq * Ls or (logits.size(1) > 1 and logits.stride(1) != 1)
+            or logits.stride(0) < logits.size(1)):
+        raise ValueError("score_rows: logits fp32 (n_seq * L, V) with unit column stride, one row per target position")
+    dev = logits.device
+    if out is None:
+        out = (torch.empty(n_seq, Ls, device=dev, dtype=torch.float32), torch.empty(n_seq, Ls, device=dev, dtype=torch.int32),
+               torch.empty(n_seq, device=dev, dtype=torch.float64), torch.empty(n_seq, device=dev, dtype=torch.int32))
+    tl, tr, sl, sn = out
+    _require_cuda(*out)
+    if not (tl.dtype == torch.float32 and tr.dtype == torch.int32 and sl.dtype == torch.float64 and sn.dtype == torch.int32
+            and tl.shape == tr.shape == target.shape and sl.numel() == sn.numel() == n_seq and all(t.is_contiguous() for t in out)):
+        raise ValueError("score_rows: out = (fp32 (n_seq, L), int32 (n_seq, L), float64 (n_seq,), int32 (n_seq,)), each contiguous")
+    a = L.ScoreArgs()
+    a.n_seq, a.L, a.V, a.pad, a.ldz = n_seq, Ls, logits.size(1), int(pad), logits.stride(0)
+    a.logits, a.target = logits.data_ptr(), target.data_ptr()
+    a.tok_logp, a.tok_rank, a.seq_logp, a.seq_len = tl.data_ptr(), tr.data_ptr(), sl.data_ptr(), sn.data_ptr()
+    L.check(L.load().mtn_score_rows(C.byref(a), L.stream_ptr()))
+    return out
+
+
+def generator_log_probs(x, w_lp, bias):
+    """Generator.forward at inference (mtn.py:68-69: log_softmax(proj(x))) on the HIP path: x (..., d) fp32 or compute dtype ->
+    (..., V) fp32 log-probabilities.  One grouped-GEMM launch (x W^T + b, fp32 logits) and one row kernel (csrc/select.hip) —
+    no vendor BLAS / softmax kernels in a decode step.  No autograd: training goes through GeneratorLossFn (fused loss head)."""
+    V = w_lp.size(0)
+    out = generator_logits(x, w_lp, bias).view(-1, V)
+    L.check(L.load().mtn_log_softmax_rows(out.data_ptr(), out.size(0), V, V, out.data_ptr(), V, L.stream_ptr()))
     return out.view(*x.shape[:-1], V)
 
 
