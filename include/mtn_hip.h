@@ -44,7 +44,7 @@ const char* mtn_last_error(void);
  * 113 (round 6): mtn_decode_args gained the trailing field `max_m`; mtn_decode_step takes W <= 16 rows, clamps `grid` to the device's
  * compute-unit count and bounds its polls in time (see there).
  * 114: mtn_assemble_tokens_desc gained the trailing field `row_len` (NULL = no cut; a zeroed struct keeps meaning that).
- * 115: new entry point mtn_sample_rows.  116: new entry point mtn_score_rows. */
+ * 115: new entry point mtn_sample_rows.  116: new entry point mtn_score_rows.  117: new entry point mtn_constrain_rows. */
 int mtn_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -633,6 +633,39 @@ typedef struct {
     int* seq_len;               /* [n_seq] */
 } mtn_score_args;
 int mtn_score_rows(const mtn_score_args* args /* host */, void* stream);
+/* Constrained decoding (version 117): rewrite each row of logp [rows, V] (fp32 log-probabilities, row stride ldx >= V; V < 2^24) from
+ * the history of the row's own hypothesis, before a selection launch (mtn_topk_rows, mtn_sample_rows) reads it.  One launch, one workgroup
+ * per row, no atomics; out [rows, V] (row stride ldo >= V) may BE logp (then only the constrained columns are written), otherwise the
+ * two must not overlap.
+ * History h[0..n-1]: the tokens the hypothesis has generated, oldest first, without <sos>; n <= L <= 1024.  Two sources:
+ *   explicit   hist != NULL: h = hist[row][0..n-1], n = hist_len[row] clamped to [0, L] (row stride ldh >= L);
+ *   step log   hist == NULL: the logs mtn_beam_advance / mtn_sample_rows write, log_tok / log_parent [L][rows] (parents relative to the
+ *              first row of the dialogue, i.e. of the row's group of `width` rows; log_parent NULL: every row is its own parent).  With
+ *              n = step[row / rows_per_step] clamped to [0, L] (rows_per_step = width where a dialogue has one step counter, 1 where
+ *              every row has its own), base = row - row % width and r = row % width:
+ *                  for j = n-1 .. 0:  h[j] = log_tok[j][base + r];  r = log_parent[j][base + r] clamped to [0, width)
+ *              — how the host rebuilds a hypothesis from the log.  Rows past a dialogue's live count read stale entries: harmless, their
+ *              output is never read.  rows is a multiple of width, width <= 16.
+ *   hist, hist_len, the logs and step are DEVICE memory (kernel arguments are frozen into a captured graph; these change per step).
+ * Transform:
+ *   1. penalty  theta >= 1 (1: off): for every DISTINCT token c of h, out[c] = logp[c] * theta — one fp32 multiply, applied once however
+ *               often c occurs.  Log-probabilities are <= 0, so this lowers them.  The row is NOT renormalised: scores, finished scores and
+ *               logged logp values of a search under a penalty are the penalised ones (mtn_sample_rows normalises over its kept set anyway).
+ *   2. n-gram   ngram = N in [1, 8] (0: off): for every j in [0, n - N] with h[j .. j+N-2] == h[n-N+1 .. n-1], out[h[j+N-1]] = -inf: no
+ *               N-gram of the history can occur a second time.  N = 1 bans every token of h.  A ban overrides the penalty.
+ *   3. every other column is copied bit for bit.
+ * A token of h outside [0, V) takes part in the comparisons of 2 but names no column: nothing is written for it.  Banned columns are
+ * -inf: mtn_topk_rows sorts them last (they never enter a head while k finite columns exist) and mtn_sample_rows never draws them. */
+typedef struct {
+    int rows, V; long ldx, ldo;
+    const float* logp; float* out;
+    int ngram; float theta;
+    int L;
+    const int* hist; long ldh; const int* hist_len;               /* device: [rows][ldh], [rows]; or hist = NULL */
+    const int* log_tok; const int* log_parent; const int* step;   /* device: [L][rows] (log_parent may be NULL), [rows / rows_per_step] */
+    int width, rows_per_step;
+} mtn_constrain_args;
+int mtn_constrain_rows(const mtn_constrain_args* args /* host */, void* stream);
 /* Generator (mtn.py:62-69) at inference: out[row][c] = x[row][c] - logsumexp(x[row][0..V-1]) over logit rows x [rows, V] (row
  * strides ldx / ldo; out may be x).  The logits themselves are one mtn_gemm (x W^T + b, fp32 out). */
 int mtn_log_softmax_rows(const float* x, int rows, int V, long ldx, float* out, long ldo, void* stream);

@@ -532,8 +532,8 @@ class MegaDecodeSession(DecodeSession):
         torch.cuda.current_stream().synchronize()
         return self._top_host.numpy()
 
-    def search(self, beam, k, start, unk, eos, penalty, min_len, nbest):
-        log = self._search_log(beam, k, start, unk, eos, penalty, min_len, eos)
+    def search(self, beam, k, start, unk, eos, penalty, min_len, nbest, no_repeat_ngram=0, repetition_penalty=1.0):
+        log = self._search_log(beam, k, start, unk, eos, penalty, min_len, eos, no_repeat_ngram, repetition_penalty)
         if log is None:
             return None
         par, tok, n_old, n_new, score, done_sc, flags = log
@@ -551,19 +551,23 @@ class MegaDecodeSession(DecodeSession):
                 results.append(([([], 0)], None))
         return results
 
-    def greedy(self, start):
+    def greedy(self, start, no_repeat_ngram=0, repetition_penalty=1.0):
         """argmax decoding of every dialogue of the session as one graph replay: a beam of one per dialogue that skips nothing and
         finishes nothing (mtn_beam_advance with beam = k = 1, no <unk> / <eos>; dialogue d's tokens are column d * width of the step
         log).  Returns D lists of the max_len - 1 generated tokens, or None (tie / not applicable)."""
-        log = self._search_log(1, 1, start, -1, -1, 0.0, self.max_len + 1, self.select[1] if self.select is not None else 0)
+        log = self._search_log(1, 1, start, -1, -1, 0.0, self.max_len + 1, self.select[1] if self.select is not None else 0,
+                               no_repeat_ngram, repetition_penalty)
         if log is None:
             return None
         return [[int(t) for t in log[1][:self.max_len - 1, d_ * self.width]] for d_ in range(self.D)]
 
-    def _search_log(self, beam, k, start, unk, eos, penalty, min_len, extra_col):
+    def _search_log(self, beam, k, start, unk, eos, penalty, min_len, extra_col, no_repeat_ngram=0, repetition_penalty=1.0):
         """A whole beam search (data_utils.py:188-242) for every dialogue of the session as ONE graph replay: max_len x [persistent decode
         step, generator, row heads (csrc/select.hip topk_rows), hypothesis bookkeeping on the device (mtn_beam_advance)], the step log
         copied to a pinned block at the end.  The host synchronises once per search and rebuilds the n-best lists from the log.
+        With a constraint on (no_repeat_ngram > 0 or repetition_penalty != 1; csrc/constrain.hip), one more launch per token sits between
+        the generator and the row heads: it rewrites the rows in place from each hypothesis' history, which it walks out of this very step
+        log (the parents and tokens of the steps before, the dialogue's step counter) — all device memory, so one graph serves every search.
         Returns None when a row's head held an exact tie (the reference's visiting order then comes from the full row: the caller runs the
         search step by step) or when the device-side selection does not apply."""
         import ctypes as C
@@ -573,7 +577,9 @@ class MegaDecodeSession(DecodeSession):
         if self.select is None or self.select[0] != k_top or self.select[1] != extra_col or beam > self.width or k_top > SELECT_MAX_K or not self.use_graph:
             return None
         W, D, Lm = self._W, self.D, self.max_len
-        key = (beam, k, start, unk, eos, float(penalty), min_len)
+        ngram, theta = int(no_repeat_ngram), float(repetition_penalty)
+        constrained = ngram > 0 or theta != 1.0
+        key = (beam, k, start, unk, eos, float(penalty), min_len, ngram, theta)
         if getattr(self, "_search_key", None) != key:
             dev = self._x.device
             # device state of the search [lp (W doubles) | n_live (D) | step (D) | flags (2)] and its initial image
@@ -618,6 +624,9 @@ class MegaDecodeSession(DecodeSession):
                 for _ in range(Lm):
                     L.check(L.load().mtn_decode_step(C.byref(self._args), self._stages_dev.data_ptr(), self._grid, L.stream_ptr()))
                     logp = ops.generator_log_probs(self._out_lp, g["w_lp"], g["bias"])
+                    if constrained:
+                        ops.constrain_rows(logp, ngram, theta, log_tok=a.log_tok, log_parent=a.log_parent, step=a.step, width=self.width,
+                                           rows_per_step=self.width, log_len=Lm)
                     top = ops.topk_rows(logp, k_top, extra_col)
                     a.top = top.data_ptr()
                     L.check(L.load().mtn_beam_advance(C.byref(a), L.stream_ptr()))
@@ -641,12 +650,14 @@ class MegaDecodeSession(DecodeSession):
             return None
         return None if self._log_views[6][0] else self._log_views
 
-    def sample_log(self, start, seed, keys, params):
+    def sample_log(self, start, seed, keys, params, no_repeat_ngram=0, repetition_penalty=1.0):
         """A whole sampling search for every row of the session as ONE graph replay: max_len x [persistent decode step, generator,
         mtn_sample_rows (csrc/sample.hip)] — no row heads, no hypothesis bookkeeping: every row starts at <sos>, draws its next token on the
         device and keeps its own cache slots (identity ancestors).  seed and keys enter through one small pinned block (kernel arguments are
         frozen into the graph, and one graph serves every search of the session's shape); the step log [token | logp[token] | u], each
         (max_len, rows), is copied out at the end and the host synchronises once.  ``params``: the keyword arguments of ops.sample_args.
+        With a constraint on, one csrc/constrain.hip launch per token rewrites the rows before the draw; a row's history is its own column of
+        the token log (no parents).
         Returns the three host views, or None after a poll timeout (timed_out() tells)."""
         import ctypes as C
         import numpy as np
@@ -654,7 +665,9 @@ class MegaDecodeSession(DecodeSession):
         if not self.use_graph:
             raise ValueError("the sampling search on the persistent step is a captured graph")
         W, Lm = self._W, self.max_len
-        key = (start,) + tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in params.items()))
+        ngram, theta = int(no_repeat_ngram), float(repetition_penalty)
+        constrained = ngram > 0 or theta != 1.0
+        key = (start,) + tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in params.items())) + (ngram, theta)
         if getattr(self, "_sample_key", None) != key:
             dev = self._x.device
             # [seed (int64) | keys (W int64) | step (W int32)]: the pinned image the host fills per search, and its device copy
@@ -681,6 +694,8 @@ class MegaDecodeSession(DecodeSession):
                 for _ in range(Lm):
                     L.check(L.load().mtn_decode_step(C.byref(self._args), self._stages_dev.data_ptr(), self._grid, L.stream_ptr()))
                     logp = ops.generator_log_probs(self._out_lp, g["w_lp"], g["bias"])
+                    if constrained:
+                        ops.constrain_rows(logp, ngram, theta, log_tok=self._slog[0], step=s0[8 + 8 * W:].view(torch.int32), width=1, rows_per_step=1)
                     ops.sample_rows(logp, s0[:8].view(torch.int64), s0[8:8 + 8 * W].view(torch.int64), s0[8 + 8 * W:].view(torch.int32), log,
                                     tokens=p0, pos=p0 + self._off_pos, anc=p0 + self._off_anc, **params)
                 self._slog_host.copy_(self._slog, non_blocking=True)
@@ -807,6 +822,36 @@ def _session(model, batch, max_len, width, pad, use_graph, kv_cache=False, selec
     return sess
 
 
+def _constraints(no_repeat_ngram, repetition_penalty):
+    """(N, theta, anything on?) of a decode call's constraint keywords, checked."""
+    ngram, theta = int(no_repeat_ngram), float(repetition_penalty)
+    if not 0 <= ngram <= 8 or not theta >= 1.0:
+        raise ValueError("no_repeat_ngram in [0, 8] (0 = off), repetition_penalty >= 1 (1 = off)")
+    return ngram, theta, ngram > 0 or theta != 1.0
+
+
+def _pass_select(model, batch, max_len, width, mega, select, constrained):
+    """The in-pass selection a search's session is built with.  A constrained search off the persistent step selects AFTER the
+    constraint launch, so its pass selects nothing (heads of unconstrained rows would be computed and thrown away); the persistent-step
+    session keeps its selection: the captured search needs it, and the tie fallback steps that same session."""
+    if constrained and not (mega and MegaDecodeSession.supported(model, batch, max_len, width)):
+        return None
+    return select
+
+
+def _constrain_step(sess, hists, ngram, theta):
+    """The step-by-step paths' constraint: csrc/constrain.hip in explicit-history mode on ALL rows of the session's last log-probabilities,
+    in place (the captured searches run the same kernel off their step log, so both give the same rows).  ``hists``: (row, generated tokens)
+    of the live rows; every other row gets an empty history.  Table and lengths travel as one block, in one copy."""
+    rows, Lm = sess.logp.size(0), sess.max_len
+    blk = torch.zeros(rows * (Lm + 1), dtype=torch.int32)
+    for r, toks in hists:
+        blk[r * Lm:r * Lm + len(toks)] = torch.tensor(list(toks), dtype=torch.int32)
+        blk[rows * Lm + r] = len(toks)
+    blk = blk.to(sess.logp.device)
+    ops.constrain_rows(sess.logp, ngram, theta, hist=blk[:rows * Lm].view(rows, Lm), hist_len=blk[rows * Lm:])
+
+
 class _Beam:
     """Hypothesis bookkeeping of data_utils.py:196-240 for one dialogue (same candidate order and tie behaviour)."""
 
@@ -863,17 +908,22 @@ class _Beam:
 
 
 def beam_search_decode_many(model, batch, max_len, start_symbol, unk_symbol, end_symbol, pad_symbol, beam=5, penalty=1.0,
-                            nbest=5, min_len=1, use_graph=True, kv_cache=None):
+                            nbest=5, min_len=1, use_graph=True, kv_cache=None, no_repeat_ngram=0, repetition_penalty=1.0):
     """beam_search_decode for a Batch of D dialogues at once: the D x beam live hypotheses are the batch dimension of ONE
     target-stream pass per generated token (the pass is launch-latency-bound, so D dialogues cost little more than one).
-    Returns a list of D (n-best list, best score) pairs, each equal to what the single-dialogue search returns."""
+    Returns a list of D (n-best list, best score) pairs, each equal to what the single-dialogue search returns.
+    ``no_repeat_ngram`` = N > 0: no hypothesis repeats an N-gram (the token that would complete one gets -inf); ``repetition_penalty`` =
+    theta > 1: the log-probability of every token a hypothesis already holds is multiplied by theta (include/mtn_hip.h mtn_constrain_rows).
+    Both act on the rows before candidates are selected, on every path; rows are not renormalised, so scores under a penalty are the
+    penalised ones.  Off (0, 1.0), the search is exactly the unconstrained one."""
+    ngram, theta, _ = _constraints(no_repeat_ngram, repetition_penalty)
     auto = kv_cache is None          # the caller leaves the pass to us: one persistent launch per token where it applies (<= 16 hypotheses, bf16)
     if kv_cache is None:
         kv_cache = max_len > KV_CACHE_FROM
     args = (model, batch, max_len, start_symbol, unk_symbol, end_symbol, pad_symbol, beam, penalty, nbest, min_len, use_graph, kv_cache)
-    res = _beam_search_many(*args, mega=auto)
+    res = _beam_search_many(*args, mega=auto, ngram=ngram, theta=theta)
     if res is None:                  # a poll of the persistent step timed out (compute units held by another kernel): the launch-per-sublayer pass
-        res = _beam_search_many(*args, mega=False)
+        res = _beam_search_many(*args, mega=False, ngram=ngram, theta=theta)
     return res
 
 
@@ -888,16 +938,19 @@ def _mega_failed(sess) -> bool:
     return True
 
 
-def _beam_search_many(model, batch, max_len, start_symbol, unk_symbol, end_symbol, pad_symbol, beam, penalty, nbest, min_len, use_graph, kv_cache, mega):
+def _beam_search_many(model, batch, max_len, start_symbol, unk_symbol, end_symbol, pad_symbol, beam, penalty, nbest, min_len, use_graph, kv_cache, mega,
+                      ngram=0, theta=1.0):
     auto = mega
+    constrained = ngram > 0 or theta != 1.0
     k = beam + 2
     # device-side candidate selection (csrc/select.hip) holds at most SELECT_MAX_K entries per row: wider beams keep torch.topk
     sel = (k + 1, end_symbol) if k + 1 <= SELECT_MAX_K else None
-    sess = _session(model, batch, max_len, beam, pad_symbol, use_graph, kv_cache, select=sel, mega=auto)
+    sess = _session(model, batch, max_len, beam, pad_symbol, use_graph, kv_cache,
+                    select=_pass_select(model, batch, max_len, beam, auto, sel, constrained), mega=auto)
     mega = isinstance(sess, MegaDecodeSession)
     if mega and sel is not None:
         # the whole search as one graph replay, hypothesis bookkeeping on the device; None = a tie somewhere: step by step below
-        res = sess.search(beam, k, start_symbol, unk_symbol, end_symbol, penalty, min_len, nbest)
+        res = sess.search(beam, k, start_symbol, unk_symbol, end_symbol, penalty, min_len, nbest, ngram, theta)
         if _mega_failed(sess):
             return None
         if res is not None:
@@ -910,20 +963,24 @@ def _beam_search_many(model, batch, max_len, start_symbol, unk_symbol, end_symbo
             live = [d * Wd + i for d, bm in enumerate(beams) for i in range(len(bm.hyps))]
             sess.step_extend(l + 1, live, [h[2][-1] for bm in beams for h in bm.hyps],
                              [d * Wd + p for d, bm in enumerate(beams) for p in bm.parents])
-            logps = [sess.logp[d * Wd:d * Wd + len(bm.hyps)] for d, bm in enumerate(beams)] if sess.top is None else None
             counts = [len(bm.hyps) for bm in beams]
         else:
-            logps = sess.step_many([bm.prefixes() for bm in beams])
-            counts = [lp.size(0) for lp in logps]
+            counts = [lp.size(0) for lp in sess.step_many([bm.prefixes() for bm in beams])]
             live = [r for d, n in enumerate(counts) for r in range(d * sess.width, d * sess.width + n)]
-        if sess.top is not None:
+        top = sess.top
+        if constrained:
+            # the rows are rewritten in place before anything is selected from them: the pass selected nothing (_pass_select), except on
+            # the persistent step, whose heads are of the unconstrained rows and are not read
+            _constrain_step(sess, [(d * sess.width + i, h[0]) for d, bm in enumerate(beams) for i, h in enumerate(bm.hyps)], ngram, theta)
+            top = ops.topk_rows(sess.logp, min(k + 1, sess.logp.size(1)), end_symbol) if sel is not None else None
+        if top is not None:
             # device-side selection inside the pass (csrc/select.hip): only the heads of the rows travel, in one copy
-            full = (sess.top_host() if mega else sess.top.cpu().numpy()).astype("float64")
+            full = (sess.top_host() if mega and not constrained else top.cpu().numpy()).astype("float64")
             packed = full[live]
             kk = (packed.shape[1] - 1) // 2
             allp = None
         else:
-            allp = torch.cat(logps, 0)
+            allp = sess.logp[live]
             tv, ti = torch.topk(allp, min(k + 1, allp.size(1)), dim=-1)
             packed = torch.cat([tv.double(), ti.double(), allp[:, end_symbol:end_symbol + 1].double()], 1).cpu().numpy()
             kk = tv.size(1)
@@ -945,86 +1002,108 @@ def _beam_search_many(model, batch, max_len, start_symbol, unk_symbol, end_symbo
 
 
 def beam_search_decode(model, batch, max_len, start_symbol, unk_symbol, end_symbol, pad_symbol, beam=5, penalty=1.0,
-                       nbest=5, min_len=1, use_graph=True, kv_cache=None):
+                       nbest=5, min_len=1, use_graph=True, kv_cache=None, no_repeat_ngram=0, repetition_penalty=1.0):
     """data_utils.py:188-242, same arguments and return value: (n-best list of (token list, score) sorted by score,
     best score).  A hypothesis ending with <eos> at length k scores logp + penalty * k; <unk> and <eos> never extend
-    a hypothesis; candidates are visited in descending log-probability exactly as the reference does (data_utils.py:219)."""
+    a hypothesis; candidates are visited in descending log-probability exactly as the reference does (data_utils.py:219).
+    no_repeat_ngram / repetition_penalty: as beam_search_decode_many (off by default)."""
     if batch.query.size(0) != 1:
         raise ValueError("beam_search_decode works on one dialogue (data_utils.py:188); use beam_search_decode_many for a batch")
     return beam_search_decode_many(model, batch, max_len, start_symbol, unk_symbol, end_symbol, pad_symbol, beam, penalty, nbest,
-                                   min_len, use_graph, kv_cache)[0]
+                                   min_len, use_graph, kv_cache, no_repeat_ngram, repetition_penalty)[0]
 
 
-def greedy_decode(model, batch, max_len, start_symbol, pad_symbol=1, use_graph=True, kv_cache=None):
+def greedy_decode(model, batch, max_len, start_symbol, pad_symbol=1, use_graph=True, kv_cache=None, no_repeat_ngram=0, repetition_penalty=1.0):
     """data_utils.py:159-186 (the reference's own greedy_decode cannot run: it calls decode() with the wrong arity, SURVEY
-    §8c) — pinned to: argmax of the generator's log-probabilities at every step, (1, max_len) tokens incl. <sos>."""
+    §8c) — pinned to: argmax of the generator's log-probabilities at every step, (1, max_len) tokens incl. <sos>.
+    no_repeat_ngram / repetition_penalty (off by default): the argmax is taken over the constrained row, as in beam_search_decode_many."""
+    ngram, theta, _ = _constraints(no_repeat_ngram, repetition_penalty)
     auto = kv_cache is None
-    ys = _greedy(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto)
+    ys = _greedy(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto, ngram, theta)
     if ys is None:                   # the persistent step timed out: the launch-per-sublayer pass
-        ys = _greedy(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, False)
+        ys = _greedy(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, False, ngram, theta)
     return torch.tensor([ys], dtype=batch.query.dtype, device=batch.query.device)
 
 
-def _greedy(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto):
+def _greedy(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto, ngram=0, theta=1.0):
+    constrained = ngram > 0 or theta != 1.0
     sess = _session(model, batch, max_len, 1, pad_symbol, use_graph, max_len > KV_CACHE_FROM if kv_cache is None else kv_cache,
-                    select=(2, 0) if auto else None, mega=auto)
+                    select=_pass_select(model, batch, max_len, 1, auto, (2, 0) if auto else None, constrained), mega=auto)
     ys = [start_symbol]
     if isinstance(sess, MegaDecodeSession) and sess.select is not None:
-        toks = sess.greedy(start_symbol)                   # the whole decode as one graph replay (None: a tie in some row's head)
+        # the whole decode as one graph replay (None: a tie in some row's head)
+        toks = sess.greedy(start_symbol, ngram, theta)
         toks = None if toks is None else toks[0]
         if toks is None:
             # step by step: the row's head (largest log-probability, its column) arrives in a pinned block — one replay and one
             # stream synchronisation per token, no argmax launch, no .item()
             for l in range(1, max_len):
                 sess.step_extend(l, [0], [ys[-1]], [0])
-                ys.append(int(sess.top_host()[0, 2]))
+                if constrained:          # (the head the pass took is of the unconstrained row)
+                    _constrain_step(sess, [(0, ys[1:])], ngram, theta)
+                    ys.append(int(ops.topk_rows(sess.logp, 2, 0)[0, 2].item()))
+                else:
+                    ys.append(int(sess.top_host()[0, 2]))
         else:
             ys += toks
         return None if _mega_failed(sess) else ys
     for _ in range(max_len - 1):
-        nxt = int(sess.step([ys]).argmax(dim=-1)[0])
+        logp = sess.step([ys])
+        if constrained:
+            _constrain_step(sess, [(0, ys[1:])], ngram, theta)          # (in place: `logp` is a view of the session's rows)
+        nxt = int(logp.argmax(dim=-1)[0])
         ys.append(nxt)
     return ys
 
 
-def greedy_decode_many(model, batch, max_len, start_symbol, pad_symbol=1, use_graph=True, kv_cache=None):
+def greedy_decode_many(model, batch, max_len, start_symbol, pad_symbol=1, use_graph=True, kv_cache=None, no_repeat_ngram=0,
+                       repetition_penalty=1.0):
     """greedy_decode for a Batch of D dialogues at once: (D, max_len) tokens incl. <sos>, row d equal to greedy_decode on
     dialogue d alone.  On the persistent step the D argmax searches are ONE graph replay; otherwise the D rows are the batch
-    dimension of one target-stream pass per token."""
+    dimension of one target-stream pass per token.  no_repeat_ngram / repetition_penalty: as greedy_decode."""
+    ngram, theta, _ = _constraints(no_repeat_ngram, repetition_penalty)
     auto = kv_cache is None
-    ys = _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto)
+    ys = _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto, ngram, theta)
     if ys is None:                   # the persistent step timed out: the launch-per-sublayer pass
-        ys = _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, False)
+        ys = _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, False, ngram, theta)
     return torch.tensor(ys, dtype=batch.query.dtype, device=batch.query.device)
 
 
-def _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto):
+def _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto, ngram=0, theta=1.0):
+    constrained = ngram > 0 or theta != 1.0
     sess = _session(model, batch, max_len, 1, pad_symbol, use_graph, max_len > KV_CACHE_FROM if kv_cache is None else kv_cache,
-                    select=(2, 0) if auto else None, mega=auto)
+                    select=_pass_select(model, batch, max_len, 1, auto, (2, 0) if auto else None, constrained), mega=auto)
     D = sess.D
     ys = [[start_symbol] for _ in range(D)]
     if isinstance(sess, MegaDecodeSession) and sess.select is not None:
-        toks = sess.greedy(start_symbol)
+        toks = sess.greedy(start_symbol, ngram, theta)
         if toks is None:
             # a tie in some row's head: step by step, every dialogue's row head from the pinned block (row d = dialogue d at width 1)
             rows = list(range(D))
             for l in range(1, max_len):
                 sess.step_extend(l, rows, [y[-1] for y in ys], rows)
-                top = sess.top_host()
+                if constrained:
+                    _constrain_step(sess, [(d_, ys[d_][1:]) for d_ in rows], ngram, theta)
+                    top = ops.topk_rows(sess.logp, 2, 0).cpu().numpy()
+                else:
+                    top = sess.top_host()
                 for d_ in rows:
                     ys[d_].append(int(top[d_, 2]))
         else:
             ys = [[start_symbol] + t for t in toks]
         return None if _mega_failed(sess) else ys
     for _ in range(max_len - 1):
-        logp = torch.cat(sess.step_many([[y] for y in ys]), 0)
+        logps = sess.step_many([[y] for y in ys])
+        if constrained:
+            _constrain_step(sess, [(d_ * sess.width, y[1:]) for d_, y in enumerate(ys)], ngram, theta)      # (in place: `logps` are views)
+        logp = torch.cat(logps, 0)
         for y, nxt in zip(ys, logp.argmax(dim=-1).tolist()):
             y.append(int(nxt))
     return ys
 
 
 def sample_decode_many(model, batch, max_len, start, eos, pad, *, samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, keys=None,
-                       banned=(), min_len=1, penalty=0.0, use_graph=True, kv_cache=None, trace=None):
+                       banned=(), min_len=1, penalty=0.0, use_graph=True, kv_cache=None, trace=None, no_repeat_ngram=0, repetition_penalty=1.0):
     """Stochastic decoding of a Batch of D dialogues x ``samples`` draws each (temperature / top-k / nucleus; include/mtn_hip.h
     mtn_sample_rows defines the filters).  Row d * samples + s draws with the random stream of key keys[d] * samples + s (keys: 0..D-1
     by default) under ``seed``: a pure function of (seed, key, position), so a dialogue's samples do not depend on what it is batched with.
@@ -1034,7 +1113,11 @@ def sample_decode_many(model, batch, max_len, start, eos, pad, *, samples=1, tem
     model's, <eos> included) + penalty * (len + 1) — a finished beam hypothesis' formula.  temperature = 0 means top_k = 1.
     On the persistent step (<= 16 rows, bf16) the whole search is one graph replay; elsewhere the launch-per-sublayer pass runs per token
     and the same kernel draws from its rows.  ``trace``: a list that receives (row keys, tokens, log-probabilities, u), each log
-    (max_len, rows), of this search."""
+    (max_len, rows), of this search.
+    no_repeat_ngram / repetition_penalty (off by default; include/mtn_hip.h mtn_constrain_rows): every row's log-probabilities are
+    rewritten from that row's own draws before the filters see them, so no sample repeats an N-gram before its <eos>; the logged
+    log-probabilities, and so the scores, are the penalised ones under a penalty."""
+    ngram, theta, _ = _constraints(no_repeat_ngram, repetition_penalty)
     D, S = batch.query.size(0), int(samples)
     if S < 1 or len(banned) > 4:
         raise ValueError("sample_decode_many: samples >= 1, at most 4 banned tokens")
@@ -1049,9 +1132,9 @@ def sample_decode_many(model, batch, max_len, start, eos, pad, *, samples=1, tem
     params = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), banned=tuple(int(b) for b in banned), eos=int(eos),
                   min_len=int(min_len))
     auto = kv_cache is None
-    log = _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, auto)
+    log = _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, auto, ngram, theta)
     if log is None:                  # a poll of the persistent step timed out: the launch-per-sublayer pass
-        log = _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, False)
+        log = _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, False, ngram, theta)
     tok, lp, u = log
     if trace is not None:
         trace.append((list(row_keys), tok.copy(), lp.copy(), u.copy()))
@@ -1068,13 +1151,13 @@ def sample_decode_many(model, batch, max_len, start, eos, pad, *, samples=1, tem
     return results
 
 
-def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, mega):
+def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, mega, ngram=0, theta=1.0):
     """The step log (tokens, log-probabilities, u — numpy, (max_len, rows)) of one sampling search, or None after a persistent-step timeout."""
     import numpy as np
     sess = _session(model, batch, max_len, S, pad, use_graph, max_len > KV_CACHE_FROM if kv_cache is None else kv_cache, select=None,
                     mega=mega and use_graph, mode="sample")
     if isinstance(sess, MegaDecodeSession):
-        log = sess.sample_log(start, seed, row_keys, params)
+        log = sess.sample_log(start, seed, row_keys, params, ngram, theta)
         if _mega_failed(sess):
             return None
         return log
@@ -1093,6 +1176,8 @@ def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params,
     prefixes = [[start] for _ in range(W)]
     for l in range(max_len):
         sess.step_many([prefixes[d * S:d * S + S] for d in range(D)])
+        if ngram > 0 or theta != 1.0:        # a row's history is its own column of the token log, up to its step counter
+            ops.constrain_rows(sess.logp, ngram, theta, log_tok=log[0], step=step_t, width=1, rows_per_step=1)
         ops.sample_rows(sess.logp, seed_t, keys_t, step_t, log, **params)      # the session's rows ARE d * S + s: all of them live
         for p, t in zip(prefixes, log[0][l].tolist()):
             p.append(int(t))

@@ -74,6 +74,11 @@ def parse(argv=None):
     p.add_argument("--candidates", default=None, type=str,
                    help='score: JSON {"<image_id>_<turn>": {"candidates": ["text", ...], "gt_index": k}} (gt_index optional); a QA '
                         "without an entry, and every QA without this flag, is scored on its own answer")
+    # constrained decoding (beam_search, greedy, sample): the rows of log-probabilities are rewritten on the device before selection
+    p.add_argument("--no-repeat-ngram", default=0, type=int, help="no response repeats an n-gram of this size (1..8; 0 = off)")
+    p.add_argument("--repetition-penalty", default=1.0, type=float,
+                   help="multiply the log-probability of every token a response already holds by this (>= 1; 1 = off)")
+    p.add_argument("--min-length", default=1, type=int, help="beam_search / sample: no response ends before this many tokens")
     p.add_argument("--no-buckets", action="store_true",
                    help="one QA per search at its own padded shape, as the reference decodes (baseline / debugging)")
     args = p.parse_args(argv)
@@ -86,6 +91,14 @@ def parse(argv=None):
         p.error("--samples must be in [1, %d] (the rows of one persistent decode step)" % MAX_SAMPLES)
     if args.temperature < 0 or args.top_k < 0 or not 0 < args.top_p <= 1:
         p.error("--temperature >= 0, --top-k >= 0, 0 < --top-p <= 1")
+    if not 0 <= args.no_repeat_ngram <= 8:
+        p.error("--no-repeat-ngram must be in [0, 8]")
+    if not args.repetition_penalty >= 1.0:
+        p.error("--repetition-penalty must be >= 1")
+    if args.decode_style == "score" and (args.no_repeat_ngram != 0 or args.repetition_penalty != 1.0):
+        p.error("--no-repeat-ngram / --repetition-penalty constrain a search: they do not go with --decode-style score")
+    if args.min_length < 0:
+        p.error("--min-length must be >= 0")
     return args
 
 
@@ -304,17 +317,20 @@ def candidate_order(scores):
 
 
 # ---------------------------------------------------------------------------------------------------------------- decoding
-def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=None, scoring=None):
+def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=None, scoring=None,
+                    no_repeat_ngram=0, repetition_penalty=1.0, min_len=1):
     """Run the planned searches; returns per qa_id the (n-best list, best score) of beam search, the greedy token list, the
     samples' (tokens, score) pairs, best first (``sampling``: samples / temperature / top_k / top_p / seed), or the candidates'
     score dicts in input order (``scoring``: tokens = per qa_id its candidates' token lists, max_len, width — one session shape
-    per bucket)."""
+    per bucket).  ``no_repeat_ngram`` / ``repetition_penalty`` constrain beam search, greedy and sample (decode.py; off by default);
+    ``min_len``: the shortest response beam search and sample may finish."""
     from . import decode
     from .data_handler import make_batch
     from .decode import beam_search_decode_many, greedy_decode_many
     sos, eos, unk, pad = vocab["<sos>"], vocab["<eos>"], vocab["<unk>"], vocab["<blank>"]
     results = {}
     batch, batch_shape = None, None
+    con = dict(no_repeat_ngram=int(no_repeat_ngram), repetition_penalty=float(repetition_penalty))
     for ids, n_real, shape in searches:
         x, h, q, a, c = shape
         index = ([vids[i] for i in ids], ids, x, h, q, a, c, len(ids))
@@ -322,29 +338,34 @@ def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, 
         batch = make_batch(corpus, index, pad, separate_caption=True, out=batch if key == batch_shape else None)
         batch_shape = key
         if decode_style == "beam_search":
-            res = beam_search_decode_many(model, batch, maxlen, sos, unk, eos, pad, beam=beam, penalty=penalty, nbest=nbest, min_len=1)
+            res = beam_search_decode_many(model, batch, maxlen, sos, unk, eos, pad, beam=beam, penalty=penalty, nbest=nbest, min_len=min_len,
+                                          **con)
         elif decode_style == "sample":
             # keys = qa_ids: a QA's random stream is the same in any bucket, at any D, with --no-buckets
-            res = decode.sample_decode_many(model, batch, maxlen, sos, eos, pad, keys=ids, banned=(unk, pad, sos), min_len=1, penalty=penalty,
-                                            **sampling)
+            res = decode.sample_decode_many(model, batch, maxlen, sos, eos, pad, keys=ids, banned=(unk, pad, sos), min_len=min_len, penalty=penalty,
+                                            **sampling, **con)
         elif decode_style == "score":
             # (a padding copy of the last QA rides with one candidate: its rows are dropped)
             cands = [scoring["tokens"][i] if k < n_real else scoring["tokens"][i][:1] for k, i in enumerate(ids)]
             res = decode.score_candidates(model, batch, cands, sos, eos, pad, penalty=penalty, max_len=scoring["max_len"], width=scoring["width"])
         else:
-            res = greedy_decode_many(model, batch, maxlen, sos, pad).cpu().tolist()
+            res = greedy_decode_many(model, batch, maxlen, sos, pad, **con).cpu().tolist()
         for i, r in zip(ids[:n_real], res[:n_real]):
             results[i] = r
     return results
 
 
 def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0, nbest=5, decode_style="greedy", undisclosed_only=False,
-                      ref_data=None, dialogues_per_search=0, buckets=True, sampling=None, candidates=None):
+                      ref_data=None, dialogues_per_search=0, buckets=True, sampling=None, candidates=None, no_repeat_ngram=0,
+                      repetition_penalty=1.0, min_len=1):
     """Decode every QA of ``data`` (data_handler.load) and return the reference's result dict, logging the reference's
     QS / REF / HYP lines per QA.  decode_style "score" generates nothing: every QA's ``candidates`` (load_candidates' ``spec``; its
     own answer without one) are scored and logged as CAND lines, best first; the answer is the best-scoring candidate, every turn
     gains "scores" in input order, and the corpus perplexity and ranking metrics (score_metrics) are logged at the end.  Candidates
-    are scored whole: ``maxlen`` does not cut them."""
+    are scored whole: ``maxlen`` does not cut them.  ``no_repeat_ngram`` / ``repetition_penalty`` / ``min_len``: as decode_searches
+    (a scoring run takes no constraints: ValueError)."""
+    if decode_style == "score" and (no_repeat_ngram != 0 or repetition_penalty != 1.0):
+        raise ValueError("generate_response: no_repeat_ngram / repetition_penalty constrain a search; a scoring run has none")
     vocablist = sorted(vocab.keys(), key=lambda s: vocab[s])
     eos = vocab["<eos>"]
     lens = qa_lengths(data)
@@ -369,7 +390,7 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
     logging.info("%d QAs in %d searches over %d padded shapes", len(lens), len(searches), n_buckets)
     vids = {it[1]: it[0] for it in data["dialogs"]}
     res = decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=sampling,
-                          scoring=scoring)
+                          scoring=scoring, no_repeat_ngram=no_repeat_ngram, repetition_penalty=repetition_penalty, min_len=min_len)
     answers = []
     scores = [] if decode_style == "score" else None
     qa_id = 0
@@ -455,7 +476,8 @@ def main(argv=None):
                                decode_style=args.decode_style, undisclosed_only=args.undisclosed_only, ref_data=labeled_test,
                                dialogues_per_search=args.dialogues_per_search, buckets=not args.no_buckets,
                                sampling=dict(samples=args.samples, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-                                             seed=args.sample_seed), candidates=args.candidates)
+                                             seed=args.sample_seed), candidates=args.candidates,
+                               no_repeat_ngram=args.no_repeat_ngram, repetition_penalty=args.repetition_penalty, min_len=args.min_length)
     wall = time.time() - start_time
     n_qa = len(test_data["dialogs"])
     logging.info("----------------")

@@ -167,6 +167,12 @@ class ScoreArgs(C.Structure):
                 ("target", C.c_void_p), ("tok_logp", C.c_void_p), ("tok_rank", C.c_void_p), ("seq_logp", C.c_void_p), ("seq_len", C.c_void_p)]
 
 
+class ConstrainArgs(C.Structure):
+    _fields_ = [("rows", C.c_int), ("V", C.c_int), ("ldx", C.c_long), ("ldo", C.c_long), ("logp", C.c_void_p), ("out", C.c_void_p),
+                ("ngram", C.c_int), ("theta", C.c_float), ("L", C.c_int), ("hist", C.c_void_p), ("ldh", C.c_long), ("hist_len", C.c_void_p),
+                ("log_tok", C.c_void_p), ("log_parent", C.c_void_p), ("step", C.c_void_p), ("width", C.c_int), ("rows_per_step", C.c_int)]
+
+
 class LnFinalizeDesc(C.Structure):
     _fields_ = [("partial", C.c_void_p), ("nparts", C.c_int), ("d", C.c_int), ("da2", C.c_void_p), ("db2", C.c_void_p)]
 
@@ -216,6 +222,7 @@ SYMBOLS = {
     "mtn_beam_advance": (C.c_int, [C.POINTER(BeamArgs), _P]),
     "mtn_sample_rows": (C.c_int, [C.POINTER(SampleArgs), _P]),
     "mtn_score_rows": (C.c_int, [C.POINTER(ScoreArgs), _P]),
+    "mtn_constrain_rows": (C.c_int, [C.POINTER(ConstrainArgs), _P]),
     "mtn_debug_hold_cus": (C.c_int, [C.c_int, C.c_int, C.c_int, _P]),
     "mtn_gemm_tt_table_aux": (C.c_int, [C.c_int, C.c_int, C.POINTER(GemmProblem), C.POINTER(TtAux), _P]),
     "mtn_layernorm_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P]),

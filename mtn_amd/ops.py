@@ -1008,6 +1008,74 @@ def sample_rows(logp, seed, keys, step, log=None, max_len=1, **kw):
     return log
 
 
+def constrain_rows(logp, ngram=0, theta=1.0, *, hist=None, hist_len=None, log_tok=None, log_parent=None, step=None, width=1,
+                   rows_per_step=1, log_len=None, out=None):
+    """N-gram blocking and repetition penalty on the rows of logp (rows, V) fp32 from each row's history (csrc/constrain.hip;
+    include/mtn_hip.h mtn_constrain_rows gives the definitions).  In place unless ``out`` (same shape, no overlap) is given.
+    History, explicit: ``hist`` (rows, >= L) int32 and ``hist_len`` (rows,) int32 on the device.  Or from a search's step log:
+    ``log_tok`` / ``log_parent`` (L, rows) int32 (log_parent None: every row is its own parent) and ``step`` int32 with one counter per
+    ``rows_per_step`` rows; ``width`` = rows per dialogue.  The log and step may be tensors or raw device pointers (then ``log_len``, the
+    log's L, is required: a captured search passes pointers into its state blocks).  Returns the rows written."""
+    _require_cuda(logp)
+    if logp.dim() != 2 or logp.dtype != torch.float32 or (logp.size(1) > 1 and logp.stride(1) != 1) or logp.stride(0) < logp.size(1):
+        raise ValueError("constrain_rows: logp fp32 (rows, V) with unit column stride")
+    rows, V = logp.shape
+    ngram, theta = int(ngram), float(theta)
+    if not 0 <= ngram <= 8 or not theta >= 1.0:
+        raise ValueError("constrain_rows: 0 <= ngram <= 8, theta >= 1")
+    if out is None:
+        out = logp
+    else:
+        _require_cuda(out)
+        if out.shape != logp.shape or out.dtype != torch.float32 or (V > 1 and out.stride(1) != 1) or out.stride(0) < V:
+            raise ValueError("constrain_rows: out is fp32 of logp's shape with unit column stride")
+        span = lambda t: (t.data_ptr(), t.data_ptr() + ((rows - 1) * t.stride(0) + V) * 4)
+        (lo, hi), (olo, ohi) = span(logp), span(out)
+        ld, off = logp.stride(0), abs(olo - lo) // 4
+        # (equal row strides: rows meet only if the offset, modulo the stride, is less than V either way — two column blocks of one
+        # buffer do not overlap; offset 0 is logp itself)
+        apart = out.stride(0) == ld and (off == 0 or (off % ld >= V and ld - off % ld >= V))
+        if lo < ohi and olo < hi and not apart:
+            raise ValueError("constrain_rows: out overlaps logp without being logp (in place: leave out None or pass logp itself)")
+    a = L.ConstrainArgs()
+    a.rows, a.V, a.ldx, a.ldo, a.logp, a.out = rows, V, logp.stride(0), out.stride(0), logp.data_ptr(), out.data_ptr()
+    a.ngram, a.theta = ngram, theta
+    if hist is not None:
+        if hist_len is None:
+            raise ValueError("constrain_rows: hist needs hist_len, int32 (rows,)")
+        _require_cuda(hist, hist_len)
+        if (hist.dim() != 2 or hist.dtype != torch.int32 or hist.size(0) != rows or hist.size(1) < 1 or hist.stride(1) != 1 or hist_len.dtype != torch.int32
+                or hist_len.numel() != rows or not hist_len.is_contiguous() or log_tok is not None):
+            raise ValueError("constrain_rows: hist int32 (rows, L) with unit column stride and hist_len int32 (rows,); one history source")
+        a.L = hist.size(1) if log_len is None else int(log_len)
+        if a.L > hist.size(1):
+            raise ValueError("constrain_rows: log_len exceeds the history table's width")
+        a.hist, a.ldh, a.hist_len = hist.data_ptr(), max(hist.stride(0), hist.size(1)), hist_len.data_ptr()
+    else:
+        if log_tok is None or step is None:
+            raise ValueError("constrain_rows: a history source is required (hist + hist_len, or log_tok + step)")
+        width, rows_per_step = int(width), int(rows_per_step)
+        if not 1 <= width <= 16 or rows % width or rows_per_step < 1:
+            raise ValueError("constrain_rows: 1 <= width <= 16, rows a multiple of width, rows_per_step >= 1")
+        for t in (log_tok, log_parent):
+            if t is not None and not isinstance(t, int):
+                _require_cuda(t)
+                if t.dtype != torch.int32 or t.dim() != 2 or t.size(1) != rows or not t.is_contiguous() or (log_len is not None and t.size(0) < int(log_len)):
+                    raise ValueError("constrain_rows: the step log is int32, contiguous (L, rows)")
+        if not isinstance(step, int):
+            _require_cuda(step)
+            if step.dtype != torch.int32 or not step.is_contiguous() or step.numel() * rows_per_step < rows:
+                raise ValueError("constrain_rows: step int32, one counter per rows_per_step rows")
+        if log_len is None:
+            if isinstance(log_tok, int):
+                raise ValueError("constrain_rows: log_len is required with a raw log pointer")
+            log_len = log_tok.size(0)
+        as_ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        a.L, a.log_tok, a.log_parent, a.step, a.width, a.rows_per_step = int(log_len), as_ptr(log_tok), as_ptr(log_parent), as_ptr(step), width, rows_per_step
+    L.check(L.load().mtn_constrain_rows(C.byref(a), L.stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ memory K/V, ahead of the layers
 def project_memories(items, lp_dtype, outs=None):
     """K|V projections (mtn.py:257-258) of CONSTANT memories for many sublayers at once: items = [(mem_lp (B,m,d) compute dtype,

@@ -4,7 +4,8 @@ text lengths of the DSTC7-AVSD test set (history of up to 3 earlier turns, capti
 features of 10-40 and 30-180 frames, run.sh's model (6 blocks, d_model 512, d_ff 2048, 8 heads; random weights), beam 5,
 penalty 1.0, maxlen 30.  Settings: buckets with automatic D, --no-buckets (on the first --no-buckets-qas QAs: it
 captures graphs per QA shape), greedy, and --decode-style sample (1 and 4 samples per QA, next to greedy).  Prints one JSON line.
---styles picks a subset (beam, greedy, no_buckets, sample).
+--styles picks a subset (beam, greedy, no_buckets, sample).  --no-repeat-ngram / --repetition-penalty constrain every search of the run
+(generate.py's flags of the same names; off by default).
 
     python tools/generate_bench.py [--dialogs 1710] [--no-buckets-qas 300]
 """
@@ -48,6 +49,8 @@ def main():
     ap.add_argument("--no-buckets-qas", type=int, default=300)
     ap.add_argument("--maxlen", type=int, default=30)
     ap.add_argument("--styles", default="beam,greedy,no_buckets,sample", help="comma-separated: beam, greedy, no_buckets, sample")
+    ap.add_argument("--no-repeat-ngram", type=int, default=0)
+    ap.add_argument("--repetition-penalty", type=float, default=1.0)
     a = ap.parse_args()
     import logging
     import torch
@@ -76,7 +79,8 @@ def main():
         corpus = dh.DeviceCorpus(data, dev)
         lens = G.qa_lengths(data)
         n = len(lens)
-        out = {"qas": n, "buckets": len({G.bucket_key(l) for l in lens}), "maxlen": a.maxlen, "beam": 5}
+        out = {"qas": n, "buckets": len({G.bucket_key(l) for l in lens}), "maxlen": a.maxlen, "beam": 5,
+               "no_repeat_ngram": a.no_repeat_ngram, "repetition_penalty": a.repetition_penalty}
 
         def timed(style, buckets, subset=None, sampling=None):
             d = data if subset is None else dict(data, dialogs=data["dialogs"][:subset],
@@ -84,7 +88,8 @@ def main():
             torch.cuda.synchronize()
             t0 = time.time()
             G.generate_response(model, d, corpus, vocab, maxlen=a.maxlen, beam=5, penalty=1.0, nbest=5, decode_style=style,
-                                undisclosed_only=True, buckets=buckets, sampling=sampling)
+                                undisclosed_only=True, buckets=buckets, sampling=sampling, no_repeat_ngram=a.no_repeat_ngram,
+                                repetition_penalty=a.repetition_penalty)
             torch.cuda.synchronize()
             dt = time.time() - t0
             return {"qas": len(d["dialogs"]), "seconds": round(dt, 2), "qa_per_s": round(len(d["dialogs"]) / dt, 1)}
