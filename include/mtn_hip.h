@@ -666,6 +666,25 @@ typedef struct {
     int width, rows_per_step;
 } mtn_constrain_args;
 int mtn_constrain_rows(const mtn_constrain_args* args /* host */, void* stream);
+/* Ensemble decoding (version 118): combine the rows of M checkpoints, 1 <= M <= 8, into one row of log-probabilities that the selection
+ * launches above read as they read a single model's.  x[m] is member m's row matrix [rows, V] (fp32, row stride ld[m] >= V; V < 2^24):
+ * logits or log-probabilities — every member row is normalised here, with lse_m = logsumexp over c of x_m[c].  w[m] >= 0 are the weights;
+ * the caller has normalised them to sum 1.  One launch, one workgroup per row, fixed reduction order, no atomics: two launches give the
+ * same bits.  out [rows, V] (row stride ldo >= V) must not overlap any input.
+ *   mode 0, prob     out[c] = log sum_m w_m exp(x_m[c] - lse_m): the arithmetic mean of the members' probabilities, evaluated as
+ *                    max_m a_m + log sum_m exp(a_m - max_m a_m) with a_m = log w_m + x_m[c] - lse_m.  Normalised as it stands.
+ *   mode 1, logprob  s[c] = sum over the m with w_m > 0 of w_m (x_m[c] - lse_m); out[c] = s[c] - logsumexp over c of s[c]: the weighted
+ *                    geometric mean, renormalised.
+ * A member with w_m == 0 contributes nothing in either mode, even where its entry is -inf (it is never read: no 0 * inf).  prob: a -inf
+ * entry contributes 0, and a column that is -inf in every weighted member gives -inf.  logprob: a -inf entry in any weighted member gives
+ * -inf.  Every weighted member row must hold at least one finite entry; this is NOT checked (the rows are device memory).
+ * MTN_ERR_ARG: a null pointer, M outside 1..8, ld or ldo < V, V >= 2^24, a negative or non-finite weight, all weights 0, another mode. */
+typedef struct {
+    int rows, V, M, mode;
+    const float* x[8]; long ld[8]; float w[8];
+    float* out; long ldo;
+} mtn_ensemble_args;
+int mtn_ensemble_rows(const mtn_ensemble_args* args /* host */, void* stream);
 /* Generator (mtn.py:62-69) at inference: out[row][c] = x[row][c] - logsumexp(x[row][0..V-1]) over logit rows x [rows, V] (row
  * strides ldx / ldo; out may be x).  The logits themselves are one mtn_gemm (x W^T + b, fp32 out). */
 int mtn_log_softmax_rows(const float* x, int rows, int V, long ldx, float* out, long ldo, void* stream);

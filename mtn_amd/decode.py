@@ -37,7 +37,9 @@ class DecodeSession:
     A session is reusable for further dialogues of the same shapes (``load``): buffers and the captured graph persist."""
 
     def __init__(self, model, batch, max_len: int, width: int, pad: int = 1, use_graph: bool = True, kv_cache: bool = False,
-                 select=None):
+                 select=None, share=None):
+        # share: another session of the same shape whose per-step inputs (tokens, pos, the cache's parent row) this one reads instead of
+        # allocating its own — the members of an Ensemble session all read ONE set
         self.model, self.width, self.max_len, self.pad = model, width, max_len, pad
         self.kv_cache = bool(kv_cache)
         # select = (k, column): the pass also leaves, per row, its k largest log-probabilities, their columns and that column's
@@ -49,8 +51,8 @@ class DecodeSession:
         self.q = self.cp = self.hs = self.aes = self.masks = None
         self._kvs, self._kv_pairs = None, []
         self.D = batch.query.size(0)
-        self.tokens = torch.full((self.D * width, max_len), pad, dtype=torch.long, device=dev)
-        self.pos = torch.zeros(1, dtype=torch.long, device=dev)
+        self.tokens = share.tokens if share is not None else torch.full((self.D * width, max_len), pad, dtype=torch.long, device=dev)
+        self.pos = share.pos if share is not None else torch.zeros(1, dtype=torch.long, device=dev)
         self.trg_mask = subsequent_mask(max_len, device=dev)       # (1, L, L): data_utils.py:204 uses the causal mask only
         ops.prepare_masks(self.trg_mask)
         self.logp = None
@@ -68,7 +70,7 @@ class DecodeSession:
             nl = len(model.decoder.layers)
             self._cache = [torch.zeros(nl, W, L, 2 * d, device=dev, dtype=lp) for _ in range(2)]
             self._cur = 0
-            self._parent = torch.arange(W, device=dev)
+            self._parent = share._parent if share is not None else torch.arange(W, device=dev)
             self._self_mem = torch.zeros(W, L, d, device=dev, dtype=torch.float32)      # shape carrier (never read: K|V are ready)
             self._self_mem._mtn_lp = torch.zeros(W, L, d, device=dev, dtype=lp) if lp != torch.float32 else self._self_mem
             self._self_mask = torch.zeros(W, 1, L, dtype=torch.bool, device=dev)
@@ -78,7 +80,8 @@ class DecodeSession:
 
     @staticmethod
     def signature(model, batch, max_len, width):
-        return (id(model), model._flat.data_ptr() if model._flat is not None else 0, model.compute_dtype, width, max_len, tuple(batch.query.shape), tuple(batch.his.shape),
+        ident = model.signature() if isinstance(model, Ensemble) else (id(model), model._flat.data_ptr() if model._flat is not None else 0, model.compute_dtype)
+        return ident + (width, max_len, tuple(batch.query.shape), tuple(batch.his.shape),
                 tuple(batch.cap.shape), tuple(tuple(f.shape) for f in (batch.fts or [])), str(batch.query.device))
 
     def load(self, batch):
@@ -194,7 +197,21 @@ class DecodeSession:
                     mine.copy_(rep(mk))
                     mine._mtn_u8.copy_(mine)
 
+    def _head(self, rows):
+        """What a pass leaves: its rows and, with in-pass selection, their heads."""
+        self.logp = rows
+        if self.select is not None:
+            self.top = ops.topk_rows(self.logp, min(self.select[0], self.logp.size(1)), self.select[1])
+
+    def _generate(self, x):
+        """The generator on the rows of a pass: (rows, V) fp32 log-probabilities (mtn.py:68-69) — or, for a member of an Ensemble session,
+        its logits: csrc/ensemble.hip normalises every member row itself."""
+        return self.model.generator.logits(x) if getattr(self, "_logits", False) else self.model.generator(x).float()
+
     def _pass(self):
+        self._head(self._target_rows())
+
+    def _target_rows(self):
         m = self.model
         cap_mask, his_mask, q_mask = self.masks
         x = m.embed_target(self.tokens)
@@ -207,11 +224,12 @@ class DecodeSession:
             m.clear_memory_kv()
         x = m.decoder.norm(x)
         last = x.index_select(1, self.pos).squeeze(1)               # (width, d): the position being extended
-        self.logp = m.generator(last).float()                       # (width, V) log-probabilities (mtn.py:68-69)
-        if self.select is not None:
-            self.top = ops.topk_rows(self.logp, min(self.select[0], self.logp.size(1)), self.select[1])
+        return self._generate(last)                                 # (width, V)
 
     def _pass_cached(self, cur: int):
+        self._head(self._target_rows_cached(cur))
+
+    def _target_rows_cached(self, cur: int):
         """One target position (self.pos) for every hypothesis, against the prefix cache: gather the cache rows of the parents
         (copy 1-cur -> cur), embed the newest token, per layer project its K|V into the cache and run the layer on that one row."""
         m = self.model
@@ -233,9 +251,7 @@ class DecodeSession:
         finally:
             m.clear_memory_kv()
         x = m.decoder.norm(x)
-        self.logp = m.generator(x.squeeze(1)).float()
-        if self.select is not None:
-            self.top = ops.topk_rows(self.logp, min(self.select[0], self.logp.size(1)), self.select[1])
+        return self._generate(x.squeeze(1))
 
     def _step_cached(self, prefix_lists):
         l = len(prefix_lists[0][0])
@@ -313,6 +329,9 @@ class DecodeSession:
     def _pass_score(self):
         """_pass for scoring: the same target-stream pass, but the generator runs at EVERY position — logits only — and
         mtn_score_rows (csrc/score.hip) reads the targets' log-probabilities and ranks off them: no (rows, V) log-softmax."""
+        ops.score_rows(self._score_logits(), self._score_target, self.pad, out=self._score_out)
+
+    def _score_logits(self):
         m = self.model
         cap_mask, his_mask, q_mask = self.masks
         x = m.embed_target(self.tokens)
@@ -325,7 +344,7 @@ class DecodeSession:
             m.clear_memory_kv()
         x = m.decoder.norm(x)
         z = m.generator.logits(x)                                   # (D * width, max_len, V) fp32
-        ops.score_rows(z.view(-1, z.size(-1)), self._score_target, self.pad, out=self._score_out)
+        return z.view(-1, z.size(-1))
 
     def score(self, rows_tokens: Sequence[Sequence[int]], start: int, eos: int):
         """Teacher-forced scores of D * width token lists (row d * width + i belongs to dialogue d; no <sos> / <eos> in them, at most
@@ -385,6 +404,8 @@ class MegaDecodeSession(DecodeSession):
     def supported(model, batch, max_len, width) -> bool:
         if os.environ.get("MTN_DECODE_MEGA", "1") == "0" or not batch.query.is_cuda:
             return False
+        if isinstance(model, Ensemble):                             # every member runs its own persistent step: all of them or none
+            return all(MegaDecodeSession.supported(m, batch, max_len, width) for m in model.active)
         try:
             layer = model.decoder.layers[0]
             d, h = layer.size, layer.self_attn.h
@@ -414,8 +435,8 @@ class MegaDecodeSession(DecodeSession):
         """The most workgroups the persistent launch may use on this device: one per compute unit, at most 256."""
         return min(256, int(torch.cuda.get_device_properties(device).multi_processor_count))
 
-    def __init__(self, model, batch, max_len, width, pad=1, use_graph=True, select=None):
-        super().__init__(model, batch, max_len, width, pad=pad, use_graph=use_graph, kv_cache=False, select=select)
+    def __init__(self, model, batch, max_len, width, pad=1, use_graph=True, select=None, share=None):
+        super().__init__(model, batch, max_len, width, pad=pad, use_graph=use_graph, kv_cache=False, select=select, share=share)
         from . import lib as L
         dev = batch.query.device
         layers = model.decoder.layers
@@ -435,8 +456,11 @@ class MegaDecodeSession(DecodeSession):
         # what the host changes every step, in ONE pinned block -> ONE copy: [W newest tokens (int64) | position (int32, padded) | anc (W x L int32)]
         self._off_pos, self._off_anc = 8 * W, 8 * W + 8
         nbytes = self._off_anc + 4 * W * Lm
-        self._host = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-        self._devblk = torch.zeros(nbytes, device=dev, dtype=torch.uint8)
+        if share is None:
+            self._host = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+            self._devblk = torch.zeros(nbytes, device=dev, dtype=torch.uint8)
+        else:                               # (same W and max_len: the same layout) this launch reads the block the sharer's bookkeeping writes
+            self._host, self._devblk = share._host, share._devblk
         import numpy as np
         hb = self._host.numpy()                       # numpy views of the pinned block: the per-step bookkeeping below is plain numpy slicing
         self._h_tok = hb[:8 * W].view(np.int64)
@@ -518,14 +542,21 @@ class MegaDecodeSession(DecodeSession):
         # the step's host inputs and (with device-side selection) its host outputs travel INSIDE the pass — copy nodes of the captured graph —
         # so a generated token costs the host one replay and one stream synchronisation
         self._devblk.copy_(self._host, non_blocking=True)
-        L.check(L.load().mtn_decode_step(C.byref(self._args), self._stages_dev.data_ptr(), self._grid, L.stream_ptr()))
-        g = m.generator._fused
-        self.logp = ops.generator_log_probs(self._out_lp, g["w_lp"], g["bias"])          # (W, V) fp32 log-probabilities (mtn.py:68-69)
+        self.logp = self._step_rows()                                                    # (W, V) fp32 log-probabilities (mtn.py:68-69)
         if self.select is not None:
             self.top = ops.topk_rows(self.logp, min(self.select[0], self.logp.size(1)), self.select[1])
             if self._top_host is None:
                 self._top_host = torch.empty(self.top.shape, dtype=self.top.dtype).pin_memory()
             self._top_host.copy_(self.top, non_blocking=True)
+
+    def _step_rows(self, logits=False):
+        """One persistent decode step on the shared [tokens | pos | anc] block and the generator on its output rows: (W, V) fp32
+        log-probabilities, or the logits (a member of an Ensemble session: csrc/ensemble.hip normalises them)."""
+        import ctypes as C
+        from . import lib as L
+        L.check(L.load().mtn_decode_step(C.byref(self._args), self._stages_dev.data_ptr(), self._grid, L.stream_ptr()))
+        g = self.model.generator._fused
+        return (ops.generator_logits if logits else ops.generator_log_probs)(self._out_lp, g["w_lp"], g["bias"])
 
     def top_host(self):
         """The rows' heads of the last step on the host (a pinned block the pass itself filled)."""
@@ -620,10 +651,8 @@ class MegaDecodeSession(DecodeSession):
                 self._devblk.copy_(self._blk_init, non_blocking=True)
                 self._bstate.copy_(self._bstate_init, non_blocking=True)
                 self._log[o_flags:].zero_()
-                g = self.model.generator._fused
                 for _ in range(Lm):
-                    L.check(L.load().mtn_decode_step(C.byref(self._args), self._stages_dev.data_ptr(), self._grid, L.stream_ptr()))
-                    logp = ops.generator_log_probs(self._out_lp, g["w_lp"], g["bias"])
+                    logp = self._step_rows()
                     if constrained:
                         ops.constrain_rows(logp, ngram, theta, log_tok=a.log_tok, log_parent=a.log_parent, step=a.step, width=self.width,
                                            rows_per_step=self.width, log_len=Lm)
@@ -690,10 +719,8 @@ class MegaDecodeSession(DecodeSession):
             def body():
                 self._devblk.copy_(self._sblk_init, non_blocking=True)
                 self._sstate.copy_(self._sstate_host, non_blocking=True)
-                g = self.model.generator._fused
                 for _ in range(Lm):
-                    L.check(L.load().mtn_decode_step(C.byref(self._args), self._stages_dev.data_ptr(), self._grid, L.stream_ptr()))
-                    logp = ops.generator_log_probs(self._out_lp, g["w_lp"], g["bias"])
+                    logp = self._step_rows()
                     if constrained:
                         ops.constrain_rows(logp, ngram, theta, log_tok=self._slog[0], step=s0[8 + 8 * W:].view(torch.int32), width=1, rows_per_step=1)
                     ops.sample_rows(logp, s0[:8].view(torch.int64), s0[8:8 + 8 * W].view(torch.int64), s0[8 + 8 * W:].view(torch.int32), log,
@@ -793,6 +820,131 @@ class MegaDecodeSession(DecodeSession):
         return [self.logp[d_ * W:d_ * W + len(p)] for d_, p in enumerate(prefix_lists)]
 
 
+class Ensemble:
+    """Several checkpoints decoded as one model: pass it wherever the functions below take a model.  Per generated token every member
+    runs its own target-stream pass on its own session (own encoder side, hoisted K|V and prefix cache), and the members' generator
+    logits become ONE row of log-probabilities per hypothesis in one launch (csrc/ensemble.hip; include/mtn_hip.h mtn_ensemble_rows):
+    ``mode`` "prob", log sum_m w_m p_m, or "logprob", sum_m w_m log p_m renormalised.  Constraints, selection, sampling and scoring read
+    those rows as they read a single model's.  Members may differ in depth, width, auto_encoder_ft and compute dtype; they share the
+    vocabulary size and the batch.  ``weights``: one number >= 0 per member (normalised to sum 1; None: uniform) — a member at weight 0
+    is not run at all.  ValueError: no member, more than 8, the same model object twice, different vocabulary sizes, bad weights / mode."""
+
+    def __init__(self, models, weights=None, mode="prob"):
+        self.models = list(models)
+        if not 1 <= len(self.models) <= ops.ENSEMBLE_MAX:
+            raise ValueError(f"Ensemble: 1 to {ops.ENSEMBLE_MAX} members")
+        if len({id(m) for m in self.models}) != len(self.models):
+            raise ValueError("Ensemble: the same model object twice (decode sessions are per model object: pass a copy)")
+        if mode not in ops.ENSEMBLE_MODES:
+            raise ValueError("Ensemble: mode is 'prob' or 'logprob'")
+        self.mode = mode
+        self.weights = tuple(float(w) for w in ops.ensemble_weights(len(self.models), weights))
+        vocab = {int(m.generator.proj.weight.size(0)) for m in self.models}
+        if len(vocab) != 1:
+            raise ValueError(f"Ensemble: the members' vocabulary sizes differ ({sorted(vocab)})")
+        self.vocab = vocab.pop()
+        self.active = [m for m, w in zip(self.models, self.weights) if w > 0]               # the members that are run ...
+        self.active_weights = [w for w in self.weights if w > 0]                            # ... and their weights (sum 1)
+
+    def prepare(self):
+        for m in self.active:
+            m.prepare()
+
+    @property
+    def _flat_version(self):
+        """Changes when any member's weights were replaced: a cached session of this ensemble is then stale."""
+        return tuple(getattr(m, "_flat_version", None) for m in self.active)
+
+    def signature(self):
+        return (tuple((id(m), m._flat.data_ptr() if m._flat is not None else 0, m.compute_dtype) for m in self.models), self.weights, self.mode)
+
+    def same_members(self, other) -> bool:
+        return isinstance(other, Ensemble) and len(other.models) == len(self.models) and all(a is b for a, b in zip(self.models, other.models))
+
+    def combine(self, rows):
+        """The active members' (rows, V) logits -> (rows, V) log-probabilities of the ensemble, one launch."""
+        return ops.ensemble_rows(rows, self.active_weights, self.mode)
+
+
+class _OwnsMembers:
+    """What the two Ensemble sessions share: they skip their base class' constructor (there is no single model to load) and own one session
+    per active member instead.  Member 0 allocates the per-step inputs and every other member is built with ``share=`` member 0, so all of
+    them read ONE set; the attributes of that shared state the base class' methods read (SHARED: the pinned block and its views, offsets, row
+    count, grid, the cache's parent row) are looked up on member 0 — nothing is copied; every other missing attribute raises as usual.  What a
+    session computes or captures (logp, top, graphs, search keys and logs) is set by those methods on this object itself."""
+
+    def _own(self, cls, ens, batch, max_len, width, pad, use_graph, select, **kw):
+        self.model, self.width, self.max_len, self.pad = ens, width, max_len, pad
+        self.select = select if (select is not None and batch.query.is_cuda) else None
+        self.use_graph = use_graph and batch.query.is_cuda
+        self.top = self.logp = self._graph = self._prev = self._top_host = None
+        self.members = []
+        for m in ens.active:
+            self.members.append(cls(m, batch, max_len, width, pad=pad, use_graph=use_graph, share=self.members[0] if self.members else None, **kw))
+        self.D = self.members[0].D
+
+    # the shared per-step state, by name: anything else a session lacks (a member's own outputs, arguments, flags; a typo) raises
+    SHARED = frozenset(("tokens", "pos", "_parent", "_host", "_devblk", "_h_tok", "_h_pos", "_h_anc", "_off_pos", "_off_anc", "_W", "_x", "_grid"))
+
+    def __getattr__(self, name):             # (only reached for what this object does not hold itself)
+        if name in _OwnsMembers.SHARED and "members" in self.__dict__ and self.members:
+            return getattr(self.members[0], name)
+        raise AttributeError(f"{type(self).__name__} has no attribute {name!r}")
+
+    def load(self, batch):
+        for s in self.members:
+            s.load(batch)
+        self.D = self.members[0].D
+
+
+class EnsembleSession(_OwnsMembers, DecodeSession):
+    """DecodeSession of an Ensemble on the launch-per-sublayer pass (full prefix or prefix K/V cache): it owns one DecodeSession per active
+    member, all reading ONE tokens / pos (/ parent) tensor, and its pass is the members' passes up to their logits + mtn_ensemble_rows + the
+    row heads — captured as one graph per step, exactly as a single model's pass is.  Everything the searches below do with a session
+    (step_many, score, logp, top) is DecodeSession's own code on the combined rows."""
+
+    def __init__(self, ens, batch, max_len, width, pad=1, use_graph=True, kv_cache=False, select=None):
+        self.kv_cache = bool(kv_cache)
+        self._own(DecodeSession, ens, batch, max_len, width, pad, use_graph, select, kv_cache=self.kv_cache)
+        for s in self.members:
+            s._logits = True
+        if self.kv_cache:
+            self._cur, self._graphs = 0, {}
+
+    def _target_rows(self):
+        return self.model.combine([s._target_rows() for s in self.members])
+
+    def _target_rows_cached(self, cur):
+        return self.model.combine([s._target_rows_cached(cur) for s in self.members])
+
+    def _score_logits(self):
+        return self.model.combine([s._score_logits() for s in self.members])
+
+
+class EnsembleMegaSession(_OwnsMembers, MegaDecodeSession):
+    """MegaDecodeSession of an Ensemble whose active members are ALL eligible for the persistent step: one MegaDecodeSession per member, every
+    one's launch reading the SAME [tokens | pos | anc] device block — the one the bookkeeping kernels write — so the prefix-cache slots are the
+    same in all of them and nothing is kept in sync.  A step is M persistent launches, M generator GEMMs (logits) and one mtn_ensemble_rows;
+    the captured searches (search / greedy / sample_log) and the stepped path are MegaDecodeSession's own code on the combined rows."""
+
+    def __init__(self, ens, batch, max_len, width, pad=1, use_graph=True, kv_cache=False, select=None):
+        self.kv_cache = False
+        self._own(MegaDecodeSession, ens, batch, max_len, width, pad, use_graph, select)
+
+    def _step_rows(self, logits=False):
+        return self.model.combine([s._step_rows(logits=True) for s in self.members])
+
+    def timed_out(self) -> bool:
+        """True if a poll of ANY member timed out: the members' flags are gathered on the device and read in one copy."""
+        return bool(torch.stack([s._sync[1] for s in self.members]).any().item())
+
+    def recover(self):
+        """A poll of ANY member timed out: every member's device state is made consistent again."""
+        for s in self.members:
+            s.recover()
+        self._prev = None
+
+
 _SESSIONS: dict = {}
 SELECT_MAX_K = 16        # csrc/select.hip SEL_MAX_K
 KV_CACHE_FROM = 32      # prefix K/V cache by default for searches longer than this (at the reference's max_len = 20 the full-prefix
@@ -809,12 +961,16 @@ def _session(model, batch, max_len, width, pad, use_graph, kv_cache=False, selec
         key += (mode,)
     ver = getattr(model, "_flat_version", None)
     hit = _SESSIONS.get(key)
-    if hit is not None and hit[1] == ver and hit[0].model is model:
+    if hit is not None and hit[1] == ver and (hit[0].model.same_members(model) if isinstance(model, Ensemble) else hit[0].model is model):
         hit[0].load(batch)
         return hit[0]
     if len(_SESSIONS) >= 8:
         _SESSIONS.clear()
-    if mega:
+    if isinstance(model, Ensemble):
+        # ONE entry that owns its members' sessions: the eviction above drops an ensemble whole, never one member's half of it
+        cls = EnsembleMegaSession if mega else EnsembleSession
+        sess = cls(model, batch, max_len, width, pad=pad, use_graph=use_graph, kv_cache=bool(kv_cache), select=select)
+    elif mega:
         sess = MegaDecodeSession(model, batch, max_len, width, pad=pad, use_graph=use_graph, select=select)
     else:
         sess = DecodeSession(model, batch, max_len, width, pad=pad, use_graph=use_graph, kv_cache=bool(kv_cache), select=select)

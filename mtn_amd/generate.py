@@ -79,6 +79,14 @@ def parse(argv=None):
     p.add_argument("--repetition-penalty", default=1.0, type=float,
                    help="multiply the log-probability of every token a response already holds by this (>= 1; 1 = off)")
     p.add_argument("--min-length", default=1, type=int, help="beam_search / sample: no response ends before this many tokens")
+    # ensemble decoding: further checkpoints combined with --model on the device, per generated token (decode.Ensemble)
+    p.add_argument("--ensemble-model", default=[], nargs="+", type=str, help="further checkpoints (PREFIX.pth.tar each), decoded together with --model")
+    p.add_argument("--ensemble-conf", default=[], nargs="+", type=str,
+                   help="their confs, one per --ensemble-model entry; without this flag every member uses --model-conf")
+    p.add_argument("--ensemble-weights", default=None, nargs="+", type=float,
+                   help="one weight >= 0 per member, --model's first (normalised to sum 1; default: uniform)")
+    p.add_argument("--ensemble-mode", default="prob", choices=["prob", "logprob"],
+                   help="prob: log of the weighted mean probability; logprob: weighted mean log-probability, renormalised")
     p.add_argument("--no-buckets", action="store_true",
                    help="one QA per search at its own padded shape, as the reference decodes (baseline / debugging)")
     args = p.parse_args(argv)
@@ -99,6 +107,17 @@ def parse(argv=None):
         p.error("--no-repeat-ngram / --repetition-penalty constrain a search: they do not go with --decode-style score")
     if args.min_length < 0:
         p.error("--min-length must be >= 0")
+    n_members = 1 + len(args.ensemble_model)
+    if args.ensemble_conf and len(args.ensemble_conf) != len(args.ensemble_model):
+        p.error("--ensemble-conf takes one conf per --ensemble-model entry (%d given for %d)" % (len(args.ensemble_conf), len(args.ensemble_model)))
+    if n_members > 8:
+        p.error("an ensemble has at most 8 members (--model and 7 --ensemble-model entries)")
+    if args.ensemble_weights is not None:
+        w = args.ensemble_weights
+        if len(w) != n_members:
+            p.error("--ensemble-weights takes one weight per member, --model's first (%d given for %d)" % (len(w), n_members))
+        if any(not (v >= 0 and v < float("inf")) for v in w) or not sum(w) > 0:
+            p.error("--ensemble-weights are finite numbers >= 0, not all of them 0")
     return args
 
 
@@ -145,6 +164,34 @@ def build_model(vocab, train_args, ft_sizes, state_dict, compute_dtype, device):
     model.to(device).eval()
     model.prepare()
     return model
+
+
+ENSEMBLE_DATA_FIELDS = ("fea_type", "include_caption", "separate_caption", "max_history_length", "merge_source")
+
+
+def check_ensemble_confs(confs, names=None):
+    """The members of an ensemble read ONE test set and write into ONE vocabulary: every conf (load_conf's pair) must carry the first one's
+    token-to-id map and its data-shaping fields (ENSEMBLE_DATA_FIELDS).  SystemExit naming the first member and field that differ."""
+    names = names or ["member %d" % i for i in range(len(confs))]
+    vocab0, args0 = confs[0]
+    for (vocab, a), name in zip(confs[1:], names[1:]):
+        if dict(vocab) != dict(vocab0):
+            raise SystemExit("ensemble: the vocabulary of %s differs from that of %s (%d and %d tokens): members share one token-to-id map"
+                             % (name, names[0], len(vocab), len(vocab0)))
+        for f in ENSEMBLE_DATA_FIELDS:
+            if getattr(a, f) != getattr(args0, f):
+                raise SystemExit("ensemble: %s of %s is %r, of %s %r: members read the same test data"
+                                 % (f, name, getattr(a, f), names[0], getattr(args0, f)))
+
+
+def load_ensemble_confs(model_conf, ensemble_models, ensemble_confs):
+    """[(vocab, train_args)] of --model and every --ensemble-model entry (its --ensemble-conf, or --model-conf without that flag), checked."""
+    paths = [model_conf] + (list(ensemble_confs) if ensemble_confs else [model_conf] * len(ensemble_models))
+    if len(paths) != 1 + len(ensemble_models):
+        raise SystemExit("ensemble: one conf per --ensemble-model entry")
+    confs = [load_conf(p) for p in paths]
+    check_ensemble_confs(confs, ["%s (member %d)" % (p, i) for i, p in enumerate(paths)])
+    return confs
 
 
 # ---------------------------------------------------------------------------------------------------------------- planning
@@ -194,7 +241,8 @@ def plan_searches(lens, per_search, buckets=True, frame_step=FRAME_STEP, text_st
 
 def auto_dialogues(model, device, shape, maxlen, width):
     """The most QAs side by side that the persistent decode step takes at this shape (D x width <= 16 rows, fewer at wide
-    feed-forwards), LAUNCH_PASS_D where it does not apply (fp32 models, unsupported widths)."""
+    feed-forwards), LAUNCH_PASS_D where it does not apply (fp32 models, unsupported widths).  An ensemble (decode.Ensemble) takes the
+    smallest count any of its members allows: the step applies to all of them or to none."""
     import types
     import torch
     from .decode import MegaDecodeSession
@@ -453,7 +501,11 @@ def main(argv=None):
     dev = torch.device("cuda", 0)                     # (as generate.py:133: --gpu is accepted and not used)
     torch.cuda.set_device(dev)
     logging.info("Loading model params from " + args.model)
-    vocab, train_args = load_conf(args.model_conf)
+    if args.ensemble_model:                           # every member's conf first: a mismatch ends the run before anything is loaded
+        member_confs = load_ensemble_confs(args.model_conf, args.ensemble_model, args.ensemble_conf)
+        vocab, train_args = member_confs[0]
+    else:
+        vocab, train_args = load_conf(args.model_conf)
     state = load_state_dict(args.model + ".pth.tar")
     logging.info("#vocab = %d" % len(vocab))
     logging.info("Loading test data from " + args.test_set)
@@ -463,7 +515,24 @@ def main(argv=None):
     if not (len(test_data["dialogs"]) and len(test_data["dialogs"][0]) > 6):
         raise SystemExit("generate: the model needs the caption as its own stream (a conf with separate_caption 1 and include_caption "
                          "caption|summary|caption,summary, as run.sh trains it)")
-    model = build_model(vocab, train_args, dh.feature_shape(test_data), state, args.compute_dtype, dev)
+    if not args.ensemble_model:
+        model = build_model(vocab, train_args, dh.feature_shape(test_data), state, args.compute_dtype, dev)
+    else:
+        # a member at weight 0 takes no part in the combination (decode.Ensemble never runs it): it is not built at all
+        from .decode import Ensemble
+        prefixes = [args.model] + list(args.ensemble_model)
+        weights = list(args.ensemble_weights) if args.ensemble_weights is not None else [1.0] * len(prefixes)
+        members = []
+        for k, (prefix, (_, member_args), w) in enumerate(zip(prefixes, member_confs, weights)):
+            if w == 0:
+                logging.info("ensemble: %s has weight 0 and is not loaded" % prefix)
+                continue
+            if k > 0:
+                logging.info("Loading model params from " + prefix)
+            sd = state if k == 0 else load_state_dict(prefix + ".pth.tar")
+            members.append(build_model(vocab, member_args, dh.feature_shape(test_data), sd, args.compute_dtype, dev))
+        model = Ensemble(members, [w for w in weights if w != 0], args.ensemble_mode)
+        logging.info("ensemble of %d members, mode %s, weights %s" % (len(members), model.mode, " ".join("%.6g" % w for w in model.weights)))
     corpus = dh.DeviceCorpus(test_data, dev)
     logging.info("#test sample = %d" % len(test_data["dialogs"]))
     logging.info("-----------------------generate--------------------------")

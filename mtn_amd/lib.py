@@ -173,6 +173,11 @@ class ConstrainArgs(C.Structure):
                 ("log_tok", C.c_void_p), ("log_parent", C.c_void_p), ("step", C.c_void_p), ("width", C.c_int), ("rows_per_step", C.c_int)]
 
 
+class EnsembleArgs(C.Structure):
+    _fields_ = [("rows", C.c_int), ("V", C.c_int), ("M", C.c_int), ("mode", C.c_int), ("x", C.c_void_p * 8), ("ld", C.c_long * 8),
+                ("w", C.c_float * 8), ("out", C.c_void_p), ("ldo", C.c_long)]
+
+
 class LnFinalizeDesc(C.Structure):
     _fields_ = [("partial", C.c_void_p), ("nparts", C.c_int), ("d", C.c_int), ("da2", C.c_void_p), ("db2", C.c_void_p)]
 
@@ -223,6 +228,7 @@ SYMBOLS = {
     "mtn_sample_rows": (C.c_int, [C.POINTER(SampleArgs), _P]),
     "mtn_score_rows": (C.c_int, [C.POINTER(ScoreArgs), _P]),
     "mtn_constrain_rows": (C.c_int, [C.POINTER(ConstrainArgs), _P]),
+    "mtn_ensemble_rows": (C.c_int, [C.POINTER(EnsembleArgs), _P]),
     "mtn_debug_hold_cus": (C.c_int, [C.c_int, C.c_int, C.c_int, _P]),
     "mtn_gemm_tt_table_aux": (C.c_int, [C.c_int, C.c_int, C.POINTER(GemmProblem), C.POINTER(TtAux), _P]),
     "mtn_layernorm_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -1076,6 +1076,62 @@ def constrain_rows(logp, ngram=0, theta=1.0, *, hist=None, hist_len=None, log_to
     return out
 
 
+ENSEMBLE_MODES = {"prob": 0, "logprob": 1}
+ENSEMBLE_MAX = 8         # csrc/ensemble.hip ENS_MAX_M
+
+
+def ensemble_weights(n, weights=None):
+    """The weights of an n-member ensemble as float64, normalised to sum 1 (None: uniform).  ValueError for a wrong count, a negative or
+    non-finite weight, or all weights 0."""
+    import numpy as np
+    w = np.full(n, 1.0, dtype=np.float64) if weights is None else np.asarray([float(v) for v in weights], dtype=np.float64)
+    if w.shape != (n,) or not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+        raise ValueError("ensemble: one finite weight >= 0 per member, not all of them 0")
+    return w / w.sum()
+
+
+def ensemble_rows(xs, weights=None, mode="prob", out=None):
+    """The rows of M <= 8 models combined into one row matrix of log-probabilities (csrc/ensemble.hip; include/mtn_hip.h mtn_ensemble_rows
+    gives the definitions): xs = M tensors (rows, V) fp32 with unit column stride and a row stride >= V, logits or log-probabilities (every
+    member row is normalised by the kernel); ``weights`` >= 0, normalised here to sum 1 in float64 (None: uniform); ``mode`` "prob" (log of the
+    weighted mean probability) or "logprob" (weighted mean log-probability, renormalised).  ``out``: fp32 (rows, V) overlapping no input.
+    Misuse raises ValueError; tensors that are not on the GPU raise MtnHipError, as in every operator of this module.  A single row's
+    stride is not looked at."""
+    xs = list(xs)
+    if not 1 <= len(xs) <= ENSEMBLE_MAX:
+        raise ValueError("ensemble_rows: 1 to 8 members")
+    if mode not in ENSEMBLE_MODES:
+        raise ValueError("ensemble_rows: mode is 'prob' or 'logprob'")
+    w = ensemble_weights(len(xs), weights)
+    _require_cuda(*xs)
+    x0 = xs[0]
+    for x in xs:
+        if (x.dim() != 2 or x.dtype != torch.float32 or x.shape != x0.shape or x.device != x0.device or x.numel() == 0
+                or (x.size(1) > 1 and x.stride(1) != 1) or (x.size(0) > 1 and x.stride(0) < x.size(1))):
+            raise ValueError("ensemble_rows: every member is fp32 (rows, V), non-empty, of one shape and device, with unit column stride")
+    rows, V = x0.shape
+    if V >= 1 << 24:
+        raise ValueError("ensemble_rows: V < 2^24")
+    if out is None:
+        out = torch.empty(rows, V, device=x0.device, dtype=torch.float32)
+    else:
+        _require_cuda(out)
+        if out.shape != x0.shape or out.dtype != torch.float32 or out.device != x0.device or (V > 1 and out.stride(1) != 1) or (rows > 1 and out.stride(0) < V):
+            raise ValueError("ensemble_rows: out is fp32 of the members' shape with unit column stride")
+        span = lambda t: (t.data_ptr(), t.data_ptr() + ((rows - 1) * t.stride(0) + V) * 4)
+        olo, ohi = span(out)
+        for x in xs:
+            lo, hi = span(x)
+            if lo < ohi and olo < hi:
+                raise ValueError("ensemble_rows: out overlaps a member")
+    a = L.EnsembleArgs()
+    a.rows, a.V, a.M, a.mode, a.out, a.ldo = rows, V, len(xs), ENSEMBLE_MODES[mode], out.data_ptr(), max(out.stride(0), V)
+    for m, x in enumerate(xs):
+        a.x[m], a.ld[m], a.w[m] = x.data_ptr(), max(x.stride(0), V), float(w[m])
+    L.check(L.load().mtn_ensemble_rows(C.byref(a), L.stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ memory K/V, ahead of the layers
 def project_memories(items, lp_dtype, outs=None):
     """K|V projections (mtn.py:257-258) of CONSTANT memories for many sublayers at once: items = [(mem_lp (B,m,d) compute dtype,

@@ -5,7 +5,8 @@ features of 10-40 and 30-180 frames, run.sh's model (6 blocks, d_model 512, d_ff
 penalty 1.0, maxlen 30.  Settings: buckets with automatic D, --no-buckets (on the first --no-buckets-qas QAs: it
 captures graphs per QA shape), greedy, and --decode-style sample (1 and 4 samples per QA, next to greedy).  Prints one JSON line.
 --styles picks a subset (beam, greedy, no_buckets, sample).  --no-repeat-ngram / --repetition-penalty constrain every search of the run
-(generate.py's flags of the same names; off by default).
+(generate.py's flags of the same names; off by default).  --ensemble M decodes with M random-init copies of the model (seeds 1..M)
+combined on the device (decode.Ensemble; --ensemble-mode prob|logprob) and records the dialogues per search auto_dialogues chose.
 
     python tools/generate_bench.py [--dialogs 1710] [--no-buckets-qas 300]
 """
@@ -51,6 +52,8 @@ def main():
     ap.add_argument("--styles", default="beam,greedy,no_buckets,sample", help="comma-separated: beam, greedy, no_buckets, sample")
     ap.add_argument("--no-repeat-ngram", type=int, default=0)
     ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--ensemble", type=int, default=1, help="members: this many random-init copies with different seeds (1 = a plain model)")
+    ap.add_argument("--ensemble-mode", default="prob", choices=["prob", "logprob"])
     a = ap.parse_args()
     import logging
     import torch
@@ -71,16 +74,25 @@ def main():
         vocab, targs = G.load_conf(os.path.join(root, "mtn.conf"))
         data = dh.load(targs.fea_type, fea_path, test_set, vocab, include_caption=targs.include_caption, separate_caption=True,
                        max_history_length=targs.max_history_length, merge_source=False, undisclosed_only=True)
-        torch.manual_seed(1)
         ft = dh.feature_shape(data)
-        sd = make_model(len(vocab), len(vocab), N=6, d_model=512, d_ff=2048, h=8, ft_sizes=ft, diff_encoder=True,
-                        auto_encoder_ft="query").state_dict()
-        model = G.build_model(vocab, targs, ft, sd, "bf16", dev)
+        members = []
+        for seed in range(1, a.ensemble + 1):
+            torch.manual_seed(seed)
+            sd = make_model(len(vocab), len(vocab), N=6, d_model=512, d_ff=2048, h=8, ft_sizes=ft, diff_encoder=True,
+                            auto_encoder_ft="query").state_dict()
+            members.append(G.build_model(vocab, targs, ft, sd, "bf16", dev))
+        model = members[0]
+        if a.ensemble > 1:
+            from mtn_amd.decode import Ensemble
+            model = Ensemble(members, mode=a.ensemble_mode)
         corpus = dh.DeviceCorpus(data, dev)
         lens = G.qa_lengths(data)
         n = len(lens)
         out = {"qas": n, "buckets": len({G.bucket_key(l) for l in lens}), "maxlen": a.maxlen, "beam": 5,
-               "no_repeat_ngram": a.no_repeat_ngram, "repetition_penalty": a.repetition_penalty}
+               "no_repeat_ngram": a.no_repeat_ngram, "repetition_penalty": a.repetition_penalty, "ensemble": a.ensemble, "ensemble_mode": a.ensemble_mode if a.ensemble > 1 else None}
+        per_search = lambda width: sorted({len(ids) for ids, _, _ in G.plan_searches(
+            lens, lambda shape: G.auto_dialogues(model, dev, shape, a.maxlen, width))})
+        out["dialogues_per_search"] = {"beam5": per_search(5), "greedy": per_search(1)}
 
         def timed(style, buckets, subset=None, sampling=None):
             d = data if subset is None else dict(data, dialogs=data["dialogs"][:subset],
