@@ -583,6 +583,37 @@ typedef struct {
     int* log_parent; int* log_tok; double* log_score; double* log_done; int* log_n_old; int* log_n_new;
 } mtn_beam_args;
 int mtn_beam_advance(const mtn_beam_args* args /* host */, void* stream);
+/* Diverse (group) beam search, Hamming diversity (version 119; Vijayakumar et al. 2016): one step of the hypothesis bookkeeping where the
+ * beam of B hypotheses of a dialogue is split into G groups of B' = B / G.  It extends mtn_beam_advance above (data_utils.py:209-240) and
+ * stands in its place in a captured search, one launch per token (csrc/diverse.hip).
+ *   Row layout    group g of dialogue d owns rows d*B + g*B' .. + B'-1 of the session (the session width stays B); every group starts from
+ *                 one <sos> hypothesis in its first row.
+ *   Group order   at a step the groups of a dialogue are processed in order g = 0 .. G-1.
+ *   Counts        c_g[v] = number of hypotheses in the FINAL new beams of groups 0 .. g-1 at this step whose newest token is v, counted
+ *                 with multiplicity; a candidate that entered a beam and was replaced later in the same walk does not count.
+ *   Penalised row group g reads, for each of its live hypotheses, r'[v] = fl32(r[v] - fl32(fl32(lambda) * (float)c_g[v])): one fp32
+ *                 multiply and one fp32 subtract, never contracted into an fma.  r is the row after mtn_constrain_rows, if one runs.
+ *   Group step    exactly mtn_beam_advance's step on the group's own hypotheses with beam B': candidates in descending r', <unk> / <eos>
+ *                 never extend a hypothesis, the worst member replaced while a candidate beats it, double sums rounded to float32.
+ *   Finished      log_done uses r[<eos>]: <eos> is never an extension, so its count is always 0.
+ *   Scores        accumulate the penalised values (as under a repetition penalty); rows are not renormalised.
+ *   Ties          two equal values among the k_top entries of a live row's head, before the penalty or after it, raise flags[0]: the
+ *                 visiting order is then the reference's argsort of the full PENALISED row (re-run that search on the host path).
+ * Why the head suffices: group g penalises at most B - B' tokens, so at least B' + 2 of the B + 2 largest entries of r keep their value, and
+ * everything outside the head is <= them before and after the penalty: the B' winners and the two skipped symbols of a row lie inside the
+ * head mtn_topk_rows delivers for a plain search at the same beam.  The kernel penalises the k_top head entries, re-sorts them (stable,
+ * descending) and walks the first k of them (k = B' + 2).
+ * beam.dialogues = D * G pseudo-dialogues, beam.width = beam.beam = B': state and step log are written in mtn_beam_advance's layout for
+ * D * G dialogues of width B' (n_live / step / log_n_* one entry per group, log parents relative to the group's first row), so a host
+ * rebuild and mtn_constrain_rows' step-log walk (width = rows_per_step = B') read them as they are.  One workgroup per REAL dialogue walks
+ * its groups in order; parents never cross groups; *pos is written once.  groups = 1 is mtn_beam_advance, bit for bit.
+ * MTN_ERR_ARG (nothing is launched): a null buffer, groups < 1, dialogues no multiple of groups, width * groups > 16,
+ * k_top < width * groups + 3 (B + 2 entries and the tie sentinel) or > 16, k outside [1, k_top], diversity negative or not finite. */
+typedef struct {
+    mtn_beam_args beam;
+    int groups; float diversity;
+} mtn_diverse_args;
+int mtn_diverse_advance(const mtn_diverse_args* args /* host */, void* stream);
 /* Sampling decode (version 115): one drawn token per row of logp [rows, V] (fp32 log-probabilities, row stride ldx; ldx = 0: every row
  * reads the same distribution; V < 2^24), one workgroup per row.  With l = step[row], the row's position:
  *   1. ban     the n_banned <= 4 ids in banned[], and eos while l < min_len, get probability 0;

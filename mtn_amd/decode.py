@@ -262,7 +262,9 @@ class DecodeSession:
             host_tok[d * W:d * W + len(prefixes), :l] = torch.tensor(prefixes, dtype=torch.long)
             if l > 1:
                 prev = self._prev[d]
-                for i, p in enumerate(prefixes):                    # the hypothesis this one extends (same tokens but the last)
+                # the hypothesis this one extends (same tokens but the last).  Two groups of a diverse search may hold the same prefix: the
+                # lookup finds the first of them, whose cache rows hold the same values
+                for i, p in enumerate(prefixes):
                     parent[d * W + i] = d * W + prev.index(list(p[:-1]))
         self._prev = [[list(p) for p in prefixes] for prefixes in prefix_lists]
         self.tokens.copy_(host_tok)
@@ -563,12 +565,28 @@ class MegaDecodeSession(DecodeSession):
         torch.cuda.current_stream().synchronize()
         return self._top_host.numpy()
 
-    def search(self, beam, k, start, unk, eos, penalty, min_len, nbest, no_repeat_ngram=0, repetition_penalty=1.0):
-        log = self._search_log(beam, k, start, unk, eos, penalty, min_len, eos, no_repeat_ngram, repetition_penalty)
+    def search(self, beam, k, start, unk, eos, penalty, min_len, nbest, no_repeat_ngram=0, repetition_penalty=1.0, beam_groups=1,
+               diversity_penalty=0.0):
+        G = int(beam_groups)
+        log = self._search_log(beam, k, start, unk, eos, penalty, min_len, eos, no_repeat_ngram, repetition_penalty, G, float(diversity_penalty))
         if log is None:
             return None
         par, tok, n_old, n_new, score, done_sc, flags = log
         results = []
+        if G > 1:
+            # diverse beam search: the log holds D x G pseudo-dialogues of width beam / G (group g of dialogue d owns rows d * width + g * Bp ..);
+            # a dialogue's finished hypotheses are pooled in the order the stepped path appends them: step, group, hypothesis
+            Bp = self.width // G
+            for d_ in range(self.D):
+                outs, done = [[[]] for _ in range(G)], []
+                for l in range(self.max_len):
+                    for g in range(G):
+                        p, base = d_ * G + g, d_ * self.width + g * Bp
+                        if l >= min_len:
+                            done += [(outs[g][h], float(done_sc[l, base + h])) for h in range(int(n_old[l, p]))]
+                        outs[g] = [outs[g][int(par[l, base + i])] + [int(tok[l, base + i])] for i in range(int(n_new[l, p]))]
+                results.append(_pool_groups(done, nbest))
+            return results
         for d_ in range(self.D):
             base = d_ * self.width
             outs, done = [[]], []
@@ -592,13 +610,17 @@ class MegaDecodeSession(DecodeSession):
             return None
         return [[int(t) for t in log[1][:self.max_len - 1, d_ * self.width]] for d_ in range(self.D)]
 
-    def _search_log(self, beam, k, start, unk, eos, penalty, min_len, extra_col, no_repeat_ngram=0, repetition_penalty=1.0):
+    def _search_log(self, beam, k, start, unk, eos, penalty, min_len, extra_col, no_repeat_ngram=0, repetition_penalty=1.0, groups=1, diversity=0.0):
         """A whole beam search (data_utils.py:188-242) for every dialogue of the session as ONE graph replay: max_len x [persistent decode
         step, generator, row heads (csrc/select.hip topk_rows), hypothesis bookkeeping on the device (mtn_beam_advance)], the step log
         copied to a pinned block at the end.  The host synchronises once per search and rebuilds the n-best lists from the log.
         With a constraint on (no_repeat_ngram > 0 or repetition_penalty != 1; csrc/constrain.hip), one more launch per token sits between
         the generator and the row heads: it rewrites the rows in place from each hypothesis' history, which it walks out of this very step
         log (the parents and tokens of the steps before, the dialogue's step counter) — all device memory, so one graph serves every search.
+        With ``groups`` = G > 1 (diverse beam search, csrc/diverse.hip) the bookkeeping launch is mtn_diverse_advance, one for one: the state
+        and the log are those of D x G pseudo-dialogues of width beam / G — every group starts from <sos> in its own first row — and the row
+        heads are the plain search's (beam + 2 entries and the tie sentinel: include/mtn_hip.h says why they suffice).  (G, lambda) are part
+        of the search key; with one group nothing here differs from the plain search.
         Returns None when a row's head held an exact tie (the reference's visiting order then comes from the full row: the caller runs the
         search step by step) or when the device-side selection does not apply."""
         import ctypes as C
@@ -607,10 +629,16 @@ class MegaDecodeSession(DecodeSession):
         k_top = k + 1
         if self.select is None or self.select[0] != k_top or self.select[1] != extra_col or beam > self.width or k_top > SELECT_MAX_K or not self.use_graph:
             return None
-        W, D, Lm = self._W, self.D, self.max_len
+        G = int(groups)
+        if G > 1 and (beam != self.width or beam % G):
+            return None
+        # the bookkeeping's dialogues: D, or D x G groups of Wd = width / G rows each
+        W, D, Lm, Wd = self._W, self.D * G, self.max_len, self.width // G
         ngram, theta = int(no_repeat_ngram), float(repetition_penalty)
         constrained = ngram > 0 or theta != 1.0
         key = (beam, k, start, unk, eos, float(penalty), min_len, ngram, theta)
+        if G > 1:
+            key += (G, float(diversity))
         if getattr(self, "_search_key", None) != key:
             dev = self._x.device
             # device state of the search [lp (W doubles) | n_live (D) | step (D) | flags (2)] and its initial image
@@ -622,7 +650,7 @@ class MegaDecodeSession(DecodeSession):
             blk = np.zeros(self._host.numel(), dtype=np.uint8)               # [tokens | pos | anc] before the first step: <sos> in every dialogue's row 0
             tok = blk[:8 * W].view(np.int64)
             tok[:] = self.pad
-            tok[::self.width] = start
+            tok[::Wd] = start
             blk[self._off_anc:].view(np.int32).reshape(W, Lm)[:] = np.arange(W, dtype=np.int32)[:, None]
             self._blk_init = torch.from_numpy(blk).pin_memory()
             # the step log: [parent | tok (int32 L x W each) | n_old | n_new (int32 L x D each) | score | done (double L x W each) | flags (2 x int32)]
@@ -638,8 +666,12 @@ class MegaDecodeSession(DecodeSession):
                                hb[o_nold:o_nnew].view(np.int32).reshape(Lm, D), hb[o_nnew:o_nnew + 4 * Lm * D].view(np.int32).reshape(Lm, D),
                                hb[o_sc:o_done].view(np.float64).reshape(Lm, W), hb[o_done:o_flags].view(np.float64).reshape(Lm, W),
                                hb[o_flags:o_flags + 8].view(np.int32))
-            a = L.BeamArgs()
-            a.dialogues, a.width, a.L, a.k_top, a.k, a.beam, a.unk, a.eos, a.pad, a.min_len = D, self.width, Lm, k_top, k, beam, unk, eos, self.pad, min_len
+            da = L.DiverseArgs()                     # (one group: the plain arguments alone, and mtn_beam_advance)
+            a = da.beam if G > 1 else L.BeamArgs()
+            da.groups, da.diversity = G, float(diversity)
+            a.dialogues, a.width, a.L, a.k_top, a.k, a.beam, a.unk, a.eos, a.pad, a.min_len = D, Wd, Lm, k_top, k, beam, unk, eos, self.pad, min_len
+            if G > 1:
+                a.beam, a.k = Wd, Wd + 2             # a group places at most Wd candidates per row and skips at most two
             a.penalty = float(penalty)
             p0, s0, l0 = self._devblk.data_ptr(), self._bstate.data_ptr(), self._log.data_ptr()
             a.tokens, a.pos, a.anc = p0, p0 + self._off_pos, p0 + self._off_anc
@@ -654,11 +686,14 @@ class MegaDecodeSession(DecodeSession):
                 for _ in range(Lm):
                     logp = self._step_rows()
                     if constrained:
-                        ops.constrain_rows(logp, ngram, theta, log_tok=a.log_tok, log_parent=a.log_parent, step=a.step, width=self.width,
-                                           rows_per_step=self.width, log_len=Lm)
+                        ops.constrain_rows(logp, ngram, theta, log_tok=a.log_tok, log_parent=a.log_parent, step=a.step, width=Wd,
+                                           rows_per_step=Wd, log_len=Lm)
                     top = ops.topk_rows(logp, k_top, extra_col)
                     a.top = top.data_ptr()
-                    L.check(L.load().mtn_beam_advance(C.byref(a), L.stream_ptr()))
+                    if G > 1:
+                        L.check(L.load().mtn_diverse_advance(C.byref(da), L.stream_ptr()))
+                    else:
+                        L.check(L.load().mtn_beam_advance(C.byref(a), L.stream_ptr()))
                 self._log_host.copy_(self._log, non_blocking=True)
 
             with torch.no_grad():
@@ -1064,22 +1099,31 @@ class _Beam:
 
 
 def beam_search_decode_many(model, batch, max_len, start_symbol, unk_symbol, end_symbol, pad_symbol, beam=5, penalty=1.0,
-                            nbest=5, min_len=1, use_graph=True, kv_cache=None, no_repeat_ngram=0, repetition_penalty=1.0):
+                            nbest=5, min_len=1, use_graph=True, kv_cache=None, no_repeat_ngram=0, repetition_penalty=1.0,
+                            beam_groups=1, diversity_penalty=0.0):
     """beam_search_decode for a Batch of D dialogues at once: the D x beam live hypotheses are the batch dimension of ONE
     target-stream pass per generated token (the pass is launch-latency-bound, so D dialogues cost little more than one).
     Returns a list of D (n-best list, best score) pairs, each equal to what the single-dialogue search returns.
     ``no_repeat_ngram`` = N > 0: no hypothesis repeats an N-gram (the token that would complete one gets -inf); ``repetition_penalty`` =
     theta > 1: the log-probability of every token a hypothesis already holds is multiplied by theta (include/mtn_hip.h mtn_constrain_rows).
     Both act on the rows before candidates are selected, on every path; rows are not renormalised, so scores under a penalty are the
-    penalised ones.  Off (0, 1.0), the search is exactly the unconstrained one."""
+    penalised ones.  Off (0, 1.0), the search is exactly the unconstrained one.
+    ``beam_groups`` = G > 1: diverse (group) beam search with Hamming diversity (Vijayakumar et al. 2016; include/mtn_hip.h
+    mtn_diverse_advance holds the definition).  The beam is split into G groups of beam / G hypotheses, each a beam search of its own that
+    starts from <sos>; at every step the groups go in order, and group g reads its rows lowered by ``diversity_penalty`` = lambda >= 0
+    times the number of hypotheses the groups before it have just extended with that token.  Scores accumulate the penalised values and
+    rows are not renormalised.  A dialogue's result pools the finished hypotheses of all groups: identical token lists once (the highest
+    score), sorted by score, the first ``nbest``.  G must divide beam; lambda > 0 needs G > 1.  G = 1 is the plain search, launch for launch."""
     ngram, theta, _ = _constraints(no_repeat_ngram, repetition_penalty)
+    G, lam = _diverse(beam, beam_groups, diversity_penalty)
     auto = kv_cache is None          # the caller leaves the pass to us: one persistent launch per token where it applies (<= 16 hypotheses, bf16)
     if kv_cache is None:
         kv_cache = max_len > KV_CACHE_FROM
     args = (model, batch, max_len, start_symbol, unk_symbol, end_symbol, pad_symbol, beam, penalty, nbest, min_len, use_graph, kv_cache)
-    res = _beam_search_many(*args, mega=auto, ngram=ngram, theta=theta)
+    kw = dict(ngram=ngram, theta=theta, groups=G, lam=lam) if G > 1 else dict(ngram=ngram, theta=theta)
+    res = _beam_search_many(*args, mega=auto, **kw)
     if res is None:                  # a poll of the persistent step timed out (compute units held by another kernel): the launch-per-sublayer pass
-        res = _beam_search_many(*args, mega=False, ngram=ngram, theta=theta)
+        res = _beam_search_many(*args, mega=False, **kw)
     return res
 
 
@@ -1095,7 +1139,7 @@ def _mega_failed(sess) -> bool:
 
 
 def _beam_search_many(model, batch, max_len, start_symbol, unk_symbol, end_symbol, pad_symbol, beam, penalty, nbest, min_len, use_graph, kv_cache, mega,
-                      ngram=0, theta=1.0):
+                      ngram=0, theta=1.0, groups=1, lam=0.0):
     auto = mega
     constrained = ngram > 0 or theta != 1.0
     k = beam + 2
@@ -1106,28 +1150,34 @@ def _beam_search_many(model, batch, max_len, start_symbol, unk_symbol, end_symbo
     mega = isinstance(sess, MegaDecodeSession)
     if mega and sel is not None:
         # the whole search as one graph replay, hypothesis bookkeeping on the device; None = a tie somewhere: step by step below
-        res = sess.search(beam, k, start_symbol, unk_symbol, end_symbol, penalty, min_len, nbest, ngram, theta)
+        res = sess.search(beam, k, start_symbol, unk_symbol, end_symbol, penalty, min_len, nbest, ngram, theta,
+                          **(dict(beam_groups=groups, diversity_penalty=lam) if groups > 1 else {}))
         if _mega_failed(sess):
             return None
         if res is not None:
             return res
-    beams = [_Beam(start_symbol, unk_symbol, end_symbol, beam, penalty, min_len) for _ in range(sess.D)]
+    # diverse beam search (groups > 1): `groups` beams of beam / groups per dialogue, advanced in group order; beams[] lists them dialogue
+    # by dialogue, group by group — with one group it is the list of the dialogues' beams
+    G, Bp = groups, beam // groups
+    beams = [_Beam(start_symbol, unk_symbol, end_symbol, Bp, penalty, min_len) for _ in range(sess.D * G)]
     for l in range(max_len):
         if mega:
             # the persistent step takes (row, newest token, parent row) of every live hypothesis: no prefix lists are built or searched
-            Wd = sess.width
-            live = [d * Wd + i for d, bm in enumerate(beams) for i in range(len(bm.hyps))]
+            # (group g of dialogue d owns rows d * width + g * beam / groups ..: the beams' rows are Bp apart)
+            live = [j * Bp + i for j, bm in enumerate(beams) for i in range(len(bm.hyps))]
             sess.step_extend(l + 1, live, [h[2][-1] for bm in beams for h in bm.hyps],
-                             [d * Wd + p for d, bm in enumerate(beams) for p in bm.parents])
-            counts = [len(bm.hyps) for bm in beams]
+                             [j * Bp + p for j, bm in enumerate(beams) for p in bm.parents])
         else:
-            counts = [lp.size(0) for lp in sess.step_many([bm.prefixes() for bm in beams])]
-            live = [r for d, n in enumerate(counts) for r in range(d * sess.width, d * sess.width + n)]
+            # the launch passes take a dialogue's live prefixes packed, group after group (two groups may hold the same prefix: the prefix
+            # cache's parent lookup then finds the first of them, whose cache rows hold the same values)
+            packed_n = [lp.size(0) for lp in sess.step_many([[p for bm in beams[d * G:d * G + G] for p in bm.prefixes()] for d in range(sess.D)])]
+            live = [r for d, n in enumerate(packed_n) for r in range(d * sess.width, d * sess.width + n)]
+        counts = [len(bm.hyps) for bm in beams]
         top = sess.top
         if constrained:
             # the rows are rewritten in place before anything is selected from them: the pass selected nothing (_pass_select), except on
             # the persistent step, whose heads are of the unconstrained rows and are not read
-            _constrain_step(sess, [(d * sess.width + i, h[0]) for d, bm in enumerate(beams) for i, h in enumerate(bm.hyps)], ngram, theta)
+            _constrain_step(sess, list(zip(live, [h[0] for bm in beams for h in bm.hyps])), ngram, theta)
             top = ops.topk_rows(sess.logp, min(k + 1, sess.logp.size(1)), end_symbol) if sel is not None else None
         if top is not None:
             # device-side selection inside the pass (csrc/select.hip): only the heads of the rows travel, in one copy
@@ -1144,6 +1194,10 @@ def _beam_search_many(model, batch, max_len, start_symbol, unk_symbol, end_symbo
         # exact ties inside a row's head would make the visiting order depend on the selection algorithm: the reference's
         # order (argsort, data_utils.py:219) is then taken from the full row
         tie = bool((vals[:, 1:] == vals[:, :-1]).any())
+        if G > 1:
+            rows = lambda: (allp if allp is not None else sess.logp[live]).float().cpu().numpy()
+            _diverse_advance(beams, G, l, lam, vals, idx, eos, Bp + 2, rows, tie)
+            continue
         host = (allp if allp is not None else sess.logp[live]).double().cpu().numpy() if tie else None
         o = 0
         for bm, n in zip(beams, counts):
@@ -1154,19 +1208,94 @@ def _beam_search_many(model, batch, max_len, start_symbol, unk_symbol, end_symbo
             o += n
     if mega and _mega_failed(sess):
         return None
+    if G > 1:
+        # a group's finished hypotheses carry their step (the length): pooled by step, then group, then hypothesis (sorted() is stable)
+        return [_pool_groups(sorted((h for bm in beams[d * G:d * G + G] for h in bm.done), key=lambda h: len(h[0])), nbest) for d in range(sess.D)]
     return [bm.result(nbest) for bm in beams]
 
 
+def _diverse(beam, beam_groups, diversity_penalty):
+    """(G, lambda) of a beam search's diversity keywords, checked."""
+    import math
+    G, lam = int(beam_groups), float(diversity_penalty)
+    if G != beam_groups or G < 1 or int(beam) % G:
+        raise ValueError("beam_groups is an integer >= 1 that divides beam")
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError("diversity_penalty is finite and >= 0")
+    if lam > 0.0 and G == 1:
+        raise ValueError("diversity_penalty > 0 needs beam_groups > 1 (one group is the plain beam search)")
+    return G, lam
+
+
+def _pool_groups(done, nbest):
+    """The result of a diverse search for one dialogue: ``done`` = the finished hypotheses of all its groups in the order step, group,
+    hypothesis.  Identical token lists are kept once (the highest score; on equal scores the first), the pool is sorted by score (stable)."""
+    at = {}
+    for i, (toks, s) in enumerate(done):
+        j = at.get(tuple(toks))
+        if j is None or done[j][1] < s:
+            at[tuple(toks)] = i
+    kept = [done[i] for i in sorted(at.values())]
+    if not kept:
+        return [([], 0)], None
+    return sorted(kept, key=lambda h: -h[1])[:nbest], max(h[1] for h in kept)
+
+
+def _diverse_advance(beams, G, l, lam, vals, idx, eos, k, rows, tie):
+    """One step of the G groups of every dialogue (include/mtn_hip.h mtn_diverse_advance), on the host: group g's rows are lowered by
+    fl32(lambda * count) for the newest tokens of the final new beams of the groups before it, in float32 as the kernel does it.  vals / idx
+    / eos: the live rows' heads in the beams' order; they are penalised, re-sorted (stable, descending) and their first k entries walked.
+    A tie inside a head, before the penalty (``tie``) or after it, sends the WHOLE step down the full-row path (``rows()``: the live rows,
+    fp32): the groups are put back as they were and advanced again on the penalised full rows, whose argsort is the reference's order."""
+    import numpy as np
+    f32 = np.float32
+
+    def run(full):
+        o = 0
+        for j, bm in enumerate(beams):
+            if j % G == 0:
+                chosen = {}
+            n = len(bm.hyps)
+            if full is not None:
+                r = full[o:o + n].copy()
+                for t, c in chosen.items():
+                    r[:, t] = r[:, t] - f32(lam) * f32(c)
+                bm.advance(r.astype("float64"), l)
+            else:
+                v, ix = vals[o:o + n].astype(f32), idx[o:o + n]
+                c = np.array([[chosen.get(int(t), 0) for t in row] for row in ix], dtype=f32).reshape(ix.shape)
+                pv = (v - (f32(lam) * c).astype(f32)).astype(f32)
+                order = np.argsort(-pv.astype("float64"), axis=1, kind="stable")
+                pv, ix = np.take_along_axis(pv, order, 1), np.take_along_axis(ix, order, 1)
+                if (pv[:, 1:] == pv[:, :-1]).any():
+                    return False
+                bm.advance(None, l, top=(pv[:, :k].astype("float64"), ix[:, :k], eos[o:o + n]))
+            o += n
+            for h in bm.hyps:
+                chosen[h[2][-1]] = chosen.get(h[2][-1], 0) + 1
+        return True
+
+    if not tie:
+        saved = [(bm.hyps, bm.parents, bm.best, len(bm.done)) for bm in beams]
+        if run(None):
+            return
+        for bm, (hyps, parents, best, n_done) in zip(beams, saved):
+            bm.hyps, bm.parents, bm.best = hyps, parents, best
+            del bm.done[n_done:]
+    run(rows())
+
+
 def beam_search_decode(model, batch, max_len, start_symbol, unk_symbol, end_symbol, pad_symbol, beam=5, penalty=1.0,
-                       nbest=5, min_len=1, use_graph=True, kv_cache=None, no_repeat_ngram=0, repetition_penalty=1.0):
+                       nbest=5, min_len=1, use_graph=True, kv_cache=None, no_repeat_ngram=0, repetition_penalty=1.0,
+                       beam_groups=1, diversity_penalty=0.0):
     """data_utils.py:188-242, same arguments and return value: (n-best list of (token list, score) sorted by score,
     best score).  A hypothesis ending with <eos> at length k scores logp + penalty * k; <unk> and <eos> never extend
     a hypothesis; candidates are visited in descending log-probability exactly as the reference does (data_utils.py:219).
-    no_repeat_ngram / repetition_penalty: as beam_search_decode_many (off by default)."""
+    no_repeat_ngram / repetition_penalty / beam_groups / diversity_penalty: as beam_search_decode_many (off by default)."""
     if batch.query.size(0) != 1:
         raise ValueError("beam_search_decode works on one dialogue (data_utils.py:188); use beam_search_decode_many for a batch")
     return beam_search_decode_many(model, batch, max_len, start_symbol, unk_symbol, end_symbol, pad_symbol, beam, penalty, nbest,
-                                   min_len, use_graph, kv_cache, no_repeat_ngram, repetition_penalty)[0]
+                                   min_len, use_graph, kv_cache, no_repeat_ngram, repetition_penalty, beam_groups, diversity_penalty)[0]
 
 
 def greedy_decode(model, batch, max_len, start_symbol, pad_symbol=1, use_graph=True, kv_cache=None, no_repeat_ngram=0, repetition_penalty=1.0):

@@ -79,6 +79,10 @@ def parse(argv=None):
     p.add_argument("--repetition-penalty", default=1.0, type=float,
                    help="multiply the log-probability of every token a response already holds by this (>= 1; 1 = off)")
     p.add_argument("--min-length", default=1, type=int, help="beam_search / sample: no response ends before this many tokens")
+    # diverse beam search (beam_search only): the beam as --beam-groups groups that are penalised for repeating each other's newest token
+    p.add_argument("--beam-groups", default=1, type=int, help="beam_search: split the beam into this many groups (divides --beam; 1 = plain beam search)")
+    p.add_argument("--diversity-penalty", default=0.0, type=float,
+                   help="beam_search: what a group's log-probability of a token loses per hypothesis of an earlier group that just took it (>= 0; needs --beam-groups > 1)")
     # ensemble decoding: further checkpoints combined with --model on the device, per generated token (decode.Ensemble)
     p.add_argument("--ensemble-model", default=[], nargs="+", type=str, help="further checkpoints (PREFIX.pth.tar each), decoded together with --model")
     p.add_argument("--ensemble-conf", default=[], nargs="+", type=str,
@@ -107,6 +111,19 @@ def parse(argv=None):
         p.error("--no-repeat-ngram / --repetition-penalty constrain a search: they do not go with --decode-style score")
     if args.min_length < 0:
         p.error("--min-length must be >= 0")
+    if args.beam_groups < 1:
+        p.error("--beam-groups must be >= 1")
+    if not (args.diversity_penalty >= 0 and args.diversity_penalty < float("inf")):
+        p.error("--diversity-penalty must be finite and >= 0")
+    if args.decode_style != "beam_search":
+        if args.beam_groups > 1:
+            p.error("--beam-groups goes with --decode-style beam_search")
+        if args.diversity_penalty > 0:
+            p.error("--diversity-penalty goes with --decode-style beam_search")
+    elif args.beam % args.beam_groups:
+        p.error("--beam-groups must divide --beam (%d groups for a beam of %d)" % (args.beam_groups, args.beam))
+    elif args.diversity_penalty > 0 and args.beam_groups == 1:
+        p.error("--diversity-penalty needs --beam-groups > 1 (one group is the plain beam search)")
     n_members = 1 + len(args.ensemble_model)
     if args.ensemble_conf and len(args.ensemble_conf) != len(args.ensemble_model):
         p.error("--ensemble-conf takes one conf per --ensemble-model entry (%d given for %d)" % (len(args.ensemble_conf), len(args.ensemble_model)))
@@ -366,12 +383,13 @@ def candidate_order(scores):
 
 # ---------------------------------------------------------------------------------------------------------------- decoding
 def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=None, scoring=None,
-                    no_repeat_ngram=0, repetition_penalty=1.0, min_len=1):
+                    no_repeat_ngram=0, repetition_penalty=1.0, min_len=1, beam_groups=1, diversity_penalty=0.0):
     """Run the planned searches; returns per qa_id the (n-best list, best score) of beam search, the greedy token list, the
     samples' (tokens, score) pairs, best first (``sampling``: samples / temperature / top_k / top_p / seed), or the candidates'
     score dicts in input order (``scoring``: tokens = per qa_id its candidates' token lists, max_len, width — one session shape
     per bucket).  ``no_repeat_ngram`` / ``repetition_penalty`` constrain beam search, greedy and sample (decode.py; off by default);
-    ``min_len``: the shortest response beam search and sample may finish."""
+    ``min_len``: the shortest response beam search and sample may finish.  ``beam_groups`` / ``diversity_penalty``: diverse beam search
+    (beam search only; decode.beam_search_decode_many)."""
     from . import decode
     from .data_handler import make_batch
     from .decode import beam_search_decode_many, greedy_decode_many
@@ -387,7 +405,7 @@ def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, 
         batch_shape = key
         if decode_style == "beam_search":
             res = beam_search_decode_many(model, batch, maxlen, sos, unk, eos, pad, beam=beam, penalty=penalty, nbest=nbest, min_len=min_len,
-                                          **con)
+                                          beam_groups=int(beam_groups), diversity_penalty=float(diversity_penalty), **con)
         elif decode_style == "sample":
             # keys = qa_ids: a QA's random stream is the same in any bucket, at any D, with --no-buckets
             res = decode.sample_decode_many(model, batch, maxlen, sos, eos, pad, keys=ids, banned=(unk, pad, sos), min_len=min_len, penalty=penalty,
@@ -405,15 +423,22 @@ def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, 
 
 def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0, nbest=5, decode_style="greedy", undisclosed_only=False,
                       ref_data=None, dialogues_per_search=0, buckets=True, sampling=None, candidates=None, no_repeat_ngram=0,
-                      repetition_penalty=1.0, min_len=1):
+                      repetition_penalty=1.0, min_len=1, beam_groups=1, diversity_penalty=0.0):
     """Decode every QA of ``data`` (data_handler.load) and return the reference's result dict, logging the reference's
     QS / REF / HYP lines per QA.  decode_style "score" generates nothing: every QA's ``candidates`` (load_candidates' ``spec``; its
     own answer without one) are scored and logged as CAND lines, best first; the answer is the best-scoring candidate, every turn
     gains "scores" in input order, and the corpus perplexity and ranking metrics (score_metrics) are logged at the end.  Candidates
     are scored whole: ``maxlen`` does not cut them.  ``no_repeat_ngram`` / ``repetition_penalty`` / ``min_len``: as decode_searches
-    (a scoring run takes no constraints: ValueError)."""
+    (a scoring run takes no constraints: ValueError).  ``beam_groups`` / ``diversity_penalty``: diverse beam search, for decode_style
+    "beam_search" alone (any other style with groups > 1 or a penalty > 0: ValueError); the n-best lines and the result are as for the
+    plain beam search, and so is the number of dialogues per search."""
     if decode_style == "score" and (no_repeat_ngram != 0 or repetition_penalty != 1.0):
         raise ValueError("generate_response: no_repeat_ngram / repetition_penalty constrain a search; a scoring run has none")
+    if decode_style == "beam_search":
+        from .decode import _diverse
+        _diverse(beam, beam_groups, diversity_penalty)
+    elif beam_groups != 1 or diversity_penalty != 0:
+        raise ValueError("generate_response: beam_groups / diversity_penalty go with decode_style beam_search")
     vocablist = sorted(vocab.keys(), key=lambda s: vocab[s])
     eos = vocab["<eos>"]
     lens = qa_lengths(data)
@@ -438,7 +463,8 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
     logging.info("%d QAs in %d searches over %d padded shapes", len(lens), len(searches), n_buckets)
     vids = {it[1]: it[0] for it in data["dialogs"]}
     res = decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=sampling,
-                          scoring=scoring, no_repeat_ngram=no_repeat_ngram, repetition_penalty=repetition_penalty, min_len=min_len)
+                          scoring=scoring, no_repeat_ngram=no_repeat_ngram, repetition_penalty=repetition_penalty, min_len=min_len,
+                          beam_groups=beam_groups, diversity_penalty=diversity_penalty)
     answers = []
     scores = [] if decode_style == "score" else None
     qa_id = 0
@@ -546,7 +572,8 @@ def main(argv=None):
                                dialogues_per_search=args.dialogues_per_search, buckets=not args.no_buckets,
                                sampling=dict(samples=args.samples, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                                              seed=args.sample_seed), candidates=args.candidates,
-                               no_repeat_ngram=args.no_repeat_ngram, repetition_penalty=args.repetition_penalty, min_len=args.min_length)
+                               no_repeat_ngram=args.no_repeat_ngram, repetition_penalty=args.repetition_penalty, min_len=args.min_length,
+                               beam_groups=args.beam_groups, diversity_penalty=args.diversity_penalty)
     wall = time.time() - start_time
     n_qa = len(test_data["dialogs"])
     logging.info("----------------")

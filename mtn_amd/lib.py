@@ -155,6 +155,10 @@ class BeamArgs(C.Structure):
                 ("log_n_new", C.c_void_p)]
 
 
+class DiverseArgs(C.Structure):
+    _fields_ = [("beam", BeamArgs), ("groups", C.c_int), ("diversity", C.c_float)]
+
+
 class SampleArgs(C.Structure):
     _fields_ = [("rows", C.c_int), ("V", C.c_int), ("ldx", C.c_long), ("logp", C.c_void_p), ("temperature", C.c_float), ("top_k", C.c_int),
                 ("top_p", C.c_float), ("n_banned", C.c_int), ("banned", C.c_int * 4), ("eos", C.c_int), ("min_len", C.c_int),
@@ -225,6 +229,7 @@ SYMBOLS = {
     "mtn_gemm_tt_table": (C.c_int, [C.c_int, C.c_int, C.POINTER(GemmProblem), _P]),
     "mtn_decode_step": (C.c_int, [C.POINTER(DecodeArgs), _P, C.c_int, _P]),
     "mtn_beam_advance": (C.c_int, [C.POINTER(BeamArgs), _P]),
+    "mtn_diverse_advance": (C.c_int, [C.POINTER(DiverseArgs), _P]),
     "mtn_sample_rows": (C.c_int, [C.POINTER(SampleArgs), _P]),
     "mtn_score_rows": (C.c_int, [C.POINTER(ScoreArgs), _P]),
     "mtn_constrain_rows": (C.c_int, [C.POINTER(ConstrainArgs), _P]),

@@ -7,6 +7,8 @@ captures graphs per QA shape), greedy, and --decode-style sample (1 and 4 sample
 --styles picks a subset (beam, greedy, no_buckets, sample).  --no-repeat-ngram / --repetition-penalty constrain every search of the run
 (generate.py's flags of the same names; off by default).  --ensemble M decodes with M random-init copies of the model (seeds 1..M)
 combined on the device (decode.Ensemble; --ensemble-mode prob|logprob) and records the dialogues per search auto_dialogues chose.
+--beam sets the beam of the beam-search settings (default 5; their keys carry it), --beam-groups / --diversity-penalty make them diverse
+beam searches (generate.py's flags of the same names; greedy and sample are not touched).
 
     python tools/generate_bench.py [--dialogs 1710] [--no-buckets-qas 300]
 """
@@ -52,6 +54,9 @@ def main():
     ap.add_argument("--styles", default="beam,greedy,no_buckets,sample", help="comma-separated: beam, greedy, no_buckets, sample")
     ap.add_argument("--no-repeat-ngram", type=int, default=0)
     ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--beam", type=int, default=5)
+    ap.add_argument("--beam-groups", type=int, default=1)
+    ap.add_argument("--diversity-penalty", type=float, default=0.0)
     ap.add_argument("--ensemble", type=int, default=1, help="members: this many random-init copies with different seeds (1 = a plain model)")
     ap.add_argument("--ensemble-mode", default="prob", choices=["prob", "logprob"])
     a = ap.parse_args()
@@ -88,27 +93,29 @@ def main():
         corpus = dh.DeviceCorpus(data, dev)
         lens = G.qa_lengths(data)
         n = len(lens)
-        out = {"qas": n, "buckets": len({G.bucket_key(l) for l in lens}), "maxlen": a.maxlen, "beam": 5,
+        out = {"qas": n, "buckets": len({G.bucket_key(l) for l in lens}), "maxlen": a.maxlen, "beam": a.beam,
+               "beam_groups": a.beam_groups, "diversity_penalty": a.diversity_penalty,
                "no_repeat_ngram": a.no_repeat_ngram, "repetition_penalty": a.repetition_penalty, "ensemble": a.ensemble, "ensemble_mode": a.ensemble_mode if a.ensemble > 1 else None}
         per_search = lambda width: sorted({len(ids) for ids, _, _ in G.plan_searches(
             lens, lambda shape: G.auto_dialogues(model, dev, shape, a.maxlen, width))})
-        out["dialogues_per_search"] = {"beam5": per_search(5), "greedy": per_search(1)}
+        out["dialogues_per_search"] = {"beam%d" % a.beam: per_search(a.beam), "greedy": per_search(1)}
 
         def timed(style, buckets, subset=None, sampling=None):
             d = data if subset is None else dict(data, dialogs=data["dialogs"][:subset],
                                                  original={"dialogs": data["original"]["dialogs"][:subset]})
             torch.cuda.synchronize()
             t0 = time.time()
-            G.generate_response(model, d, corpus, vocab, maxlen=a.maxlen, beam=5, penalty=1.0, nbest=5, decode_style=style,
+            div = dict(beam_groups=a.beam_groups, diversity_penalty=a.diversity_penalty) if style == "beam_search" else {}
+            G.generate_response(model, d, corpus, vocab, maxlen=a.maxlen, beam=a.beam, penalty=1.0, nbest=5, decode_style=style,
                                 undisclosed_only=True, buckets=buckets, sampling=sampling, no_repeat_ngram=a.no_repeat_ngram,
-                                repetition_penalty=a.repetition_penalty)
+                                repetition_penalty=a.repetition_penalty, **div)
             torch.cuda.synchronize()
             dt = time.time() - t0
             return {"qas": len(d["dialogs"]), "seconds": round(dt, 2), "qa_per_s": round(len(d["dialogs"]) / dt, 1)}
 
         styles = set(a.styles.split(","))
         if "beam" in styles:
-            out["beam5_buckets_auto_d"] = timed("beam_search", True)
+            out["beam%d_buckets_auto_d" % a.beam] = timed("beam_search", True)
         if "greedy" in styles:
             out["greedy_buckets_auto_d"] = timed("greedy", True)
         if "sample" in styles:
@@ -122,7 +129,7 @@ def main():
             out["sample4_buckets_auto_d"] = timed("sample", True, sampling=dict(smp, samples=4))
             out["sample_over_greedy"] = round(out["sample1_buckets_auto_d"]["qa_per_s"] / out["greedy_buckets_auto_d_again"]["qa_per_s"], 3)
         if "no_buckets" in styles:
-            out["beam5_no_buckets"] = timed("beam_search", False, min(n, a.no_buckets_qas))
+            out["beam%d_no_buckets" % a.beam] = timed("beam_search", False, min(n, a.no_buckets_qas))
         from mtn_amd.decode import MegaDecodeSession
         out["persistent_step_fallbacks"] = MegaDecodeSession.FALLBACKS
     print(json.dumps(out))
