@@ -441,6 +441,23 @@ int mtn_fused_enable(int on);
 /* How many sublayer groups took which path since the library was loaded: out4 = {forward fused, forward per-stage, backward
  * fused (groups with attention members), backward per-stage}.  The parity tests use it to assert that the fused kernels ran. */
 int mtn_fused_counters(long* out4);
+/* K|V projections of CONSTANT memories for many sublayers (problems as for mtn_gemm: bf16, K = 512, bias epilogue into out_lp; any
+ * count).  The first n_now problems are computed now.  The others may WAIT (riders on, every grouped launch of the list would take
+ * the wide one-shot K = 512 kernel): they leave as rider workgroups of the fused forward launches of mtn_sublayer_group_fwd, on
+ * compute units those launches leave empty (csrc/gemm_k512.hip, csrc/fused.hip), in the order given — pass them in the order of
+ * their first use.  mtn_sublayer_group_fwd first launches stand-alone whatever is still pending of a K|V buffer its members read
+ * (and of everything in front of it), and mtn_riders_flush() launches all that is left: nothing is skipped, and a buffer's bits do not
+ * depend on which launch carried its tiles.  Operands and outputs must stay valid until then.  Otherwise — riders off, other
+ * shapes, batches whose launches take the persistent form — the call is the grouped mtn_gemm launches of the whole list, now.
+ * Environment (mtn_reload_env): MTN_RIDERS=0 riders off; MTN_RIDER_MAX_SLOTS=<n> at most n rider workgroups per launch;
+ * MTN_RIDER_FFN_HOSTS=0|1 launches with feed-forward members carry riders or not. */
+int mtn_kv_project(int dtype, int count, const mtn_gemm_problem* problems /* host array */, int n_now, void* stream);
+/* Launch stand-alone whatever is still pending.  Call it at the end of every forward that deferred work. */
+int mtn_riders_flush(void* stream);
+int mtn_riders_enabled(void);
+/* out4 = {K|V tiles computed by rider workgroups, tiles launched stand-alone from the pending list, such stand-alone launches,
+ * tiles pending now} since the library was loaded. */
+int mtn_rider_counters(long* out4);
 /* Backward groups (since the library was loaded) whose LayerNorm backward rode in the epilogue of the dLN-out GEMM (mtn_ln_epilogue)
  * instead of its own launch: the tests use it to assert which path ran. */
 long mtn_ln_epilogue_groups(void);

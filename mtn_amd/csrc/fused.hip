@@ -26,6 +26,7 @@
 // The workgroup of head 0 / slice 0 also writes xn, mean, rstd for backward.  Workgroup id % 8 = head and workgroups go to the
 // 8 XCDs round-robin: each XCD streams only its head's weight slice.
 #include "fused_common.h"
+#include "gemm_k512_tile.h"
 
 struct FhMember {
     int kind;
@@ -72,7 +73,13 @@ struct FhGroup {
 #endif
     int wg_start[FH_MAX_MEMBERS + 1];
     FhMember m[FH_MAX_MEMBERS];
+    // RIDER workgroups (block ids rider_base + r, behind the members'): work of LATER launches that is off the critical path now — K|V tiles of
+    // constant memories for the next layers (gemm_k512.hip: pending K|V work) — on compute units this launch leaves empty.  Ordinary
+    // independent workgroups: they share nothing with the members' and nobody waits for them inside the launch.
+    int rider_base;    // wg_start[FH_MAX_MEMBERS] rounded up to a multiple of 8: rider r sits on XCD r % 8 like tile r of a stand-alone launch
+    GkRider kv;        // riders 0 .. kv.units - 1
 };
+static_assert(sizeof(FhGroup) <= 4096, "FhGroup travels by value in the kernel arguments");
 
 // LDS map (bytes), the same arithmetic on host and device
 struct FhLds { int gains, xn, xm, qi, ki, vi, mask, total; };
@@ -666,6 +673,11 @@ __global__ __launch_bounds__(FH_THREADS) void fused_head_fwd_kernel(const FhGrou
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     FH_STAMP(0);
     FH_STAMP_CLK(10);
+    if ((int)blockIdx.x >= G.wg_start[FH_MAX_MEMBERS]) {       // a rider (or padding in front of the riders)
+        const int r = (int)blockIdx.x - G.rider_base;
+        if (r >= 0 && r < G.kv.units) gk_rider_unit(G.kv, r, smem);
+        return;
+    }
     int g = 0;
     while (g + 1 < G.count && (int)blockIdx.x >= G.wg_start[g + 1]) ++g;
     const FhMember& M = G.m[g];
@@ -877,10 +889,54 @@ template <int NP> static int fh_launch(const FhGroup& G, int wgs, size_t lds, hi
     return MTN_OK;
 }
 
+// Compute units of the current device (asked once per device, not once per process: the ranks of a data-parallel run may sit on
+// different parts)
+static int fh_cu_count() {
+    static int cus[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    int n = __atomic_load_n(&cus[dev], __ATOMIC_RELAXED);
+    if (n == 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = -1;
+        __atomic_store_n(&cus[dev], n, __ATOMIC_RELAXED);
+    }
+    return n > 0 ? n : 0;
+}
+// Rider slots of a launch = the compute units its own workgroups leave empty (one 512-thread workgroup of ~240 VGPRs per CU; a rider
+// is 512 threads, 206 VGPRs and 128 KiB of LDS: it cannot share a CU with anything here).  A launch that fills the chip (batch 64:
+// 384+ workgroups) has none.  MTN_RIDER_MAX_SLOTS caps the number.
+// Launches with feed-forward members (the 4-block kernel; 160 workgroups of ~14.5 us in the layer's last group) are SHORTER than a
+// rider tile (~19 us): a rider there lengthens the launch (to ~19.8 us) — and still pays: with those 96 + 8 slots per layer every
+// tile of layers 1-5 finds a launch in front of its reader, without them 808 of 1 512 leave in stand-alone launches and the step is
+// where it was (profiles/riders_ab.txt: -1.8 % against -0.4 %).  MTN_RIDER_FFN_HOSTS=0 keeps riders out of them (measurements).
+static bool fh_rider_ffn_hosts() {
+    const char* e = MTN_ENV("MTN_RIDER_FFN_HOSTS");
+    return e ? e[0] != '0' : true;
+}
+static int fh_rider_slots(const FhLaunch& P) {
+    if (!mtn_riders_enabled()) return 0;
+    if (P.np == 4 && !fh_rider_ffn_hosts()) return 0;
+    const int base = (P.wgs + 7) & ~7;
+    int slots = fh_cu_count() - base;
+    const char* cap = MTN_ENV("MTN_RIDER_MAX_SLOTS");
+    if (cap && atoi(cap) < slots) slots = atoi(cap);
+    return slots > 0 ? slots : 0;
+}
+
 int fh_group_fwd_stage1(int n_mha, const mtn_mha_args* mha, int n_ffn, const mtn_ffn_args* ffn, void* stream) {
     FhLaunch P;
     MTN_CHECK_ARG(fh_plan(n_mha, mha, n_ffn, ffn, P), "group outside the fused kernel's tiling");
     hipStream_t s = (hipStream_t)stream;
+    const int slots = fh_rider_slots(P);
+    if (slots > 0) {
+        gk_rider_take(slots, &P.G.kv);
+        if (P.G.kv.units > 0) {
+            P.G.rider_base = (P.wgs + 7) & ~7;
+            P.wgs = P.G.rider_base + P.G.kv.units;
+            if (P.lds < (size_t)GK_LDS) P.lds = GK_LDS;
+        }
+    }
+    static_assert(GK_LDS <= FH_LDS_MAX, "a rider tile's x image fits the launch's dynamic LDS limit");
     const int rc = P.np == 4 ? fh_launch<4>(P.G, P.wgs, P.lds, s) : (P.np == 3 ? fh_launch<3>(P.G, P.wgs, P.lds, s) : fh_launch<1>(P.G, P.wgs, P.lds, s));
     if (rc != MTN_OK) return rc;
     MTN_CHECK_LAUNCH();

@@ -2316,6 +2316,16 @@ extern "C" int mtn_gemm_tt_table_aux(int dtype, int count, const mtn_gemm_proble
     return MTN_OK;
 }
 
+// a wide K = 512 launch issued outside mtn_gemm (gemm_k512.hip: pending K|V work flushed stand-alone); `tiles` = what it launched
+void gemm_census_note_k512(int count, const mtn_gemm_problem* p, int tiles) {
+    if (!g_census_on) return;
+    CensusEntry e;
+    memset(&e, 0, sizeof(e));
+    e.dtype = MTN_BF16; e.count = count; e.variant = V_K512; e.tiles = tiles; e.table = -1;
+    for (int i = 0; i < count; ++i) e.p[i] = p[i];
+    g_census.push_back(e);
+}
+
 extern "C" int mtn_census_begin(void) { g_census.clear(); g_census_tables.clear(); g_census_on = true; return MTN_OK; }
 extern "C" int mtn_census_end(void) { g_census_on = false; return (int)g_census.size(); }
 extern "C" const char* mtn_census_variant_name(int variant) { return (variant >= 0 && variant < V_COUNT) ? g_variant_name[variant] : "?"; }

@@ -7,14 +7,8 @@
 // W tile [128][512] as MFMA fragments in registers (wave w = output columns 16w .. 16w+15; coalesced loads — lane 4r + c reads row r,
 // 16-byte chunk c — put in operand order with ds_bpermute), one wait, 1024 MFMAs, bias, bf16, and the tile leaves through LDS as
 // whole 256-byte row segments.
-#include "fused_common.h"
+#include "gemm_k512_tile.h"
 
-static constexpr int GK_THREADS = 512;
-static constexpr int GK_K = 512;
-static constexpr int GK_LDS = 128 * FH_ROWB;              // 128 KiB: the x image; reused as the output staging area
-static constexpr int GK_CPITCH = 272;                     // bytes per staged output row (256 + 16)
-
-struct GkProblem { const bf16_t* A; const bf16_t* B; const float* bias; bf16_t* out; int lda, ldb, ldc, M, N, tiles_m; };
 struct GkGroup {
     int count;
     int tile_start[MTN_GEMM_MAX_GROUP + 1];
@@ -102,95 +96,11 @@ __global__ __launch_bounds__(GK_THREADS) void gemm_k512_kernel(const GkGroup G) 
 // at LDS speed.  Here a wave owns two 16-column blocks (32 of the tile's 256 columns): an x fragment feeds two MFMAs, the LDS
 // reads per FLOP halve, and an x row tile is re-read for 4 column tiles instead of 8.  W fragments: 128 VGPRs.
 // ====================================================================================================================
-static constexpr int GW_CPITCH = 528;                     // bytes per staged output row (512 + 16)
 __global__ __launch_bounds__(GK_THREADS) void gemm_k512w_kernel(const GkGroup G) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lg = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int g = 0;
     while (g + 1 < G.count && (int)blockIdx.x >= G.tile_start[g + 1]) ++g;
-    const GkProblem& P = G.p[g];
-    const int t = (int)blockIdx.x - G.tile_start[g];
-    const int tn = t / P.tiles_m, tm = t - tn * P.tiles_m;      // row tiles vary fastest (see gemm_k512_kernel)
-    const int row0 = tm * 128, col0 = tn * 256;
-    const int R = (P.M - row0) < 128 ? (P.M - row0) : 128;
-    {
-        const unsigned ldab = (unsigned)P.lda * 2u;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(P.A + (size_t)row0 * P.lda), 0, (R - 1) * ldab + FH_ROWB, 0x00020000);
-        for (int r = wave; r < 128; r += 8) {
-            const unsigned vo = r < R ? (unsigned)r * ldab + (unsigned)((lane ^ (r & 15)) << 4) : 0x80000000u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (fh_lds_void_t*)(smem + r * FH_ROWB), 16, vo, 0, 0, 0);
-        }
-    }
-    float4 bq[2];
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-        const int colq = col0 + 128 * cb + 16 * wave + 4 * lg;
-        bq[cb] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (P.bias && colq < P.N) bq[cb] = *(const float4*)(P.bias + colq);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    // W fragments in CONTRACTION order (step s of both column blocks, then step s + 1, ...): the MFMAs of step s start as soon as its
-    // two fragments have landed, while the later ones are still being accepted — a wave's 32 loads take ~6 us to issue, and the kernel
-    // used to wait for all of them before its first MFMA.
-    uint4 wf[2][16];                                             // column block cb: columns col0 + 128 cb + 16 wave .. + 15
-    {
-        const bf16_t* wrow[2];
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-            int n = col0 + 128 * cb + 16 * wave + (lane >> 2);
-            n = n < P.N ? n : P.N - 1;
-            wrow[cb] = P.B + (size_t)n * P.ldb + (lane & 3) * 8;
-        }
-#pragma unroll
-        for (int s = 0; s < 16; ++s) { wf[0][s] = *(const uint4*)(wrow[0] + s * 32); wf[1][s] = *(const uint4*)(wrow[1] + s * 32); }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    // the x image (and the bias) has landed once at most the 32 W loads behind it fly: s_waitcnt vmcnt(32) lgkmcnt(15) expcnt(7) as a
-    // BUILTIN, so that the compiler's own counter knows that no LDS-DMA is outstanding any more (behind an inline-asm wait it would put
-    // vmcnt(0) in front of the first LDS read it sees)
-    __builtin_amdgcn_s_waitcnt(0x8F70);
-    __builtin_amdgcn_s_barrier();
-    f32x4_t acc[2][8];
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt) acc[cb][mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const int src = (4 * l15 + lg) * 4;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {                         // coalesced load order -> MFMA operand order
-            wf[cb][s].x = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)wf[cb][s].x);
-            wf[cb][s].y = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)wf[cb][s].y);
-            wf[cb][s].z = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)wf[cb][s].z);
-            wf[cb][s].w = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)wf[cb][s].w);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt) {
-            const uint4 xf = fh_xfrag(smem, mt * 16 + l15, s * 4 + lg);
-            mma16<bf16_t>(acc[0][mt], wf[0][s], xf);
-            mma16<bf16_t>(acc[1][mt], wf[1][s], xf);
-        }
-    }
-    __syncthreads();                                             // the x image is dead: it becomes the output staging area
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt) {
-            const int r = mt * 16 + l15;
-            *(uint2*)(smem + r * GW_CPITCH + (128 * cb + 16 * wave + 4 * lg) * 2) =
-                make_uint2(fh_pack2(acc[cb][mt][0] + bq[cb].x, acc[cb][mt][1] + bq[cb].y), fh_pack2(acc[cb][mt][2] + bq[cb].z, acc[cb][mt][3] + bq[cb].w));
-        }
-    __syncthreads();
-    // whole 512-byte row segments: 32 lanes per row, 16 rows per pass
-#pragma unroll
-    for (int ps = 0; ps < 8; ++ps) {
-        const int r = ps * 16 + (tid >> 5), c = tid & 31;
-        const int col = col0 + c * 8;
-        if (r < R && col < P.N)
-            *(uint4*)(P.out + (size_t)(row0 + r) * P.ldc + col) = *(const uint4*)(smem + r * GW_CPITCH + c * 16);
-    }
+    gk_wide_tile(G.p[g], (int)blockIdx.x - G.tile_start[g], smem);      // (gemm_k512_tile.h: the body the K|V riders of fused.hip share)
 }
 
 // ====================================================================================================================
@@ -400,6 +310,32 @@ __global__ __launch_bounds__(GK_THREADS, 2) void gemm_k512p_kernel(const GkGroup
     }
 }
 
+// one problem in the form of these kernels (bf16, row-major x row-major, K = 512, plain bias epilogue into out_lp); false: not theirs
+static bool gk_fill(const mtn_gemm_problem& q, GkProblem& P) {
+    if (q.a_trans || q.b_trans || q.K != GK_K || q.relu || q.gate || q.residual || q.out_f32 || q.rowsum_out || q.adam || !q.out_lp) return false;
+    if (q.drop.p > 0.f && q.drop.seed) return false;
+    if (q.M < 1 || q.N < 8 || (q.N & 7) || (q.lda & 7) || (q.ldb & 7) || (q.ldc & 7) || q.lda < GK_K || q.ldb < GK_K) return false;
+    if ((long)q.M * q.lda * 2 >= (1L << 31)) return false;
+    if (((size_t)q.A | (size_t)q.B | (size_t)q.out_lp) & 15) return false;
+    if (q.bias && ((size_t)q.bias & 15)) return false;
+    P.A = (const bf16_t*)q.A; P.B = (const bf16_t*)q.B; P.bias = q.bias; P.out = (bf16_t*)q.out_lp;
+    P.lda = q.lda; P.ldb = q.ldb; P.ldc = q.ldc; P.M = q.M; P.N = q.N; P.tiles_m = (q.M + 127) / 128;
+    return true;
+}
+static long gk_persist_units(int count, const mtn_gemm_problem* p) {
+    long units = 0;
+    for (int i = 0; i < count; ++i) units += (long)((p[i].M + GP_ROWS - 1) / GP_ROWS) * ((p[i].N + 127) / 128);
+    return units;
+}
+static bool gk_wide_attr() {
+    static bool attr_w = false;
+    if (!attr_w) {
+        if (hipFuncSetAttribute((const void*)gemm_k512w_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GK_LDS) != hipSuccess) return false;
+        attr_w = true;
+    }
+    return true;
+}
+
 // -> 1 when the launch was taken (every problem: bf16, row-major x row-major, K = 512, plain bias epilogue into out_lp), 0 when the
 // caller should use the general kernels, < 0 on a launch error
 int gemm_k512_try(int count, const mtn_gemm_problem* p, int min_tiles, hipStream_t s, int* tiles_out) {
@@ -408,18 +344,9 @@ int gemm_k512_try(int count, const mtn_gemm_problem* p, int min_tiles, hipStream
     memset(&G, 0, sizeof(G));
     int tiles = 0;
     for (int i = 0; i < count; ++i) {
-        const mtn_gemm_problem& q = p[i];
-        if (q.a_trans || q.b_trans || q.K != GK_K || q.relu || q.gate || q.residual || q.out_f32 || q.rowsum_out || q.adam || !q.out_lp) return 0;
-        if (q.drop.p > 0.f && q.drop.seed) return 0;
-        if (q.M < 1 || q.N < 8 || (q.N & 7) || (q.lda & 7) || (q.ldb & 7) || (q.ldc & 7) || q.lda < GK_K || q.ldb < GK_K) return 0;
-        if ((long)q.M * q.lda * 2 >= (1L << 31)) return 0;
-        if (((size_t)q.A | (size_t)q.B | (size_t)q.out_lp) & 15) return 0;
-        if (q.bias && ((size_t)q.bias & 15)) return 0;
-        GkProblem& P = G.p[i];
-        P.A = (const bf16_t*)q.A; P.B = (const bf16_t*)q.B; P.bias = q.bias; P.out = (bf16_t*)q.out_lp;
-        P.lda = q.lda; P.ldb = q.ldb; P.ldc = q.ldc; P.M = q.M; P.N = q.N; P.tiles_m = (q.M + 127) / 128;
+        if (!gk_fill(p[i], G.p[i])) return 0;
         G.tile_start[i] = tiles;
-        tiles += P.tiles_m * ((q.N + 127) / 128);
+        tiles += G.p[i].tiles_m * ((p[i].N + 127) / 128);
     }
     if (tiles < min_tiles) return 0;
     G.count = count;
@@ -433,8 +360,7 @@ int gemm_k512_try(int count, const mtn_gemm_problem* p, int min_tiles, hipStream
     // Persistent form: measured per launch in the step, same box (profiles/r03_u_k512_persistent_ab.txt): 69.4 vs 69.0 us at 14 units
     // per workgroup (cfg2, batch 32), 104 vs 123 us at 28 (batch 64) — the resident workgroups pay ~5 us of start-up per W tile and
     // their x images land in 4-5 us however few are in flight, so it wins only when the lists are long.  MTN_K512_PERSIST=1 / 0 forces.
-    long units = 0;
-    for (int i = 0; i < count; ++i) units += (long)((p[i].M + GP_ROWS - 1) / GP_ROWS) * ((p[i].N + 127) / 128);
+    const long units = gk_persist_units(count, p);
     const char* pe = MTN_ENV("MTN_K512_PERSIST");
     if (pe ? pe[0] != '0' : units >= 20L * GP_GRID) {
         hipLaunchKernelGGL(gemm_k512p_kernel, dim3(GP_GRID), dim3(GK_THREADS), GP_LDS, s, G);
@@ -446,11 +372,7 @@ int gemm_k512_try(int count, const mtn_gemm_problem* p, int min_tiles, hipStream
     bool wide = true;
     for (int i = 0; i < count; ++i) wide = wide && (p[i].N % 256) == 0;
     if (wide) {
-        static bool attr_w = false;
-        if (!attr_w) {
-            if (hipFuncSetAttribute((const void*)gemm_k512w_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GK_LDS) != hipSuccess) return 0;
-            attr_w = true;
-        }
+        if (!gk_wide_attr()) return 0;
         int tw = 0;
         for (int i = 0; i < count; ++i) { G.tile_start[i] = tw; tw += G.p[i].tiles_m * (p[i].N / 256); }
         for (int i = count; i <= MTN_GEMM_MAX_GROUP; ++i) G.tile_start[i] = tw;
@@ -463,4 +385,127 @@ int gemm_k512_try(int count, const mtn_gemm_problem* p, int min_tiles, hipStream
     if (hipGetLastError() != hipSuccess) return -1;
     if (tiles_out) *tiles_out = tiles;
     return 1;
+}
+
+// ====================================================================================================================
+// Pending K|V work (mtn_kv_project).  The memories' K|V projections of decoder layer L are first read at layer L's second launch,
+// yet they used to run for ALL layers at the head of the step, where nothing else can run beside them.  The fused forward launches
+// of a layer (fused.hip) leave compute units empty — 192 or 160 workgroups of one per CU on 256 CUs — so the projections of the
+// later layers wait here, in deadline order, and leave as RIDER workgroups of those launches: one 128 x 256 tile (gk_wide_tile) per
+// empty CU.  What a launch is about to read is flushed first as a stand-alone gemm_k512w launch; nothing is ever skipped.
+// Host state only (pointers and tile counts): under stream capture the same decisions are taken once and the graph replays them.
+// ====================================================================================================================
+#include <deque>
+#include <mutex>
+void gemm_census_note_k512(int count, const mtn_gemm_problem* p, int tiles);      // gemm.hip
+
+struct GkPending { mtn_gemm_problem q; GkProblem P; int total, done; };      // tiles [done, total) are still to be computed
+static std::deque<GkPending> g_pending;
+static std::mutex g_pending_mutex;
+static long g_rider_stats[3] = {0, 0, 0};      // tiles computed by riders, tiles flushed stand-alone, stand-alone flush launches
+
+extern "C" int mtn_riders_enabled(void) {
+    const char* e = MTN_ENV("MTN_RIDERS");
+    if (e && e[0] == '0') return 0;
+    const char* cap = MTN_ENV("MTN_RIDER_MAX_SLOTS");      // no slot in any launch: nothing waits for one, the schedule is that of MTN_RIDERS=0
+    return (cap && atoi(cap) <= 0) ? 0 : 1;
+}
+
+// stand-alone wide launches of the first n pending problems (what is left of them), then they leave the queue
+static int gk_flush_head(int n, hipStream_t s) {
+    if (n > 0 && !gk_wide_attr()) { mtn_set_error("gemm_k512w_kernel: cannot raise the dynamic LDS limit"); return MTN_ERR_LAUNCH; }
+    while (n > 0) {
+        const int k = n < MTN_GEMM_MAX_GROUP ? n : MTN_GEMM_MAX_GROUP;
+        GkGroup G;
+        memset(&G, 0, sizeof(G));
+        mtn_gemm_problem q[MTN_GEMM_MAX_GROUP];
+        int tw = -g_pending[0].done;               // block 0 is the first problem's first pending tile (only the head problem can be part done)
+        for (int i = 0; i < k; ++i) {
+            G.p[i] = g_pending[i].P; q[i] = g_pending[i].q;
+            G.tile_start[i] = tw;
+            tw += g_pending[i].total;
+        }
+        for (int i = k; i <= MTN_GEMM_MAX_GROUP; ++i) G.tile_start[i] = tw;
+        G.count = k;
+        if (tw > 0) {
+            hipLaunchKernelGGL(gemm_k512w_kernel, dim3(tw), dim3(GK_THREADS), GK_LDS, s, G);
+            if (hipGetLastError() != hipSuccess) { mtn_set_error("gemm_k512w_kernel: launch failed"); return MTN_ERR_LAUNCH; }
+            gemm_census_note_k512(k, q, tw);
+            g_rider_stats[1] += tw; ++g_rider_stats[2];
+        }
+        g_pending.erase(g_pending.begin(), g_pending.begin() + k);
+        n -= k;
+    }
+    return MTN_OK;
+}
+
+// Before a launch that reads the buffers outs[0 .. n): everything pending up to the last problem that writes one of them
+int gk_pending_flush_reads(int n, const void* const* outs, void* stream) {
+    std::lock_guard<std::mutex> lock(g_pending_mutex);
+    int last = -1;
+    for (int i = 0; i < (int)g_pending.size(); ++i)
+        for (int j = 0; j < n; ++j)
+            if (outs[j] && (const void*)g_pending[i].P.out == outs[j]) last = i;
+    return last < 0 ? MTN_OK : gk_flush_head(last + 1, (hipStream_t)stream);
+}
+
+// Up to `slots` pending tiles, from the head, for the rider workgroups of one launch.  They are this launch's from now on.
+void gk_rider_take(int slots, GkRider* K) {
+    std::lock_guard<std::mutex> lock(g_pending_mutex);
+    memset(K, 0, sizeof(*K));
+    int j = 0;
+    while (j < GK_RIDER_PROBLEMS && slots > 0 && !g_pending.empty()) {
+        GkPending& e = g_pending.front();
+        const int n = e.total - e.done < slots ? e.total - e.done : slots;
+        K->start[j] = K->units; K->tile0[j] = e.done; K->p[j] = e.P;
+        K->units += n; slots -= n; e.done += n;
+        ++j;
+        if (e.done == e.total) g_pending.pop_front();
+    }
+    for (int i = j; i <= GK_RIDER_PROBLEMS; ++i) K->start[i] = K->units;
+    g_rider_stats[0] += K->units;
+}
+
+int gk_pending_flush_all(void* stream) {
+    std::lock_guard<std::mutex> lock(g_pending_mutex);
+    return gk_flush_head((int)g_pending.size(), (hipStream_t)stream);
+}
+
+extern "C" int mtn_rider_counters(long* out4) {
+    MTN_CHECK_ARG(out4, "null output");
+    std::lock_guard<std::mutex> lock(g_pending_mutex);
+    long left = 0;
+    for (const GkPending& e : g_pending) left += e.total - e.done;
+    out4[0] = g_rider_stats[0]; out4[1] = g_rider_stats[1]; out4[2] = g_rider_stats[2]; out4[3] = left;
+    return MTN_OK;
+}
+
+// K|V projections of constant memories (problems as for mtn_gemm, any count): the first n_now problems run now, the others may wait
+// for an empty compute unit (see above) when riders are on and the grouped launches of all of them would take the wide one-shot
+// kernel anyway — same kernel body, same bits.  Otherwise exactly the grouped mtn_gemm launches of all of them, now.
+extern "C" int mtn_kv_project(int dtype, int count, const mtn_gemm_problem* problems, int n_now, void* stream) {
+    MTN_CHECK_ARG(count >= 1 && problems && n_now >= 0, "bad problem list");
+    bool defer = mtn_riders_enabled() && dtype == MTN_BF16 && n_now < count && !MTN_ENV("MTN_K512_PERSIST") && !MTN_ENV("MTN_K512_WIDE");
+    GkProblem tmp;
+    for (int i = 0; i < count && defer; ++i) defer = gk_fill(problems[i], tmp) && problems[i].N % 256 == 0;
+    for (int i = 0; i < count && defer; i += MTN_GEMM_MAX_GROUP)      // a group that the persistent form would take (long unit lists: batch 64) keeps it
+        defer = gk_persist_units(count - i < MTN_GEMM_MAX_GROUP ? count - i : MTN_GEMM_MAX_GROUP, problems + i) < 20L * GP_GRID;
+    if (!defer) {
+        for (int i = 0; i < count; i += MTN_GEMM_MAX_GROUP) {
+            const int rc = mtn_gemm(dtype, count - i < MTN_GEMM_MAX_GROUP ? count - i : MTN_GEMM_MAX_GROUP, problems + i, stream);
+            if (rc != MTN_OK) return rc;
+        }
+        return MTN_OK;
+    }
+    std::lock_guard<std::mutex> lock(g_pending_mutex);
+    int rc = gk_flush_head((int)g_pending.size(), (hipStream_t)stream);      // (left by a forward that did not finish: its buffers are still the caller's)
+    if (rc != MTN_OK) return rc;
+    for (int i = 0; i < count; ++i) {
+        GkPending e;
+        e.q = problems[i];
+        gk_fill(problems[i], e.P);
+        e.total = e.P.tiles_m * (e.P.N / 256); e.done = 0;
+        g_pending.push_back(e);
+    }
+    return gk_flush_head(n_now, (hipStream_t)stream);
 }

@@ -18,6 +18,9 @@
 int fh_group_eligible(int dtype, int n_mha, const mtn_mha_args* mha, int n_ffn, const mtn_ffn_args* ffn);
 int fh_group_fwd_stage1(int n_mha, const mtn_mha_args* mha, int n_ffn, const mtn_ffn_args* ffn, void* stream);
 int fh_is_enabled();
+// csrc/gemm_k512.hip
+int gk_pending_flush_reads(int n, const void* const* outs, void* stream);
+int gk_pending_flush_all(void* stream);
 // csrc/fused_bwd.hip
 struct FbIo { const void* dyl; void *dq, *dk, *dv; int ldq, ldkv; const float* lnf; float* ln_part; };
 int fb_group_eligible(int dtype, int n_mha, const mtn_mha_args* mha, const FbIo* io);
@@ -107,12 +110,22 @@ void attn_args_of(const mtn_mha_args* a, int dtype, mtn_attn_args* t) {
     t->o = a->o; t->ldo = d; t->lse = a->lse;
 }
 
+// everything that still waits for a launch to ride in (K|V projections: mtn_kv_project), stand-alone, now
+extern "C" int mtn_riders_flush(void* stream) { return gk_pending_flush_all(stream); }
+
 // ------------------------------------------------------------------------------------------ forward
 extern "C" int mtn_sublayer_group_fwd(int dtype, int n_mha, const mtn_mha_args* mha, int n_ffn, const mtn_ffn_args* ffn, void* stream) {
     MTN_CHECK_ARG(dtype == MTN_F32 || dtype == MTN_BF16, "bad dtype");
     MTN_CHECK_ARG(n_mha >= 0 && n_mha <= MTN_SUBLAYER_MAX_GROUP && n_ffn >= 0 && n_ffn <= MTN_SUBLAYER_MAX_GROUP && n_mha + n_ffn > 0, "bad group size");
     for (int i = 0; i < n_mha; ++i) RUN(check_mha(&mha[i], false));
     for (int i = 0; i < n_ffn; ++i) RUN(check_ffn(&ffn[i], false));
+    {   // a memory's K|V that is still pending (mtn_kv_project) and that this group reads: computed now, stand-alone
+        const void* reads[MTN_SUBLAYER_MAX_GROUP];
+        int n = 0;
+        for (int i = 0; i < n_mha; ++i)
+            if (!mha[i].self_attn && mha[i].kv_ready) reads[n++] = mha[i].kv;
+        if (n) RUN(gk_pending_flush_reads(n, reads, stream));
+    }
     // Fused first launch (csrc/fused.hip): stages 1-3 in one kernel per (sample block, head | w_1 column slice)
     bool fused = fh_group_eligible(dtype, n_mha, mha, n_ffn, ffn) != 0;
     mtn_mha_args pre[MTN_SUBLAYER_MAX_GROUP];

@@ -244,6 +244,10 @@ SYMBOLS = {
     "mtn_attention_bwd_group": (C.c_int, [C.c_int, C.c_int, C.POINTER(AttnArgs), _P]),
     "mtn_cast_group": (C.c_int, [C.c_int, C.c_int, C.POINTER(CastDesc), _P]),
     "mtn_fused_enable": (C.c_int, [C.c_int]),
+    "mtn_kv_project": (C.c_int, [C.c_int, C.c_int, C.POINTER(GemmProblem), C.c_int, _P]),
+    "mtn_riders_flush": (C.c_int, [_P]),
+    "mtn_riders_enabled": (C.c_int, []),
+    "mtn_rider_counters": (C.c_int, [C.POINTER(C.c_long)]),
     "mtn_fused_counters": (C.c_int, [C.POINTER(C.c_long)]),
     "mtn_ln_epilogue_groups": (C.c_long, []),
     "mtn_ln_fold": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, _P]),

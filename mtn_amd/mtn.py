@@ -910,8 +910,12 @@ class EncoderDecoder(nn.Module):
 
     # ---- reference API ---------------------------------------------------------------------------
     def forward(self, b):                      # mtn.py:28-30
-        q, v, cp, hs, ae = self.encode(b.query, b.query_mask, b.his, b.his_mask, b.cap, b.cap_mask, b.fts, b.fts_mask)
-        return self.decode(v, hs, cp, q, b.fts_mask, b.his_mask, b.cap_mask, b.query_mask, b.trg, b.trg_mask, ae)
+        try:
+            q, v, cp, hs, ae = self.encode(b.query, b.query_mask, b.his, b.his_mask, b.cap, b.cap_mask, b.fts, b.fts_mask)
+            return self.decode(v, hs, cp, q, b.fts_mask, b.his_mask, b.cap_mask, b.query_mask, b.trg, b.trg_mask, ae)
+        finally:
+            if self._flat is not None and self._flat.is_cuda:
+                ops.flush_riders()             # nothing that waited for a launch to ride in outlives the forward
 
     def vid_encode(self, video_features, video_features_mask=None, encoded_query=None):   # mtn.py:32-36
         return [self.vid_encoder[i](ft) for i, ft in enumerate(video_features)]
@@ -997,18 +1001,23 @@ class EncoderDecoder(nn.Module):
             ae = [self.query_embed(ft) for _ in range(len(vid))]
         return self.query_encoder(*streams, ae)
 
-    def hoist_memory_kv(self, cap_memory, his_memory, q_memory, vid_fts, outs=None):
+    def hoist_memory_kv(self, cap_memory, his_memory, q_memory, vid_fts, outs=None, defer=False):
         """Project K|V of the encoder-side memories for every decoder layer that attends them (3 text cross-attentions + F
         video attentions per layer) in a few grouped GEMMs ahead of the layer loop (ops.project_memories).  The projections
         are left on the sublayer connections (``_kv_ready``) for the lockstep groups to pick up; clear_memory_kv() removes
-        them.  Returns the list of K|V buffers (pass it back as ``outs`` to refresh them in place)."""
+        them.  Returns the list of K|V buffers (pass it back as ``outs`` to refresh them in place).
+        ``defer`` (the whole-model forward): only layer 0's projections are needed before the layer loop; those of the later
+        layers may ride in the layers' fused launches (ops.project_memories n_now) — the caller flushes after the loop."""
         if not (self.hoist_kv and self.lockstep and self._flat is not None and q_memory.is_cuda):
             return None
         nF = len(vid_fts)
-        items, targets = [], []
-        for layer in self.decoder.layers:
+        items, targets, n_head, use_order = [], [], None, []
+        for li, layer in enumerate(self.decoder.layers):
+            if li == 1:
+                n_head = len(items)
             if layer._forward_hooks_on_sublayers() or nF + 1 > 4:
                 continue
+            first = len(items)
             text, chains, _, _ = layer._plan(cap_memory, None, his_memory, None, q_memory, None, None, vid_fts, [None] * nF,
                                              self.auto_encoder_ft)
             for sc, mod, mem, _ in list(text[1:]) + [chains[i][1] for i in range(nF)]:
@@ -1018,7 +1027,13 @@ class EncoderDecoder(nn.Module):
                     continue
                 items.append((mem_lp, f["w_qkv_lp"], f["b_qkv"]))
                 targets.append(sc)
-        kvs = ops.project_memories(items, self.compute_dtype, outs)
+            # order of first use inside the layer (_forward_lockstep): x's first memory and the chains' video memories share a group, x's
+            # other memories follow one group each — the order in which deferred projections must be ready
+            idx = list(range(first, len(items)))
+            text_n = sum(1 for sc in targets[first:] if any(sc is t[0] for t in text[1:]))
+            use_order += idx[:1] + idx[text_n:] + idx[1:text_n] if text_n else idx
+        n_now = (n_head if n_head is not None else len(items)) if defer and L.load().mtn_riders_enabled() else None
+        kvs = ops.project_memories(items, self.compute_dtype, outs, n_now=n_now, order=use_order)
         self._kv_targets = list(zip(targets, kvs))
         self.attach_memory_kv(self._kv_targets)
         return kvs
@@ -1029,6 +1044,8 @@ class EncoderDecoder(nn.Module):
             object.__setattr__(sc, "_kv_ready", kv)
 
     def clear_memory_kv(self):
+        if self._flat is not None and self._flat.is_cuda:
+            ops.flush_riders()               # (deferred projections that found no launch to ride in: nothing reads them any more, but nothing is skipped)
         for layer in self.decoder.layers:
             for sc in layer.sublayer:
                 if getattr(sc, "_kv_ready", None) is not None:
@@ -1064,7 +1081,7 @@ class EncoderDecoder(nn.Module):
         v_l = enc_leaf[4:4 + nF]
         ae_l = enc_leaf[4 + nF:] if ae is not None else None
         ops.prepare_masks(b.trg_mask, b.his_mask, b.cap_mask, b.query_mask, b.fts_mask)
-        self.hoist_memory_kv(cp_l, hs_l, q_l, v_l)
+        self.hoist_memory_kv(cp_l, hs_l, q_l, v_l, defer=True)
         layers = []
         x_in, ae_in = x_l, ae_l
         for layer in self.decoder.layers:
@@ -1087,7 +1104,7 @@ class EncoderDecoder(nn.Module):
                query_mask, tgt, tgt_mask, auto_encoded_ft):          # mtn.py:58-60
         self.prepare()
         x0 = self.embed_target(tgt)
-        self.hoist_memory_kv(cap_memory, his_memory, query_memory, encoded_vid_features)
+        self.hoist_memory_kv(cap_memory, his_memory, query_memory, encoded_vid_features, defer=True)
         try:
             return self._decode_layers(encoded_vid_features, vid_features_mask, x0, his_memory, his_mask, cap_memory, cap_mask,
                                        query_memory, query_mask, tgt_mask, auto_encoded_ft)

@@ -1133,12 +1133,15 @@ def ensemble_rows(xs, weights=None, mode="prob", out=None):
 
 
 # ------------------------------------------------------------------------------------------ memory K/V, ahead of the layers
-def project_memories(items, lp_dtype, outs=None):
+def project_memories(items, lp_dtype, outs=None, n_now=None, order=None):
     """K|V projections (mtn.py:257-258) of CONSTANT memories for many sublayers at once: items = [(mem_lp (B,m,d) compute dtype,
     w_qkv_lp (3d,d), b_qkv (3d,) fp32)] -> list of (B*m, 2d) compute-dtype tensors.  The encoder-side memories (history,
     caption, query, video) are the same tensors in every decoder layer, so their N x (3+F) projections do not depend on
     anything computed inside the layer loop: they run here as a few large grouped GEMMs instead of riding in N x (3+F)
-    small per-sublayer launches (and, in the decode path, once per dialogue instead of once per token)."""
+    small per-sublayer launches (and, in the decode path, once per dialogue instead of once per token).
+    ``n_now`` (whole-model training forward): only the first n_now items are needed at once; the library may keep the others, in
+    the order of their first use (``order``: a permutation of the item indices that keeps the first n_now in front), for compute units that the fused forward launches of the layers leave empty (mtn_kv_project), and computes
+    whatever a launch is about to read.  The caller ends the forward with flush_riders()."""
     if not items:
         return []
     code = L.dtype_code(lp_dtype)
@@ -1152,9 +1155,18 @@ def project_memories(items, lp_dtype, outs=None):
         p.bias, p.gate_scale, p.out_lp, p.ldc = b.data_ptr() + d * b.element_size(), 1.0, kv.data_ptr(), 2 * d
         outs.append(kv)
         probs.append(p)
+    if n_now is not None:
+        arr = (L.GemmProblem * len(probs))(*(probs[k] for k in (order if order is not None else range(len(probs)))))
+        L.check(L.load().mtn_kv_project(code, len(probs), arr, min(n_now, len(probs)), L.stream_ptr()))
+        return outs
     for i in range(0, len(probs), L.GEMM_MAX_GROUP):
         gemm(code, probs[i:i + L.GEMM_MAX_GROUP])
     return outs
+
+
+def flush_riders():
+    """Compute whatever project_memories(..., n_now=...) left waiting (nothing, when every tile found a launch to ride in)."""
+    L.check(L.load().mtn_riders_flush(L.stream_ptr()))
 
 
 # ------------------------------------------------------------------------------------------ fused embeddings
