@@ -44,7 +44,8 @@ const char* mtn_last_error(void);
  * 113 (round 6): mtn_decode_args gained the trailing field `max_m`; mtn_decode_step takes W <= 16 rows, clamps `grid` to the device's
  * compute-unit count and bounds its polls in time (see there).
  * 114: mtn_assemble_tokens_desc gained the trailing field `row_len` (NULL = no cut; a zeroed struct keeps meaning that).
- * 115: new entry point mtn_sample_rows.  116: new entry point mtn_score_rows.  117: new entry point mtn_constrain_rows. */
+ * 115: new entry point mtn_sample_rows.  116: new entry point mtn_score_rows.  117: new entry point mtn_constrain_rows.
+ * 121: new entry point mtn_mbr_select. */
 int mtn_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -733,6 +734,41 @@ typedef struct {
     float* out; long ldo;
 } mtn_ensemble_args;
 int mtn_ensemble_rows(const mtn_ensemble_args* args /* host */, void* stream);
+/* Minimum-Bayes-risk selection (version 121; not in the reference, like sampling): of the K <= MTN_MBR_MAX_HYP hypotheses of a set — the
+ * samples or the n-best list of a dialogue — answer with the one that agrees most, in n-grams, with the others (csrc/mbr.hip).  A hypothesis
+ * is a list of token ids without <sos> / <eos>; tokens compare as int32, any value.  For hypotheses h, r and an order n:
+ *   c_n(h)    = max(len(h) - n + 1, 0)
+ *   m_n(h, r) = the clipped n-gram match count: the sum over distinct n-grams g of min(count of g in h, count of g in r)
+ * and for the maximum order N in 1..4:
+ *   F_n(h, r) = (double)(2 m_n) / (double)(c_n(h) + c_n(r)), exactly 0.0 when that denominator is 0
+ *   U(h, r)   = (F_1 + F_2 + .. + F_N) / (double)N, the additions in ascending n starting from 0.0
+ * U is symmetric and lies in [0, 1]; U(h, h) = min(len(h), N) / N; an empty hypothesis has U = 0 with everything, itself included.
+ * With weights w (doubles; finite), over the n_hyp valid hypotheses of the set:
+ *   expected[i] = sum_j w_j U(h_i, h_j) in ascending j, self included, from 0.0: one multiply then one add per step, never an fma
+ *   best        = the index of the largest expected value, the lower index among equals (-1 when n_hyp = 0)
+ *   order[rank_i] = i with rank_i = #{j : expected[j] > expected[i], or expected[j] == expected[i] and j < i}
+ * Every operation is integer or a single IEEE double operation in this order: a host implementation that follows it agrees bit for bit.
+ * An index >= n_hyp gets expected = -1.0, follows the valid ones in `order` by ascending index, and its rows and columns of util are 0.0.
+ * Two sources of hypotheses (all pointers are DEVICE memory: kernel arguments are frozen into a captured graph):
+ *   explicit    tok != NULL: tok [sets][K][ldl] int32, len [sets][K] clamped to [0, L], n_hyp [sets] clamped to [0, K], w [sets][K] or
+ *               NULL = uniform, w_j = 1.0 / (double)n_hyp;
+ *   sample log  tok == NULL: set s owns columns s*K .. s*K+K-1 of log_tok [L][sets * K], the token log mtn_sample_rows writes; a
+ *               hypothesis is its column's tokens before the first `eos`, the first L - 1 tokens without one (the cut
+ *               mtn_amd/decode.py sample_decode_many makes); n_hyp = K; len, n_hyp and ldl are not read; w as above.
+ * One launch, one workgroup per set, fixed reduction order, no float atomics: two launches give the same bits, and a set's outputs do not
+ * depend on what other sets share the launch.  util [sets][K][K] (U of every pair) is optional.
+ * MTN_ERR_ARG (nothing is launched): a null required buffer, sets < 1, K outside 1..16, L outside 1..128, N outside 1..4, ldl < L with
+ * explicit hypotheses. */
+#define MTN_MBR_MAX_HYP 16
+typedef struct {
+    int sets, K, L, N; long ldl;
+    const int* tok; const int* len; const int* n_hyp;             /* device: explicit hypotheses, or tok = NULL */
+    const double* w;                                              /* device: [sets][K], or NULL */
+    const int* log_tok; int eos;                                  /* device: [L][sets * K], the sample log */
+    double* expected; int* best; int* order;                      /* device: [sets][K], [sets], [sets][K] */
+    double* util;                                                 /* device: [sets][K][K], or NULL */
+} mtn_mbr_args;
+int mtn_mbr_select(const mtn_mbr_args* args /* host */, void* stream);
 /* Generator (mtn.py:62-69) at inference: out[row][c] = x[row][c] - logsumexp(x[row][0..V-1]) over logit rows x [rows, V] (row
  * strides ldx / ldo; out may be x).  The logits themselves are one mtn_gemm (x W^T + b, fp32 out). */
 int mtn_log_softmax_rows(const float* x, int rows, int V, long ldx, float* out, long ldo, void* stream);

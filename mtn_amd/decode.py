@@ -714,7 +714,7 @@ class MegaDecodeSession(DecodeSession):
             return None
         return None if self._log_views[6][0] else self._log_views
 
-    def sample_log(self, start, seed, keys, params, no_repeat_ngram=0, repetition_penalty=1.0):
+    def sample_log(self, start, seed, keys, params, no_repeat_ngram=0, repetition_penalty=1.0, mbr=0):
         """A whole sampling search for every row of the session as ONE graph replay: max_len x [persistent decode step, generator,
         mtn_sample_rows (csrc/sample.hip)] — no row heads, no hypothesis bookkeeping: every row starts at <sos>, draws its next token on the
         device and keeps its own cache slots (identity ancestors).  seed and keys enter through one small pinned block (kernel arguments are
@@ -722,7 +722,10 @@ class MegaDecodeSession(DecodeSession):
         (max_len, rows), is copied out at the end and the host synchronises once.  ``params``: the keyword arguments of ops.sample_args.
         With a constraint on, one csrc/constrain.hip launch per token rewrites the rows before the draw; a row's history is its own column of
         the token log (no parents).
-        Returns the three host views, or None after a poll timeout (timed_out() tells)."""
+        ``mbr`` = N > 0: minimum-Bayes-risk selection of order N (csrc/mbr.hip) is the LAST node of the graph — dialogue d's ``width`` rows
+        are set d, read from the token log in device memory; its outputs are copied out next to the log, and the host still synchronises once.
+        Returns the three host views (with mbr two more: expected utilities (D, width) and order (D, width)), or None after a poll timeout
+        (timed_out() tells)."""
         import ctypes as C
         import numpy as np
         from . import lib as L
@@ -731,7 +734,8 @@ class MegaDecodeSession(DecodeSession):
         W, Lm = self._W, self.max_len
         ngram, theta = int(no_repeat_ngram), float(repetition_penalty)
         constrained = ngram > 0 or theta != 1.0
-        key = (start,) + tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in params.items())) + (ngram, theta)
+        mbr = int(mbr)
+        key = (start,) + tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in params.items())) + (ngram, theta, mbr)
         if getattr(self, "_sample_key", None) != key:
             dev = self._x.device
             # [seed (int64) | keys (W int64) | step (W int32)]: the pinned image the host fills per search, and its device copy
@@ -748,6 +752,14 @@ class MegaDecodeSession(DecodeSession):
             self._slog_host = torch.zeros(3, Lm, W, dtype=torch.int32).pin_memory()
             hl = self._slog_host.numpy()
             self._slog_views = (hl[0], hl[1].view(np.float32), hl[2].view(np.float32))
+            if mbr:
+                # [expected (W float64) | order (W int32) | best (D int32)]: the selection's outputs in one block -> one copy
+                D = self.D
+                self._smbr = torch.zeros(12 * W + 4 * D, device=dev, dtype=torch.uint8)
+                self._smbr_host = torch.zeros(12 * W + 4 * D, dtype=torch.uint8).pin_memory()
+                hm = self._smbr_host.numpy()
+                self._smbr_views = (hm[:8 * W].view(np.float64).reshape(D, W // D), hm[8 * W:12 * W].view(np.int32).reshape(D, W // D))
+                mbr_out = (self._smbr[:8 * W].view(torch.float64), self._smbr[12 * W:].view(torch.int32), self._smbr[8 * W:12 * W].view(torch.int32))
             s0, p0 = self._sstate, self._devblk.data_ptr()
             log = (self._slog[0], self._slog[1].view(torch.float32), self._slog[2].view(torch.float32))
 
@@ -760,6 +772,9 @@ class MegaDecodeSession(DecodeSession):
                         ops.constrain_rows(logp, ngram, theta, log_tok=self._slog[0], step=s0[8 + 8 * W:].view(torch.int32), width=1, rows_per_step=1)
                     ops.sample_rows(logp, s0[:8].view(torch.int64), s0[8:8 + 8 * W].view(torch.int64), s0[8 + 8 * W:].view(torch.int32), log,
                                     tokens=p0, pos=p0 + self._off_pos, anc=p0 + self._off_anc, **params)
+                if mbr:
+                    ops.mbr_select(mbr, log_tok=self._slog[0], sets=self.D, eos=params["eos"], out=mbr_out)
+                    self._smbr_host.copy_(self._smbr, non_blocking=True)
                 self._slog_host.copy_(self._slog, non_blocking=True)
 
             self._h_seed[0], self._h_keys[:] = 0, 0
@@ -781,7 +796,7 @@ class MegaDecodeSession(DecodeSession):
         torch.cuda.current_stream().synchronize()
         if self.timed_out():                 # the log is garbage: the caller sees timed_out() and falls back
             return None
-        return self._slog_views
+        return self._slog_views + self._smbr_views if mbr else self._slog_views
 
     def timed_out(self) -> bool:
         """True if a poll of any step since the session was built (or last recovered) timed out: the results since then are garbage."""
@@ -1388,7 +1403,8 @@ def _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_
 
 
 def sample_decode_many(model, batch, max_len, start, eos, pad, *, samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, keys=None,
-                       banned=(), min_len=1, penalty=0.0, use_graph=True, kv_cache=None, trace=None, no_repeat_ngram=0, repetition_penalty=1.0):
+                       banned=(), min_len=1, penalty=0.0, use_graph=True, kv_cache=None, trace=None, no_repeat_ngram=0, repetition_penalty=1.0,
+                       mbr=0):
     """Stochastic decoding of a Batch of D dialogues x ``samples`` draws each (temperature / top-k / nucleus; include/mtn_hip.h
     mtn_sample_rows defines the filters).  Row d * samples + s draws with the random stream of key keys[d] * samples + s (keys: 0..D-1
     by default) under ``seed``: a pure function of (seed, key, position), so a dialogue's samples do not depend on what it is batched with.
@@ -1401,11 +1417,17 @@ def sample_decode_many(model, batch, max_len, start, eos, pad, *, samples=1, tem
     (max_len, rows), of this search.
     no_repeat_ngram / repetition_penalty (off by default; include/mtn_hip.h mtn_constrain_rows): every row's log-probabilities are
     rewritten from that row's own draws before the filters see them, so no sample repeats an N-gram before its <eos>; the logged
-    log-probabilities, and so the scores, are the penalised ones under a penalty."""
+    log-probabilities, and so the scores, are the penalised ones under a penalty.
+    ``mbr`` = N in 1..4 (0: off): minimum-Bayes-risk selection of n-gram order N with uniform weights — the right ones for draws from the
+    model — over each dialogue's samples (include/mtn_hip.h mtn_mbr_select; at most 16 samples, max_len <= 128): one more launch, the last
+    node of the captured search on the persistent step, once after the token loop elsewhere; it changes no draw.  The result is then per
+    dialogue its (tokens, score, expected utility) triples, largest expected utility first (equal ones in sample order)."""
     ngram, theta, _ = _constraints(no_repeat_ngram, repetition_penalty)
-    D, S = batch.query.size(0), int(samples)
+    D, S, mbr = batch.query.size(0), int(samples), int(mbr)
     if S < 1 or len(banned) > 4:
         raise ValueError("sample_decode_many: samples >= 1, at most 4 banned tokens")
+    if not 0 <= mbr <= ops.MBR_MAX_ORDER or (mbr and (S > ops.MBR_MAX_HYP or max_len > ops.MBR_MAX_LEN)):
+        raise ValueError("sample_decode_many: mbr in 0..4; with it at most 16 samples and max_len <= 128")
     if temperature == 0:
         temperature, top_k = 1.0, 1
     if not (temperature > 0 and top_k >= 0 and 0 < top_p <= 1):
@@ -1417,10 +1439,10 @@ def sample_decode_many(model, batch, max_len, start, eos, pad, *, samples=1, tem
     params = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), banned=tuple(int(b) for b in banned), eos=int(eos),
                   min_len=int(min_len))
     auto = kv_cache is None
-    log = _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, auto, ngram, theta)
+    log = _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, auto, ngram, theta, mbr)
     if log is None:                  # a poll of the persistent step timed out: the launch-per-sublayer pass
-        log = _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, False, ngram, theta)
-    tok, lp, u = log
+        log = _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, False, ngram, theta, mbr)
+    tok, lp, u = log[:3]
     if trace is not None:
         trace.append((list(row_keys), tok.copy(), lp.copy(), u.copy()))
     results = []
@@ -1432,17 +1454,22 @@ def sample_decode_many(model, batch, max_len, start, eos, pad, *, samples=1, tem
             n = col.index(eos) if eos in col else len(col) - 1
             used = n + 1 if eos in col else n
             hyps.append((col[:n], float(lp[:used, r].astype("float64").sum()) + penalty * (n + 1)))
-        results.append(sorted(hyps, key=lambda h: -h[1]))
+        if mbr:                      # the kernel cut the same columns at the same places: its order and expected utilities, as they are
+            expected, order = log[3], log[4]
+            results.append([hyps[int(j)] + (float(expected[d, j]),) for j in order[d]])
+        else:
+            results.append(sorted(hyps, key=lambda h: -h[1]))
     return results
 
 
-def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, mega, ngram=0, theta=1.0):
-    """The step log (tokens, log-probabilities, u — numpy, (max_len, rows)) of one sampling search, or None after a persistent-step timeout."""
+def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, mega, ngram=0, theta=1.0, mbr=0):
+    """The step log (tokens, log-probabilities, u — numpy, (max_len, rows)) of one sampling search, or None after a persistent-step timeout.
+    With ``mbr`` the selection's expected utilities and order, each (D, S), follow the log."""
     import numpy as np
     sess = _session(model, batch, max_len, S, pad, use_graph, max_len > KV_CACHE_FROM if kv_cache is None else kv_cache, select=None,
                     mega=mega and use_graph, mode="sample")
     if isinstance(sess, MegaDecodeSession):
-        log = sess.sample_log(start, seed, row_keys, params, ngram, theta)
+        log = sess.sample_log(start, seed, row_keys, params, ngram, theta, mbr)
         if _mega_failed(sess):
             return None
         return log
@@ -1466,7 +1493,57 @@ def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params,
         ops.sample_rows(sess.logp, seed_t, keys_t, step_t, log, **params)      # the session's rows ARE d * S + s: all of them live
         for p, t in zip(prefixes, log[0][l].tolist()):
             p.append(int(t))
+    if mbr:                          # once, after the token loop, on the device log
+        expected, _, order, _ = ops.mbr_select(mbr, log_tok=log[0], sets=D, eos=params["eos"])
+        return tuple(t.cpu().numpy() for t in log + (expected, order))
     return tuple(t.cpu().numpy() for t in log)
+
+
+def mbr_weights(scores, temperature=1.0):
+    """The ``score`` weights of mbr_rerank: w_j = exp((s_j - max s) / temperature) / sum, float64, the sum in ascending j."""
+    import math
+    top = max(scores)
+    e = [math.exp((float(v) - float(top)) / float(temperature)) for v in scores]
+    z = 0.0
+    for v in e:
+        z = z + v
+    return [v / z for v in e]
+
+
+def mbr_rerank(lists, ngram, weights="uniform", temperature=1.0, device=None):
+    """Minimum-Bayes-risk re-ranking of hypothesis lists (include/mtn_hip.h mtn_mbr_select; csrc/mbr.hip): ``lists[d]`` is dialogue d's
+    list of (tokens, score) pairs, as sample_decode_many and the beam search return them (at most 16 of at most 128 tokens; lists may
+    differ in length or be empty).  One launch for all dialogues.  ``ngram``: the maximum n-gram order, 1..4.  ``weights``: "uniform", or
+    "score" — w_j = exp((s_j - max s) / temperature) / sum over the list, computed here in float64.
+    Returns per dialogue its (tokens, score, expected utility) triples, largest expected utility first, equal ones in input order."""
+    import numpy as np
+    lists = [list(l) for l in lists]
+    if weights not in ("uniform", "score"):
+        raise ValueError("mbr_rerank: weights is 'uniform' or 'score'")
+    if not float(temperature) > 0:
+        raise ValueError("mbr_rerank: temperature > 0")
+    if not 1 <= int(ngram) <= ops.MBR_MAX_ORDER:
+        raise ValueError("mbr_rerank: the n-gram order is in 1..4")
+    if any(len(l) > ops.MBR_MAX_HYP for l in lists) or any(len(h[0]) > ops.MBR_MAX_LEN for l in lists for h in l):
+        raise ValueError("mbr_rerank: at most 16 hypotheses per list, of at most 128 tokens")
+    if not lists:
+        return []
+    S, K = len(lists), max(1, max(len(l) for l in lists))
+    Lh = max([1] + [len(h[0]) for l in lists for h in l])
+    tok, length = np.zeros((S, K, Lh), dtype=np.int32), np.zeros((S, K), dtype=np.int32)
+    n_hyp = np.asarray([len(l) for l in lists], dtype=np.int32)
+    w = np.zeros((S, K), dtype=np.float64) if weights == "score" else None
+    for d, l in enumerate(lists):
+        for k, h in enumerate(l):
+            tok[d, k, :len(h[0])] = np.asarray(h[0], dtype=np.int64).astype(np.int32)
+            length[d, k] = len(h[0])
+        if w is not None and l:
+            w[d, :len(l)] = mbr_weights([h[1] for h in l], temperature)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+    expected, _, order, _ = ops.mbr_select(ngram, tok=up(tok), length=up(length), n_hyp=up(n_hyp), w=up(w))
+    expected, order = expected.cpu().numpy(), order.cpu().numpy()
+    return [[(l[j][0], l[j][1], float(expected[d, j])) for j in order[d, :len(l)].tolist()] for d, l in enumerate(lists)]
 
 
 def score_candidates(model, batch, candidates, start, eos, pad, *, penalty=0.0, max_len=None, width=None, use_graph=True):

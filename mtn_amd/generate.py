@@ -33,6 +33,7 @@ from collections import OrderedDict
 FRAME_STEP = 64          # bucket grid: frame counts of every feature type rounded up to a multiple of this
 TEXT_STEP = 32           # ... history, question and caption lengths to a multiple of this
 MAX_SAMPLES = 16         # --samples: the samples of a QA ride in one search (decode.MegaDecodeSession.MAX_W rows)
+MBR_MAX_HYP, MBR_MAX_LEN = 16, 128       # --mbr: hypotheses per QA and tokens per hypothesis (include/mtn_hip.h mtn_mbr_select)
 LAUNCH_PASS_D = 8        # dialogues per search where the persistent decode step does not apply (launch-per-sublayer pass)
 
 # the reference train.py's defaults (train.py:57-96) for fields a conf may lack (confs written by older versions)
@@ -91,6 +92,12 @@ def parse(argv=None):
                    help="one weight >= 0 per member, --model's first (normalised to sum 1; default: uniform)")
     p.add_argument("--ensemble-mode", default="prob", choices=["prob", "logprob"],
                    help="prob: log of the weighted mean probability; logprob: weighted mean log-probability, renormalised")
+    # minimum-Bayes-risk selection (sample, beam_search): the answer is the hypothesis that agrees most, in n-grams, with the others (csrc/mbr.hip)
+    p.add_argument("--mbr", default=0, type=int,
+                   help="sample / beam_search: answer with the hypothesis of the largest expected n-gram utility, n-grams up to this order (1..4; 0 = off)")
+    p.add_argument("--mbr-weights", default=None, choices=["uniform", "score"],
+                   help="mbr: weight of a hypothesis in the expectation: uniform (default), or score = softmax of the hypotheses' scores")
+    p.add_argument("--mbr-temperature", default=None, type=float, help="mbr: temperature of the score weights (> 0; default 1)")
     p.add_argument("--no-buckets", action="store_true",
                    help="one QA per search at its own padded shape, as the reference decodes (baseline / debugging)")
     args = p.parse_args(argv)
@@ -124,6 +131,21 @@ def parse(argv=None):
         p.error("--beam-groups must divide --beam (%d groups for a beam of %d)" % (args.beam_groups, args.beam))
     elif args.diversity_penalty > 0 and args.beam_groups == 1:
         p.error("--diversity-penalty needs --beam-groups > 1 (one group is the plain beam search)")
+    if not 0 <= args.mbr <= 4:
+        p.error("--mbr must be in [0, 4]")
+    if args.mbr_temperature is not None and not args.mbr_temperature > 0:
+        p.error("--mbr-temperature must be > 0")
+    if args.mbr == 0 and (args.mbr_weights is not None or args.mbr_temperature is not None):
+        p.error("--mbr-weights / --mbr-temperature go with --mbr > 0")
+    if args.mbr > 0:
+        if args.decode_style not in ("sample", "beam_search"):
+            p.error("--mbr selects among several hypotheses: it goes with --decode-style sample or beam_search")
+        if args.decode_style == "beam_search" and args.nbest > MBR_MAX_HYP:
+            p.error("--mbr takes at most %d hypotheses: --nbest must be <= %d" % (MBR_MAX_HYP, MBR_MAX_HYP))
+        if args.maxlen > MBR_MAX_LEN:
+            p.error("--mbr takes hypotheses of at most %d tokens: --maxlen must be <= %d" % (MBR_MAX_LEN, MBR_MAX_LEN))
+    args.mbr_weights = args.mbr_weights or "uniform"
+    args.mbr_temperature = 1.0 if args.mbr_temperature is None else args.mbr_temperature
     n_members = 1 + len(args.ensemble_model)
     if args.ensemble_conf and len(args.ensemble_conf) != len(args.ensemble_model):
         p.error("--ensemble-conf takes one conf per --ensemble-model entry (%d given for %d)" % (len(args.ensemble_conf), len(args.ensemble_model)))
@@ -288,9 +310,10 @@ def greedy_text(ys, vocablist, eos):
     return detokenize(list(ys)[1:], vocablist, eos)
 
 
-def build_result(original, undisclosed_only, answers, scores=None):
+def build_result(original, undisclosed_only, answers, scores=None, mbr=None):
     """{'dialogs': [{'image_id', 'dialog'}]} in file order (generate.py:27-38): every turn, or the last one with undisclosed-only;
-    ``answers[qa_id]`` replaces the answer of the qa_id-th output turn; ``scores[qa_id]`` (--decode-style score) becomes its "scores"."""
+    ``answers[qa_id]`` replaces the answer of the qa_id-th output turn; ``scores[qa_id]`` (--decode-style score) becomes its "scores",
+    ``mbr[qa_id]`` (--mbr) its "mbr"."""
     dialogs, qa = [], 0
     for dialog in original["dialogs"]:
         out = copy.deepcopy(dialog["dialog"][-1:] if undisclosed_only else dialog["dialog"])
@@ -298,6 +321,8 @@ def build_result(original, undisclosed_only, answers, scores=None):
             turn["answer"] = answers[qa]
             if scores is not None:
                 turn["scores"] = scores[qa]
+            if mbr is not None:
+                turn["mbr"] = mbr[qa]
             qa += 1
         dialogs.append({"image_id": dialog["image_id"], "dialog": out})
     return {"dialogs": dialogs}
@@ -383,13 +408,16 @@ def candidate_order(scores):
 
 # ---------------------------------------------------------------------------------------------------------------- decoding
 def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=None, scoring=None,
-                    no_repeat_ngram=0, repetition_penalty=1.0, min_len=1, beam_groups=1, diversity_penalty=0.0):
+                    no_repeat_ngram=0, repetition_penalty=1.0, min_len=1, beam_groups=1, diversity_penalty=0.0, mbr=0, mbr_weights="uniform",
+                    mbr_temperature=1.0):
     """Run the planned searches; returns per qa_id the (n-best list, best score) of beam search, the greedy token list, the
     samples' (tokens, score) pairs, best first (``sampling``: samples / temperature / top_k / top_p / seed), or the candidates'
     score dicts in input order (``scoring``: tokens = per qa_id its candidates' token lists, max_len, width — one session shape
     per bucket).  ``no_repeat_ngram`` / ``repetition_penalty`` constrain beam search, greedy and sample (decode.py; off by default);
     ``min_len``: the shortest response beam search and sample may finish.  ``beam_groups`` / ``diversity_penalty``: diverse beam search
-    (beam search only; decode.beam_search_decode_many)."""
+    (beam search only; decode.beam_search_decode_many).  ``mbr`` = N > 0 (beam search and sample): every QA's hypotheses — the n-best list cut
+    to ``nbest``, or the samples — come back as (tokens, score, expected utility) triples in minimum-Bayes-risk order of n-gram order N
+    (decode.mbr_rerank; uniform weights over samples ride inside the search, decode.sample_decode_many's ``mbr``)."""
     from . import decode
     from .data_handler import make_batch
     from .decode import beam_search_decode_many, greedy_decode_many
@@ -406,10 +434,16 @@ def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, 
         if decode_style == "beam_search":
             res = beam_search_decode_many(model, batch, maxlen, sos, unk, eos, pad, beam=beam, penalty=penalty, nbest=nbest, min_len=min_len,
                                           beam_groups=int(beam_groups), diversity_penalty=float(diversity_penalty), **con)
+            if mbr:                  # plain, diverse and ensemble searches hand back the same list: one launch re-ranks the whole search's
+                ranked = decode.mbr_rerank([r[0][:nbest] for r in res], mbr, weights=mbr_weights, temperature=mbr_temperature)
+                res = [(t, r[1]) for t, r in zip(ranked, res)]
         elif decode_style == "sample":
             # keys = qa_ids: a QA's random stream is the same in any bucket, at any D, with --no-buckets
+            in_search = dict(mbr=int(mbr)) if mbr and mbr_weights == "uniform" else {}
             res = decode.sample_decode_many(model, batch, maxlen, sos, eos, pad, keys=ids, banned=(unk, pad, sos), min_len=min_len, penalty=penalty,
-                                            **sampling, **con)
+                                            **sampling, **con, **in_search)
+            if mbr and not in_search:
+                res = decode.mbr_rerank(res, mbr, weights=mbr_weights, temperature=mbr_temperature)
         elif decode_style == "score":
             # (a padding copy of the last QA rides with one candidate: its rows are dropped)
             cands = [scoring["tokens"][i] if k < n_real else scoring["tokens"][i][:1] for k, i in enumerate(ids)]
@@ -423,7 +457,7 @@ def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, 
 
 def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0, nbest=5, decode_style="greedy", undisclosed_only=False,
                       ref_data=None, dialogues_per_search=0, buckets=True, sampling=None, candidates=None, no_repeat_ngram=0,
-                      repetition_penalty=1.0, min_len=1, beam_groups=1, diversity_penalty=0.0):
+                      repetition_penalty=1.0, min_len=1, beam_groups=1, diversity_penalty=0.0, mbr=0, mbr_weights="uniform", mbr_temperature=1.0):
     """Decode every QA of ``data`` (data_handler.load) and return the reference's result dict, logging the reference's
     QS / REF / HYP lines per QA.  decode_style "score" generates nothing: every QA's ``candidates`` (load_candidates' ``spec``; its
     own answer without one) are scored and logged as CAND lines, best first; the answer is the best-scoring candidate, every turn
@@ -431,7 +465,16 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
     are scored whole: ``maxlen`` does not cut them.  ``no_repeat_ngram`` / ``repetition_penalty`` / ``min_len``: as decode_searches
     (a scoring run takes no constraints: ValueError).  ``beam_groups`` / ``diversity_penalty``: diverse beam search, for decode_style
     "beam_search" alone (any other style with groups > 1 or a penalty > 0: ValueError); the n-best lines and the result are as for the
-    plain beam search, and so is the number of dialogues per search."""
+    plain beam search, and so is the number of dialogues per search.  ``mbr`` = N in 1..4 (decode_style "beam_search" or "sample";
+    ValueError elsewhere): minimum-Bayes-risk selection — the HYP lines come in its order, so HYP[1] is the answer, one line
+    "MBR: e_1 e_2 ..." (the expected utilities, in that order) follows them, and every turn gains "mbr"; ``mbr_weights`` "uniform" or
+    "score" with ``mbr_temperature`` > 0 (decode.mbr_rerank)."""
+    if not 0 <= int(mbr) <= 4 or mbr_weights not in ("uniform", "score") or not mbr_temperature > 0:
+        raise ValueError("generate_response: mbr in 0..4, mbr_weights 'uniform' or 'score', mbr_temperature > 0")
+    if mbr and decode_style not in ("beam_search", "sample"):
+        raise ValueError("generate_response: mbr selects among several hypotheses: decode_style beam_search or sample")
+    if mbr and (maxlen > MBR_MAX_LEN or (decode_style == "beam_search" and nbest > MBR_MAX_HYP)):
+        raise ValueError("generate_response: mbr takes at most %d hypotheses of at most %d tokens" % (MBR_MAX_HYP, MBR_MAX_LEN))
     if decode_style == "score" and (no_repeat_ngram != 0 or repetition_penalty != 1.0):
         raise ValueError("generate_response: no_repeat_ngram / repetition_penalty constrain a search; a scoring run has none")
     if decode_style == "beam_search":
@@ -462,11 +505,13 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
     n_buckets = len({(tuple(s[2][0]),) + tuple(s[2][1:]) for s in searches})
     logging.info("%d QAs in %d searches over %d padded shapes", len(lens), len(searches), n_buckets)
     vids = {it[1]: it[0] for it in data["dialogs"]}
+    mbr_kw = dict(mbr=int(mbr), mbr_weights=mbr_weights, mbr_temperature=float(mbr_temperature)) if mbr else {}
     res = decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=sampling,
                           scoring=scoring, no_repeat_ngram=no_repeat_ngram, repetition_penalty=repetition_penalty, min_len=min_len,
-                          beam_groups=beam_groups, diversity_penalty=diversity_penalty)
+                          beam_groups=beam_groups, diversity_penalty=diversity_penalty, **mbr_kw)
     answers = []
     scores = [] if decode_style == "score" else None
+    mbr_out = [] if mbr else None
     qa_id = 0
     for idx, dialog in enumerate(data["original"]["dialogs"]):
         vid = dialog["image_id"]
@@ -491,11 +536,17 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
             elif decode_style in ("beam_search", "sample"):
                 pred_out = r[0] if decode_style == "beam_search" else r          # (sample: every draw is logged, best first)
                 hyp = ""
+                shown = []
                 for n in range(min(nbest, len(pred_out)) if decode_style == "beam_search" else len(pred_out)):
                     hypstr = detokenize(pred_out[n][0], vocablist, eos)
                     logging.info("HYP[%d]: %s  ( %f )" % (n + 1, hypstr, pred_out[n][1]))
                     if n == 0:
                         hyp = hypstr
+                    if mbr:
+                        shown.append(dict(hypothesis=hypstr, score=pred_out[n][1], expected=pred_out[n][2]))
+                if mbr:
+                    logging.info("MBR: " + " ".join(repr(h["expected"]) for h in shown))
+                    mbr_out.append(shown)
             else:
                 hyp = greedy_text(r, vocablist, eos)
                 logging.info("HYP: {}".format(hyp))
@@ -510,7 +561,7 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
         if m["n_ranked"]:
             logging.info("MRR = %.6f  R@1 = %.6f  R@5 = %.6f  R@10 = %.6f  mean rank = %.4f  ( %d QAs with gt_index )"
                          % (m["mrr"], m["r1"], m["r5"], m["r10"], m["mean_rank"], m["n_ranked"]))
-    return build_result(data["original"], undisclosed_only, answers, scores)
+    return build_result(data["original"], undisclosed_only, answers, scores, mbr_out)
 
 
 def main(argv=None):
@@ -573,7 +624,8 @@ def main(argv=None):
                                sampling=dict(samples=args.samples, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                                              seed=args.sample_seed), candidates=args.candidates,
                                no_repeat_ngram=args.no_repeat_ngram, repetition_penalty=args.repetition_penalty, min_len=args.min_length,
-                               beam_groups=args.beam_groups, diversity_penalty=args.diversity_penalty)
+                               beam_groups=args.beam_groups, diversity_penalty=args.diversity_penalty, mbr=args.mbr,
+                               mbr_weights=args.mbr_weights, mbr_temperature=args.mbr_temperature)
     wall = time.time() - start_time
     n_qa = len(test_data["dialogs"])
     logging.info("----------------")

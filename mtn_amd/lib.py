@@ -182,6 +182,12 @@ class EnsembleArgs(C.Structure):
                 ("w", C.c_float * 8), ("out", C.c_void_p), ("ldo", C.c_long)]
 
 
+class MbrArgs(C.Structure):
+    _fields_ = [("sets", C.c_int), ("K", C.c_int), ("L", C.c_int), ("N", C.c_int), ("ldl", C.c_long), ("tok", C.c_void_p), ("len", C.c_void_p),
+                ("n_hyp", C.c_void_p), ("w", C.c_void_p), ("log_tok", C.c_void_p), ("eos", C.c_int), ("expected", C.c_void_p),
+                ("best", C.c_void_p), ("order", C.c_void_p), ("util", C.c_void_p)]
+
+
 class LnFinalizeDesc(C.Structure):
     _fields_ = [("partial", C.c_void_p), ("nparts", C.c_int), ("d", C.c_int), ("da2", C.c_void_p), ("db2", C.c_void_p)]
 
@@ -234,6 +240,7 @@ SYMBOLS = {
     "mtn_score_rows": (C.c_int, [C.POINTER(ScoreArgs), _P]),
     "mtn_constrain_rows": (C.c_int, [C.POINTER(ConstrainArgs), _P]),
     "mtn_ensemble_rows": (C.c_int, [C.POINTER(EnsembleArgs), _P]),
+    "mtn_mbr_select": (C.c_int, [C.POINTER(MbrArgs), _P]),
     "mtn_debug_hold_cus": (C.c_int, [C.c_int, C.c_int, C.c_int, _P]),
     "mtn_gemm_tt_table_aux": (C.c_int, [C.c_int, C.c_int, C.POINTER(GemmProblem), C.POINTER(TtAux), _P]),
     "mtn_layernorm_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P]),

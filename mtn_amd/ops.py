@@ -1132,6 +1132,74 @@ def ensemble_rows(xs, weights=None, mode="prob", out=None):
     return out
 
 
+MBR_MAX_HYP, MBR_MAX_LEN, MBR_MAX_ORDER = 16, 128, 4        # include/mtn_hip.h MTN_MBR_MAX_HYP; csrc/mbr.hip MBR_MAX_L
+
+
+def mbr_select(ngram, *, tok=None, length=None, n_hyp=None, w=None, log_tok=None, sets=None, eos=None, out=None, util=False):
+    """Minimum-Bayes-risk selection over sets of at most 16 hypotheses (csrc/mbr.hip; include/mtn_hip.h mtn_mbr_select gives the
+    definition), ``ngram`` = the maximum n-gram order N in 1..4.  Hypotheses, explicit: ``tok`` (sets, K, >= L) int32 with unit token
+    stride, ``length`` (sets, K) and ``n_hyp`` (sets,) int32, ``w`` (sets, K) float64 or None for uniform weights.  Or the token log of a
+    sampling search: ``log_tok`` (L, sets * K) int32 with ``sets`` and ``eos`` — set s is columns s * K .. s * K + K - 1, cut at the first
+    <eos>.  Everything lives on the device.  ``out`` = (expected (sets, K) float64, best (sets,) int32, order (sets, K) int32), allocated
+    when None; ``util``: True allocates, or a (sets, K, K) float64 tensor receives, the utility of every pair.
+    Returns (expected, best, order, util or None)."""
+    ngram = int(ngram)
+    if not 1 <= ngram <= MBR_MAX_ORDER:
+        raise ValueError("mbr_select: the n-gram order is in 1..4")
+    a = L.MbrArgs()
+    if tok is not None:
+        if length is None or n_hyp is None or log_tok is not None:
+            raise ValueError("mbr_select: explicit hypotheses need length and n_hyp; one source of hypotheses")
+        _require_cuda(tok, length, n_hyp)
+        if (tok.dim() != 3 or tok.dtype != torch.int32 or tok.numel() == 0 or (tok.size(2) > 1 and tok.stride(2) != 1)
+                or tok.stride(1) < tok.size(2) or tok.stride(0) != tok.size(1) * tok.stride(1)):
+            raise ValueError("mbr_select: tok int32 (sets, K, L), non-empty, with unit token stride and rows of one stride")
+        S, K, Lh = tok.shape
+        if length.dtype != torch.int32 or tuple(length.shape) != (S, K) or not length.is_contiguous() or n_hyp.dtype != torch.int32 \
+                or n_hyp.numel() != S or not n_hyp.is_contiguous():
+            raise ValueError("mbr_select: length int32 (sets, K) and n_hyp int32 (sets,), contiguous")
+        a.tok, a.len, a.n_hyp, a.ldl = tok.data_ptr(), length.data_ptr(), n_hyp.data_ptr(), tok.stride(1)
+        dev = tok.device
+    else:
+        if log_tok is None or sets is None or eos is None:
+            raise ValueError("mbr_select: a source of hypotheses is required (tok + length + n_hyp, or log_tok + sets + eos)")
+        _require_cuda(log_tok)
+        S = int(sets)
+        if log_tok.dim() != 2 or log_tok.dtype != torch.int32 or not log_tok.is_contiguous() or S < 1 or log_tok.size(1) < S or log_tok.size(1) % S:
+            raise ValueError("mbr_select: the token log is int32, contiguous (L, sets * K)")
+        Lh, K = log_tok.size(0), log_tok.size(1) // S
+        a.log_tok, a.eos = log_tok.data_ptr(), int(eos)
+        dev = log_tok.device
+    if not 1 <= K <= MBR_MAX_HYP or not 1 <= Lh <= MBR_MAX_LEN:
+        raise ValueError("mbr_select: at most 16 hypotheses per set, of at most 128 tokens")
+    if w is not None:
+        _require_cuda(w)
+        if w.dtype != torch.float64 or tuple(w.shape) != (S, K) or not w.is_contiguous():
+            raise ValueError("mbr_select: w float64 (sets, K), contiguous")
+        a.w = w.data_ptr()
+    if out is None:
+        out = (torch.empty(S, K, device=dev, dtype=torch.float64), torch.empty(S, dtype=torch.int32, device=dev),
+               torch.empty(S, K, dtype=torch.int32, device=dev))
+    expected, best, order = out
+    _require_cuda(expected, best, order)
+    if (expected.dtype != torch.float64 or best.dtype != torch.int32 or order.dtype != torch.int32 or expected.numel() != S * K or best.numel() != S
+            or order.numel() != S * K or not all(t.is_contiguous() for t in out)):
+        raise ValueError("mbr_select: out = (expected float64 (sets, K), best int32 (sets,), order int32 (sets, K)), contiguous")
+    if util is True:
+        util = torch.empty(S, K, K, device=dev, dtype=torch.float64)
+    elif util is False:
+        util = None
+    if util is not None:
+        _require_cuda(util)
+        if util.dtype != torch.float64 or util.numel() != S * K * K or not util.is_contiguous():
+            raise ValueError("mbr_select: util float64 (sets, K, K), contiguous")
+        a.util = util.data_ptr()
+    a.sets, a.K, a.L, a.N = S, K, Lh, ngram
+    a.expected, a.best, a.order = expected.data_ptr(), best.data_ptr(), order.data_ptr()
+    L.check(L.load().mtn_mbr_select(C.byref(a), L.stream_ptr()))
+    return expected, best, order, util
+
+
 # ------------------------------------------------------------------------------------------ memory K/V, ahead of the layers
 def project_memories(items, lp_dtype, outs=None, n_now=None, order=None):
     """K|V projections (mtn.py:257-258) of CONSTANT memories for many sublayers at once: items = [(mem_lp (B,m,d) compute dtype,

@@ -8,7 +8,9 @@ captures graphs per QA shape), greedy, and --decode-style sample (1 and 4 sample
 (generate.py's flags of the same names; off by default).  --ensemble M decodes with M random-init copies of the model (seeds 1..M)
 combined on the device (decode.Ensemble; --ensemble-mode prob|logprob) and records the dialogues per search auto_dialogues chose.
 --beam sets the beam of the beam-search settings (default 5; their keys carry it), --beam-groups / --diversity-penalty make them diverse
-beam searches (generate.py's flags of the same names; greedy and sample are not touched).
+beam searches (generate.py's flags of the same names; greedy and sample are not touched).  --mbr N / --mbr-weights add minimum-Bayes-risk
+selection of order N to the beam-search and sample settings (generate.py's flags; greedy is not touched), --samples sets the draws per QA
+of the multi-sample setting (default 4; its key carries it).
 
     python tools/generate_bench.py [--dialogs 1710] [--no-buckets-qas 300]
 """
@@ -57,6 +59,9 @@ def main():
     ap.add_argument("--beam", type=int, default=5)
     ap.add_argument("--beam-groups", type=int, default=1)
     ap.add_argument("--diversity-penalty", type=float, default=0.0)
+    ap.add_argument("--mbr", type=int, default=0)
+    ap.add_argument("--mbr-weights", default="uniform", choices=["uniform", "score"])
+    ap.add_argument("--samples", type=int, default=4)
     ap.add_argument("--ensemble", type=int, default=1, help="members: this many random-init copies with different seeds (1 = a plain model)")
     ap.add_argument("--ensemble-mode", default="prob", choices=["prob", "logprob"])
     a = ap.parse_args()
@@ -94,7 +99,7 @@ def main():
         lens = G.qa_lengths(data)
         n = len(lens)
         out = {"qas": n, "buckets": len({G.bucket_key(l) for l in lens}), "maxlen": a.maxlen, "beam": a.beam,
-               "beam_groups": a.beam_groups, "diversity_penalty": a.diversity_penalty,
+               "beam_groups": a.beam_groups, "diversity_penalty": a.diversity_penalty, "mbr": a.mbr, "mbr_weights": a.mbr_weights if a.mbr else None,
                "no_repeat_ngram": a.no_repeat_ngram, "repetition_penalty": a.repetition_penalty, "ensemble": a.ensemble, "ensemble_mode": a.ensemble_mode if a.ensemble > 1 else None}
         per_search = lambda width: sorted({len(ids) for ids, _, _ in G.plan_searches(
             lens, lambda shape: G.auto_dialogues(model, dev, shape, a.maxlen, width))})
@@ -106,6 +111,8 @@ def main():
             torch.cuda.synchronize()
             t0 = time.time()
             div = dict(beam_groups=a.beam_groups, diversity_penalty=a.diversity_penalty) if style == "beam_search" else {}
+            if a.mbr and style in ("beam_search", "sample"):
+                div.update(mbr=a.mbr, mbr_weights=a.mbr_weights)
             G.generate_response(model, d, corpus, vocab, maxlen=a.maxlen, beam=a.beam, penalty=1.0, nbest=5, decode_style=style,
                                 undisclosed_only=True, buckets=buckets, sampling=sampling, no_repeat_ngram=a.no_repeat_ngram,
                                 repetition_penalty=a.repetition_penalty, **div)
@@ -125,8 +132,8 @@ def main():
             out["greedy_buckets_auto_d_again"] = timed("greedy", True)
             out["sample1_buckets_auto_d"] = timed("sample", True, sampling=dict(smp, samples=1))
             out["sample1_plain_buckets_auto_d"] = timed("sample", True, sampling=dict(samples=1))
-            timed("sample", True, sampling=dict(smp, samples=4))
-            out["sample4_buckets_auto_d"] = timed("sample", True, sampling=dict(smp, samples=4))
+            timed("sample", True, sampling=dict(smp, samples=a.samples))
+            out["sample%d_buckets_auto_d" % a.samples] = timed("sample", True, sampling=dict(smp, samples=a.samples))
             out["sample_over_greedy"] = round(out["sample1_buckets_auto_d"]["qa_per_s"] / out["greedy_buckets_auto_d_again"]["qa_per_s"], 3)
         if "no_buckets" in styles:
             out["beam%d_no_buckets" % a.beam] = timed("beam_search", False, min(n, a.no_buckets_qas))
