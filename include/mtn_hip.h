@@ -45,7 +45,7 @@ const char* mtn_last_error(void);
  * compute-unit count and bounds its polls in time (see there).
  * 114: mtn_assemble_tokens_desc gained the trailing field `row_len` (NULL = no cut; a zeroed struct keeps meaning that).
  * 115: new entry point mtn_sample_rows.  116: new entry point mtn_score_rows.  117: new entry point mtn_constrain_rows.
- * 121: new entry point mtn_mbr_select. */
+ * 121: new entry point mtn_mbr_select.  122: new entry points mtn_eval_metrics and mtn_eval_workspace_bytes. */
 int mtn_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -769,6 +769,48 @@ typedef struct {
     double* util;                                                 /* device: [sets][K][K], or NULL */
 } mtn_mbr_args;
 int mtn_mbr_select(const mtn_mbr_args* args /* host */, void* stream);
+/* Corpus metrics of generated responses (version 122; csrc/eval.hip): BLEU-1..4, ROUGE-L and CIDEr of Q items on the device.  The reference
+ * scores with coco-caption on the host (run.sh stage 4, utils/evaluate.py); these are the numbers it prints, without METEOR, on token ids.
+ * Item q is one hypothesis h of hyp_len[q] tokens (0..L) and n_ref[q] references (1..R, R <= MTN_EVAL_MAX_REF) of ref_len[q][r] tokens
+ * (0..L), L <= 128.  Tokens compare as int32, any value; nothing is an index.  For orders n = 1..4: count_s(g) = the occurrences of the
+ * n-gram g in sentence s, c_n(s) = max(len(s) - n + 1, 0).
+ *   BLEU, per item (integers)   guess_n = c_n(h);  match_n = sum over distinct g of min(count_h(g), max_r count_r(g));
+ *                               closest = the reference length l that minimises (|l - len(h)|, l): ties go to the shorter.
+ *   BLEU, corpus                G_n, M_n, T = sum len(h), C = sum closest as int64 sums over the items;  p = 1;  for n = 1..4:
+ *                               p = p * (M_n + 1e-15) / (G_n + 1e-9), Bleu_n = p^(1/n);  ratio = (T + 1e-15) / (C + 1e-9); where ratio < 1
+ *                               every Bleu_n is multiplied by exp(1 - 1/ratio).
+ *   ROUGE-L, per item           LCS(h, r) the longest-common-subsequence length;  P = max_r LCS / len(h), Rc = max_r LCS / len(r) (an empty
+ *                               sentence gives 0), beta = 1.2;  score = (1 + beta^2) P Rc / (Rc + beta^2 P), 0 where P = 0 or Rc = 0.
+ *                               The corpus value is the mean.
+ *   document frequency          df(g) = the number of ITEMS whose reference set holds g at least once (not the number of references);
+ *                               exact: two different n-grams never share a count.
+ *   CIDEr, per item             idf(g) = ln Q - ln max(1, df(g)) (a hypothesis n-gram no reference holds has df 0);  v_s(g) = count_s(g) idf(g);
+ *                               |s|_n = sqrt(sum_g v_s(g)^2) over the n-grams of order n;  sim_n(h, r) = sum over g in h of min(v_h(g), v_r(g)) v_r(g),
+ *                               divided by |h|_n |r|_n where both are non-zero, then multiplied by exp(-(len h - len r)^2 / (2 * 6^2));
+ *                               score = 10 * (1/4) sum_n (1/n_ref) sum_r sim_n(h, r).  The corpus value is the mean.  Q = 1, or a corpus in
+ *                               which every n-gram occurs in every item, gives exactly 0.
+ * Layout (all pointers DEVICE memory): hyp [Q][ldl], hyp_len [Q], ref [Q][R][ldl], ref_len [Q][R], n_ref [Q]; lengths are clamped to [0, L]
+ * and n_ref to [1, R]; what lies past a length or past n_ref is never read as a token.  Outputs: stats [Q][10] = guess_1..4, match_1..4,
+ * len(h), closest;  rouge [Q], cider [Q];  corpus [8] = Bleu_1..4, ROUGE_L, CIDEr, T, C;  optional df_of_ref [Q][R][L][4] = the df of the
+ * n-gram that starts at each reference position, 0 where there is none.
+ * workspace: the document-frequency table, owned by the caller — 16-byte aligned, at least mtn_eval_workspace_bytes(Q, R, L) bytes (0 for
+ * sizes mtn_eval_metrics refuses); its contents before and after a call mean nothing.
+ * Four launches on `stream` (clear, table, per item, reduction), no grid barrier.  Integers are exact; all floating point is double with
+ * every sum across lanes in a fixed order; the table counts with integer atomics only: two calls give the same bytes, and an item's stats
+ * and rouge do not depend on the other items (its cider does, through df and Q).
+ * MTN_ERR_ARG (nothing is launched): a null required buffer, Q < 1, R outside 1..8, L outside 1..128, ldl < L, Q R L > 2^28, a workspace
+ * that is null, misaligned or too small. */
+#define MTN_EVAL_MAX_REF 8
+typedef struct {
+    int Q, R, L; long ldl;
+    const int* hyp; const int* hyp_len;                           /* device: [Q][ldl], [Q] */
+    const int* ref; const int* ref_len; const int* n_ref;         /* device: [Q][R][ldl], [Q][R], [Q] */
+    void* workspace; long workspace_bytes;                        /* device */
+    int* stats; double* rouge; double* cider; double* corpus;     /* device: [Q][10], [Q], [Q], [8] */
+    int* df_of_ref;                                               /* device: [Q][R][L][4], or NULL */
+} mtn_eval_args;
+long mtn_eval_workspace_bytes(int Q, int R, int L);
+int mtn_eval_metrics(const mtn_eval_args* args /* host */, void* stream);
 /* Generator (mtn.py:62-69) at inference: out[row][c] = x[row][c] - logsumexp(x[row][0..V-1]) over logit rows x [rows, V] (row
  * strides ldx / ldo; out may be x).  The logits themselves are one mtn_gemm (x W^T + b, fp32 out). */
 int mtn_log_softmax_rows(const float* x, int rows, int V, long ldx, float* out, long ldo, void* stream);

@@ -1546,6 +1546,48 @@ def mbr_rerank(lists, ngram, weights="uniform", temperature=1.0, device=None):
     return [[(l[j][0], l[j][1], float(expected[d, j])) for j in order[d, :len(l)].tolist()] for d, l in enumerate(lists)]
 
 
+EVAL_NAMES = ("Bleu_1", "Bleu_2", "Bleu_3", "Bleu_4", "ROUGE_L", "CIDEr")
+
+
+def evaluate_responses(hyps, refs, device=None):
+    """BLEU-1..4, ROUGE-L and CIDEr of generated responses on the device (include/mtn_hip.h mtn_eval_metrics; csrc/eval.hip).  ``hyps[q]`` is
+    item q's hypothesis as a list of token ids, ``refs[q]`` the list of its 1..8 references (token-id lists); any ids, sentences of at
+    most 128 tokens (ValueError names the first item that breaks a bound).  The whole corpus is one call whatever its size: the document
+    frequencies are the corpus'.  Returns dict(Bleu_1 .. Bleu_4, ROUGE_L, CIDEr: floats; hyp_len, ref_len: the corpus sums of hypothesis
+    and closest reference lengths; stats (Q, 10) int32, rouge (Q,), cider (Q,) float64 numpy arrays, per item)."""
+    import numpy as np
+    hyps, refs = [list(h) for h in hyps], [[list(r) for r in rs] for rs in refs]
+    if len(hyps) != len(refs):
+        raise ValueError("evaluate_responses: one reference list per hypothesis (%d and %d)" % (len(hyps), len(refs)))
+    if not hyps:
+        raise ValueError("evaluate_responses: nothing to evaluate")
+    for q, (h, rs) in enumerate(zip(hyps, refs)):
+        if not 1 <= len(rs) <= ops.EVAL_MAX_REF:
+            raise ValueError("evaluate_responses: item %d has %d references (1..%d)" % (q, len(rs), ops.EVAL_MAX_REF))
+        if len(h) > ops.EVAL_MAX_LEN or any(len(r) > ops.EVAL_MAX_LEN for r in rs):
+            raise ValueError("evaluate_responses: item %d holds a sentence of more than %d tokens" % (q, ops.EVAL_MAX_LEN))
+    Q, R = len(hyps), max(len(rs) for rs in refs)
+    Lh = max([1] + [len(h) for h in hyps] + [len(r) for rs in refs for r in rs])
+    tok = np.zeros((Q, R + 1, Lh), dtype=np.int32)                # row R of an item: its hypothesis
+    length = np.zeros((Q, R + 1), dtype=np.int32)
+    for q, (h, rs) in enumerate(zip(hyps, refs)):
+        for r, s in enumerate(rs + [None] * (R - len(rs)) + [h]):
+            if s is not None:
+                tok[q, r, :len(s)] = np.asarray(s, dtype=np.int64).astype(np.int32)
+                length[q, r] = len(s)
+    if device is None:                                           # (without a GPU the tensors stay on the host and ops.eval_metrics refuses them)
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cpu"
+    dev = torch.device(device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    ref_tok, hyp_tok = up(tok[:, :R]), up(tok[:, R])
+    n_ref = up(np.asarray([len(rs) for rs in refs], dtype=np.int32))
+    stats, rouge, cider, corpus, _ = ops.eval_metrics(hyp_tok, up(length[:, R]), ref_tok, up(length[:, :R]), n_ref)
+    corpus = corpus.cpu().numpy()
+    out = {k: float(v) for k, v in zip(EVAL_NAMES, corpus[:6])}
+    out.update(hyp_len=int(corpus[6]), ref_len=int(corpus[7]), stats=stats.cpu().numpy(), rouge=rouge.cpu().numpy(), cider=cider.cpu().numpy())
+    return out
+
+
 def score_candidates(model, batch, candidates, start, eos, pad, *, penalty=0.0, max_len=None, width=None, use_graph=True):
     """Teacher-forced log-likelihood of GIVEN responses: candidates[d] is a list of token-id lists (no <sos> / <eos>; empty lists
     allowed; counts may differ) for dialogue d of ``batch``.  The encoder side and the auto-encoder chains run once per call

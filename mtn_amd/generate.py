@@ -98,6 +98,11 @@ def parse(argv=None):
     p.add_argument("--mbr-weights", default=None, choices=["uniform", "score"],
                    help="mbr: weight of a hypothesis in the expectation: uniform (default), or score = softmax of the hypotheses' scores")
     p.add_argument("--mbr-temperature", default=None, type=float, help="mbr: temperature of the score weights (> 0; default 1)")
+    # scoring of the generated answers on the device (mtn_amd.evaluate; csrc/eval.hip): run.sh's stage 4 inside stage 3
+    p.add_argument("--evaluate", action="store_true",
+                   help="score the answers written to the result JSON: Bleu_1..4, ROUGE_L, CIDEr against the test set's own answers, or with "
+                        "--undisclosed-only 1 against the last answers of --labeled-test FILE")
+    p.add_argument("--stopwords", default="", type=str, help="evaluate: stopword file applied to hypotheses and references (utils/stopword_filter.py's format)")
     p.add_argument("--no-buckets", action="store_true",
                    help="one QA per search at its own padded shape, as the reference decodes (baseline / debugging)")
     args = p.parse_args(argv)
@@ -144,6 +149,13 @@ def parse(argv=None):
             p.error("--mbr takes at most %d hypotheses: --nbest must be <= %d" % (MBR_MAX_HYP, MBR_MAX_HYP))
         if args.maxlen > MBR_MAX_LEN:
             p.error("--mbr takes hypotheses of at most %d tokens: --maxlen must be <= %d" % (MBR_MAX_LEN, MBR_MAX_LEN))
+    if args.stopwords and not args.evaluate:
+        p.error("--stopwords goes with --evaluate")
+    if args.evaluate:
+        if args.decode_style == "score":
+            p.error("--evaluate scores generated answers: --decode-style score generates nothing")
+        if args.undisclosed_only and not args.labeled_test:
+            p.error("--evaluate with --undisclosed-only 1 needs --labeled-test FILE: the test set's own last answers are undisclosed")
     args.mbr_weights = args.mbr_weights or "uniform"
     args.mbr_temperature = 1.0 if args.mbr_temperature is None else args.mbr_temperature
     n_members = 1 + len(args.ensemble_model)
@@ -564,10 +576,35 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
     return build_result(data["original"], undisclosed_only, answers, scores, mbr_out)
 
 
+def evaluate_result(result, reference, last=False, stopwords=""):
+    """--evaluate: the answers of ``result`` (build_result's dict) scored against ``reference`` (a labelled dialogue dict; ``last``: its last
+    answers, for an undisclosed-only result) by mtn_amd.evaluate on the device.  Logs the six '%s: %.3f' lines and returns what becomes the
+    result JSON's top-level "eval"."""
+    from . import evaluate as E
+    sw = E.StopwordFilter(stopwords) if stopwords else None
+    _, res = E.score_files(result, reference, last=last, stopwords=sw)
+    for line in E.format_lines(res):
+        logging.info(line)
+    return E.summary(res)
+
+
+def write_result(args, result, original, labeled_test=None):
+    """The tail of a run: with --evaluate the scores (logged, and the result's "eval"), then the result JSON where --output names one."""
+    if args.evaluate:
+        undisclosed = bool(args.undisclosed_only)
+        result["eval"] = evaluate_result(result, labeled_test if undisclosed else original, last=undisclosed, stopwords=args.stopwords)
+    if args.output:
+        logging.info("writing results to " + args.output)
+        with open(args.output, "w") as f:
+            json.dump(result, f, indent=4)
+    return result
+
+
 def main(argv=None):
     args = parse(argv)
     for arg in vars(args):
-        print("{}={}".format(arg, getattr(args, arg)))
+        if args.evaluate or arg not in ("evaluate", "stopwords"):           # (a run without --evaluate prints what it always did)
+            print("{}={}".format(arg, getattr(args, arg)))
     logging.basicConfig(level=logging.DEBUG if args.verbose >= 1 else logging.INFO, format="%(asctime)s %(levelname)s: %(message)s")
     import torch
     from . import data_handler as dh
@@ -631,10 +668,7 @@ def main(argv=None):
     logging.info("----------------")
     logging.info("wall time = %f" % wall)
     logging.info("%d QAs, %.1f QA/s" % (n_qa, n_qa / max(wall, 1e-9)))
-    if args.output:
-        logging.info("writing results to " + args.output)
-        with open(args.output, "w") as f:
-            json.dump(result, f, indent=4)
+    write_result(args, result, test_data["original"], labeled_test)
     logging.info("done")
     return result
 

@@ -188,6 +188,12 @@ class MbrArgs(C.Structure):
                 ("best", C.c_void_p), ("order", C.c_void_p), ("util", C.c_void_p)]
 
 
+class EvalArgs(C.Structure):
+    _fields_ = [("Q", C.c_int), ("R", C.c_int), ("L", C.c_int), ("ldl", C.c_long), ("hyp", C.c_void_p), ("hyp_len", C.c_void_p),
+                ("ref", C.c_void_p), ("ref_len", C.c_void_p), ("n_ref", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
+                ("stats", C.c_void_p), ("rouge", C.c_void_p), ("cider", C.c_void_p), ("corpus", C.c_void_p), ("df_of_ref", C.c_void_p)]
+
+
 class LnFinalizeDesc(C.Structure):
     _fields_ = [("partial", C.c_void_p), ("nparts", C.c_int), ("d", C.c_int), ("da2", C.c_void_p), ("db2", C.c_void_p)]
 
@@ -241,6 +247,8 @@ SYMBOLS = {
     "mtn_constrain_rows": (C.c_int, [C.POINTER(ConstrainArgs), _P]),
     "mtn_ensemble_rows": (C.c_int, [C.POINTER(EnsembleArgs), _P]),
     "mtn_mbr_select": (C.c_int, [C.POINTER(MbrArgs), _P]),
+    "mtn_eval_metrics": (C.c_int, [C.POINTER(EvalArgs), _P]),
+    "mtn_eval_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int]),
     "mtn_debug_hold_cus": (C.c_int, [C.c_int, C.c_int, C.c_int, _P]),
     "mtn_gemm_tt_table_aux": (C.c_int, [C.c_int, C.c_int, C.POINTER(GemmProblem), C.POINTER(TtAux), _P]),
     "mtn_layernorm_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P]),

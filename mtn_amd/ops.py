@@ -1200,6 +1200,71 @@ def mbr_select(ngram, *, tok=None, length=None, n_hyp=None, w=None, log_tok=None
     return expected, best, order, util
 
 
+EVAL_MAX_REF, EVAL_MAX_LEN = 8, 128                        # include/mtn_hip.h MTN_EVAL_MAX_REF; csrc/eval.hip EV_L
+
+
+def eval_workspace_bytes(Q, R, Lh):
+    """Bytes of the document-frequency table eval_metrics needs for Q items of R references of Lh tokens (0 for sizes it refuses)."""
+    return int(L.load().mtn_eval_workspace_bytes(int(Q), int(R), int(Lh)))
+
+
+def eval_metrics(hyp, hyp_len, ref, ref_len, n_ref, *, workspace=None, out=None, df_of_ref=False):
+    """BLEU-1..4, ROUGE-L and CIDEr of Q items on the device (csrc/eval.hip; include/mtn_hip.h mtn_eval_metrics gives the definition).
+    ``hyp`` (Q, >= Lh) and ``ref`` (Q, R, >= Lh) int32 with unit token stride and ONE row stride (ldl) between them, ``hyp_len`` (Q,),
+    ``ref_len`` (Q, R) and ``n_ref`` (Q,) int32, contiguous; R <= 8, Lh <= 128.  Everything lives on the device.  ``workspace``: a uint8
+    tensor of at least eval_workspace_bytes(Q, R, Lh) bytes, allocated when None.  ``out`` = (stats (Q, 10) int32, rouge (Q,) float64,
+    cider (Q,) float64, corpus (8,) float64), allocated when None; ``df_of_ref``: True allocates, or a (Q, R, Lh, 4) int32 tensor
+    receives, the document frequency of the n-gram at every reference position.
+    Returns (stats, rouge, cider, corpus, df_of_ref or None); corpus = Bleu_1..4, ROUGE_L, CIDEr, sum len(h), sum closest."""
+    _require_cuda(hyp, hyp_len, ref, ref_len, n_ref)
+    if (ref.dim() != 3 or ref.dtype != torch.int32 or ref.numel() == 0 or (ref.size(2) > 1 and ref.stride(2) != 1)
+            or ref.stride(1) < ref.size(2) or ref.stride(0) != ref.size(1) * ref.stride(1)):
+        raise ValueError("eval_metrics: ref int32 (Q, R, L), non-empty, with unit token stride and rows of one stride")
+    Q, R, Lh = ref.shape
+    ldl = ref.stride(1)
+    if (hyp.dim() != 2 or hyp.dtype != torch.int32 or tuple(hyp.shape) != (Q, Lh) or (Lh > 1 and hyp.stride(1) != 1)
+            or (Q > 1 and hyp.stride(0) != ldl)):
+        raise ValueError("eval_metrics: hyp int32 (Q, L) with unit token stride and the row stride of ref")
+    if not 1 <= R <= EVAL_MAX_REF or not 1 <= Lh <= EVAL_MAX_LEN:
+        raise ValueError("eval_metrics: at most 8 references per item, sentences of at most 128 tokens")
+    for t, shape, name in ((hyp_len, (Q,), "hyp_len (Q,)"), (ref_len, (Q, R), "ref_len (Q, R)"), (n_ref, (Q,), "n_ref (Q,)")):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("eval_metrics: %s int32, contiguous" % name)
+    need = eval_workspace_bytes(Q, R, Lh)
+    if need <= 0:
+        raise ValueError("eval_metrics: Q * R * L is at most 2^28")
+    dev = ref.device
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    _require_cuda(workspace)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 16:
+        raise ValueError("eval_metrics: workspace uint8, contiguous, 16-byte aligned, at least eval_workspace_bytes(Q, R, L) = %d bytes" % need)
+    if out is None:
+        out = (torch.empty(Q, 10, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.float64, device=dev),
+               torch.empty(Q, dtype=torch.float64, device=dev), torch.empty(8, dtype=torch.float64, device=dev))
+    stats, rouge, cider, corpus = out
+    _require_cuda(stats, rouge, cider, corpus)
+    if (stats.dtype != torch.int32 or tuple(stats.shape) != (Q, 10) or any(t.dtype != torch.float64 for t in (rouge, cider, corpus))
+            or rouge.numel() != Q or cider.numel() != Q or corpus.numel() != 8 or not all(t.is_contiguous() for t in out)):
+        raise ValueError("eval_metrics: out = (stats int32 (Q, 10), rouge float64 (Q,), cider float64 (Q,), corpus float64 (8,)), contiguous")
+    if df_of_ref is True:
+        df_of_ref = torch.empty(Q, R, Lh, 4, dtype=torch.int32, device=dev)
+    elif df_of_ref is False:
+        df_of_ref = None
+    a = L.EvalArgs()
+    if df_of_ref is not None:
+        _require_cuda(df_of_ref)
+        if df_of_ref.dtype != torch.int32 or tuple(df_of_ref.shape) != (Q, R, Lh, 4) or not df_of_ref.is_contiguous():
+            raise ValueError("eval_metrics: df_of_ref int32 (Q, R, L, 4), contiguous")
+        a.df_of_ref = df_of_ref.data_ptr()
+    a.Q, a.R, a.L, a.ldl = Q, R, Lh, ldl
+    a.hyp, a.hyp_len, a.ref, a.ref_len, a.n_ref = hyp.data_ptr(), hyp_len.data_ptr(), ref.data_ptr(), ref_len.data_ptr(), n_ref.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    a.stats, a.rouge, a.cider, a.corpus = stats.data_ptr(), rouge.data_ptr(), cider.data_ptr(), corpus.data_ptr()
+    L.check(L.load().mtn_eval_metrics(C.byref(a), L.stream_ptr()))
+    return stats, rouge, cider, corpus, df_of_ref
+
+
 # ------------------------------------------------------------------------------------------ memory K/V, ahead of the layers
 def project_memories(items, lp_dtype, outs=None, n_now=None, order=None):
     """K|V projections (mtn.py:257-258) of CONSTANT memories for many sublayers at once: items = [(mem_lp (B,m,d) compute dtype,

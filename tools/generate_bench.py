@@ -10,7 +10,9 @@ combined on the device (decode.Ensemble; --ensemble-mode prob|logprob) and recor
 --beam sets the beam of the beam-search settings (default 5; their keys carry it), --beam-groups / --diversity-penalty make them diverse
 beam searches (generate.py's flags of the same names; greedy and sample are not touched).  --mbr N / --mbr-weights add minimum-Bayes-risk
 selection of order N to the beam-search and sample settings (generate.py's flags; greedy is not touched), --samples sets the draws per QA
-of the multi-sample setting (default 4; its key carries it).
+of the multi-sample setting (default 4; its key carries it).  --evaluate scores every pass's answers on the device against a labelled copy
+of the corpus (random last answers of the same lengths), as generate.py --evaluate does after decoding: the time of a pass then holds the
+scoring, and the run records the six corpus values of its last pass.
 
     python tools/generate_bench.py [--dialogs 1710] [--no-buckets-qas 300]
 """
@@ -62,6 +64,7 @@ def main():
     ap.add_argument("--mbr", type=int, default=0)
     ap.add_argument("--mbr-weights", default="uniform", choices=["uniform", "score"])
     ap.add_argument("--samples", type=int, default=4)
+    ap.add_argument("--evaluate", action="store_true", help="score every pass's answers (generate.py --evaluate) inside its time")
     ap.add_argument("--ensemble", type=int, default=1, help="members: this many random-init copies with different seeds (1 = a plain model)")
     ap.add_argument("--ensemble-mode", default="prob", choices=["prob", "logprob"])
     a = ap.parse_args()
@@ -96,6 +99,12 @@ def main():
             from mtn_amd.decode import Ensemble
             model = Ensemble(members, mode=a.ensemble_mode)
         corpus = dh.DeviceCorpus(data, dev)
+        labelled, scores = None, {}
+        if a.evaluate:                                           # a labelled copy: every undisclosed last answer gets a random sentence
+            rs = np.random.RandomState(7)
+            labelled = json.loads(json.dumps(data["original"]))
+            for d in labelled["dialogs"]:
+                d["dialog"][-1]["answer"] = " ".join("w%d" % i for i in rs.randint(0, 3000, size=rs.randint(5, 17)))
         lens = G.qa_lengths(data)
         n = len(lens)
         out = {"qas": n, "buckets": len({G.bucket_key(l) for l in lens}), "maxlen": a.maxlen, "beam": a.beam,
@@ -113,9 +122,12 @@ def main():
             div = dict(beam_groups=a.beam_groups, diversity_penalty=a.diversity_penalty) if style == "beam_search" else {}
             if a.mbr and style in ("beam_search", "sample"):
                 div.update(mbr=a.mbr, mbr_weights=a.mbr_weights)
-            G.generate_response(model, d, corpus, vocab, maxlen=a.maxlen, beam=a.beam, penalty=1.0, nbest=5, decode_style=style,
+            res = G.generate_response(model, d, corpus, vocab, maxlen=a.maxlen, beam=a.beam, penalty=1.0, nbest=5, decode_style=style,
                                 undisclosed_only=True, buckets=buckets, sampling=sampling, no_repeat_ngram=a.no_repeat_ngram,
                                 repetition_penalty=a.repetition_penalty, **div)
+            if labelled is not None:
+                scores.clear()
+                scores.update(G.evaluate_result(res, labelled, last=True))
             torch.cuda.synchronize()
             dt = time.time() - t0
             return {"qas": len(d["dialogs"]), "seconds": round(dt, 2), "qa_per_s": round(len(d["dialogs"]) / dt, 1)}
@@ -139,6 +151,8 @@ def main():
             out["beam%d_no_buckets" % a.beam] = timed("beam_search", False, min(n, a.no_buckets_qas))
         from mtn_amd.decode import MegaDecodeSession
         out["persistent_step_fallbacks"] = MegaDecodeSession.FALLBACKS
+        if a.evaluate:
+            out["evaluate"] = dict(scores)
     print(json.dumps(out))
 
 
