@@ -510,6 +510,49 @@ typedef struct {
 int mtn_losshead_fwd(const mtn_losshead_args* args, void* stream);
 int mtn_losshead_bwd(int dtype, const mtn_losshead_args* args, void* stream);
 
+/* Loss head with teacher soft targets (version 123; csrc/distill.hip): word-level knowledge distillation.  Every field of
+ * mtn_losshead_args keeps its meaning.  teacher[s] is a device matrix [rows[s]][ldq[s]] of float, 16-byte aligned, ldq >= V and
+ * ldq % 4 == 0 (columns V..ldq-1 are never read), NULL = segment s has no teacher.  A teacher row holds log-probabilities or logits:
+ * it is normalised here, as mtn_ensemble_rows normalises its members.  With z the student row, q the teacher row, t the target,
+ * KL_ls and td the loss head's (the lone-<pad> quirk included), scale = coef[s] / *norm[s], T = temperature:
+ *   a_j = z_j / T, b_j = q_j / T, pS = softmax(a), pT = softmax(b)
+ *   kd      = sum_j pT_j (log pT_j - log pS_j); a column with q_j = -inf contributes exactly 0 (no 0 * inf).  Evaluated with the row
+ *             maxima m_a, m_b taken out: kd = sum_j e_j ((b_j - m_b) - (a_j - m_a)) / sum_j e_j - log sum_j e_j + log sum_j exp(a_j - m_a),
+ *             e_j = exp(b_j - m_b)
+ *   kd      = 0 on every row whose target is <pad> (the teacher row is not read); on the quirk row (a lone <pad> at a segment's row 0)
+ *             the hard part is the loss head's KL_ls as on any live row
+ *   rowloss = scale [(1 - alpha) KL_ls + alpha T^2 kd]          rowkd (optional, [sum rows]) = kd, unscaled
+ *   lse     = the T = 1 log-sum-exp of z, as mtn_losshead_fwd writes it
+ *   bwd:      dlogits_j = *gloss scale [(1 - alpha)(softmax_j(z) sum(td) - td_j) + alpha T (pS_j - pT_j)], the second term 0 on
+ *             <pad>-target rows; columns V..ldd-1 are +0.0.  Reads lse (of the forward call), logits and the teacher rows.
+ * A segment with teacher == NULL, and every segment when alpha == 0, never reads a teacher and applies no (1 - alpha) factor: lse,
+ * rowloss and dlogits are those of mtn_losshead_fwd / _bwd on the same inputs bit for bit, rowkd is 0.
+ * MTN_ERR_ARG, nothing launched: whatever mtn_losshead_fwd / _bwd refuse; alpha outside [0, 1] or not finite; temperature <= 0 or not
+ * finite; ldq < V, ldq % 4 != 0 or a misaligned pointer on a segment with a teacher.  A teacher row without a finite entry is NOT
+ * checked (device memory): its kd and gradient are NaN. */
+typedef struct {
+    int n_seg;
+    int rows[MTN_LOSSHEAD_MAX_SEG];
+    const long* target[MTN_LOSSHEAD_MAX_SEG];
+    const float* norm[MTN_LOSSHEAD_MAX_SEG];
+    float coef[MTN_LOSSHEAD_MAX_SEG];
+    int V, ldz, pad;
+    float smoothing;
+    const float* logits;
+    float* lse;
+    float* rowloss;
+    const float* gloss; /* backward: device scalar dL/dloss */
+    void* dlogits;
+    int ldd;
+    const float* teacher[MTN_LOSSHEAD_MAX_SEG];
+    long ldq[MTN_LOSSHEAD_MAX_SEG];
+    float alpha;
+    float temperature;
+    float* rowkd; /* optional */
+} mtn_distill_args;
+int mtn_distill_fwd(const mtn_distill_args* args, void* stream);
+int mtn_distill_bwd(int dtype, const mtn_distill_args* args, void* stream);
+
 /* Transposed compute-dtype weight copies (operand of dX = dY W on the LDS-DMA GEMM path): for each descriptor the
  * [rows, cols] matrix at src+off is written as [cols, rows] at dst+dst_off (v111: the copies have a compact buffer of
  * their own — by default only the W_o^T matrices are kept).  `descs_device` is a DEVICE array (built once),

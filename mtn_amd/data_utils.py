@@ -14,6 +14,7 @@ from typing import List, Optional
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import lib as L
 
@@ -289,8 +290,9 @@ class SimpleLossCompute:
     def __init__(self, generator, ae_generator, criterion, opt=None, l=1.0, sync=True, grad_sync=None, fused=True):
         self.generator, self.ae_generator, self.criterion = generator, ae_generator, criterion
         self.opt, self.l, self.sync, self.grad_sync, self.fused = opt, l, sync, grad_sync, fused
+        self.last_kd_sum = None
 
-    def _fused_loss(self, x, y, norm, ae_x, ae_y, ae_norm):
+    def _fused_loss(self, x, y, norm, ae_x, ae_y, ae_norm, teacher_logp=None, alpha=0.0, temperature=1.0):
         """Generator + log-softmax + label-smoothed KL + weighted sum as the fused HIP loss head (ops.GeneratorLossFn).
         Returns None when the fused path does not apply (CPU tensors, un-flattened model, vocab not a multiple of 8,
         foreign criterion): the caller then composes the same value from PyTorch ops."""
@@ -317,14 +319,39 @@ class SimpleLossCompute:
                     pad=self.criterion.padding_idx, smoothing=self.criterion.smoothing, lp_dtype=fused[0]["lp_dtype"],
                     queue=fused[0].get("queue"))
         spec["norms"] = [n.detach().float().reshape(1) for n in spec["norms"]]
-        return ops.GeneratorLossFn.apply(spec, *xs)
+        if teacher_logp is not None:            # the main stream only: the auto-encoder streams keep the plain loss
+            spec["teacher"] = [teacher_logp.reshape(-1, teacher_logp.size(-1))] + [None] * (len(xs) - 1)
+            spec["alpha"], spec["temperature"] = float(alpha), float(temperature)
+        out = ops.GeneratorLossFn.apply(spec, *xs)
+        self.last_kd_sum = spec.get("kd_sum")
+        return out
 
-    def loss(self, x, y, norm, ae_x=None, ae_y=None, ae_norm=None):
-        fused = self._fused_loss(x, y, norm, ae_x, ae_y, ae_norm) if self.fused else None
+    def loss(self, x, y, norm, ae_x=None, ae_y=None, ae_norm=None, teacher_logp=None, alpha=0.0, temperature=1.0):
+        """``teacher_logp``: (rows, V) fp32 teacher log-probabilities (or logits: they are normalised) for the main stream — word-level
+        knowledge distillation, loss = (1 - alpha) KL_ls + alpha T^2 KL(softmax(q / T) || softmax(z / T)) over the rows whose target is
+        not <pad>, both over ``norm`` (include/mtn_hip.h mtn_distill_args).  alpha == 0 is the plain loss.  ``last_kd_sum`` is left
+        holding the sum of the rows' KL (None without a teacher)."""
+        if teacher_logp is not None and not (0.0 <= float(alpha) <= 1.0 and 0.0 < float(temperature) < float("inf")):
+            raise ValueError("distillation: alpha in [0, 1] and a finite temperature > 0")
+        self.last_kd_sum = None
+        fused = self._fused_loss(x, y, norm, ae_x, ae_y, ae_norm, teacher_logp, alpha, temperature) if self.fused else None
         if fused is not None:
             return fused
+        if teacher_logp is not None and float(alpha) == 0.0:
+            teacher_logp = None                 # as the fused head: the teacher is not read, nothing is multiplied by (1 - alpha)
         out = self.generator(x)
         loss = self.criterion(out.reshape(-1, out.size(-1)), y.reshape(-1)) / norm.float()
+        if teacher_logp is not None:
+            # the composed form of the fused head's soft term: the generator's output is log_softmax(z), and log_softmax(logp / T) ==
+            # log_softmax(z / T) (the row's log-sum-exp is a common shift)
+            T = float(temperature)
+            logp = out.reshape(-1, out.size(-1))
+            live = (y.reshape(-1) != self.criterion.padding_idx)
+            q = teacher_logp.reshape(-1, teacher_logp.size(-1)).to(logp.dtype)
+            kd = F.kl_div(torch.log_softmax(logp / T, dim=-1), torch.softmax(q / T, dim=-1), reduction="none").sum(-1)
+            kd = torch.where(live, kd, torch.zeros_like(kd)).sum()
+            self.last_kd_sum = kd.detach()
+            loss = (1.0 - float(alpha)) * loss + float(alpha) * T * T * kd / norm.float()
         if ae_x is not None:
             xs = ae_x if isinstance(ae_x, (list, tuple)) else [ae_x]
             for i, ae_in in enumerate(xs):
@@ -336,8 +363,8 @@ class SimpleLossCompute:
                 loss = loss + self.l * self.criterion(ae_out.reshape(-1, ae_out.size(-1)), ae_y.reshape(-1)) / ae_norm.float()
         return loss
 
-    def __call__(self, x, y, norm, ae_x=None, ae_y=None, ae_norm=None):
-        loss = self.loss(x, y, norm, ae_x, ae_y, ae_norm)
+    def __call__(self, x, y, norm, ae_x=None, ae_y=None, ae_norm=None, teacher_logp=None, alpha=0.0, temperature=1.0):
+        loss = self.loss(x, y, norm, ae_x, ae_y, ae_norm, teacher_logp, alpha, temperature)
         if self.opt is not None:
             loss.backward()
             if self.grad_sync is not None:

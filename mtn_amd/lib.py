@@ -95,6 +95,11 @@ class LossHeadArgs(C.Structure):
                 ("gloss", C.c_void_p), ("dlogits", C.c_void_p), ("ldd", C.c_int)]
 
 
+class DistillHeadArgs(C.Structure):
+    _fields_ = LossHeadArgs._fields_ + [("teacher", C.c_void_p * 4), ("ldq", C.c_long * 4), ("alpha", C.c_float), ("temperature", C.c_float),
+                                        ("rowkd", C.c_void_p)]
+
+
 class TransposeDesc(C.Structure):
     _fields_ = [("off", C.c_long), ("rows", C.c_int), ("cols", C.c_int), ("tile_start", C.c_int), ("reserved", C.c_int), ("dst_off", C.c_long)]
 
@@ -287,6 +292,8 @@ SYMBOLS = {
     "mtn_dropout_bwd_to_lp": (C.c_int, [C.c_int, C.c_long, _P, Dropout, _P, _P]),
     "mtn_losshead_fwd": (C.c_int, [C.POINTER(LossHeadArgs), _P]),
     "mtn_losshead_bwd": (C.c_int, [C.c_int, C.POINTER(LossHeadArgs), _P]),
+    "mtn_distill_fwd": (C.c_int, [C.POINTER(DistillHeadArgs), _P]),
+    "mtn_distill_bwd": (C.c_int, [C.c_int, C.POINTER(DistillHeadArgs), _P]),
     "mtn_transpose_group": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
     "mtn_noam_tick": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, _P]),
     "mtn_adam_step": (C.c_int, [C.c_int, C.c_long, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P]),

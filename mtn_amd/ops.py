@@ -9,6 +9,7 @@ for device memory, streams and autograd bookkeeping only.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -1497,12 +1498,38 @@ class FeatureEncodeFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------ loss head
+def _distill_teachers(spec, rows, V, dev):
+    """spec["teacher"] checked against the streams: None when no stream has a teacher (the plain loss head runs), else the list."""
+    teachers = spec.get("teacher")
+    if teachers is None or all(q is None for q in teachers):
+        return None
+    if len(teachers) != len(rows):
+        raise ValueError("GeneratorLossFn: spec['teacher'] holds one entry (a tensor or None) per stream")
+    alpha, T = float(spec.get("alpha", 0.5)), float(spec.get("temperature", 1.0))
+    if not (0.0 <= alpha <= 1.0) or not (T > 0.0 and math.isfinite(T)):
+        raise ValueError("GeneratorLossFn: alpha in [0, 1] and a finite temperature > 0")
+    for q, r in zip(teachers, rows):
+        if q is None:
+            continue
+        if not (torch.is_tensor(q) and q.device == dev and q.dtype == torch.float32 and q.dim() == 2 and tuple(q.shape) == (r, V)
+                and q.stride(1) == 1 and q.stride(0) >= V and q.stride(0) % 4 == 0 and q.data_ptr() % 16 == 0):
+            raise ValueError("GeneratorLossFn: a teacher is an fp32 (rows, V) tensor on the student's device, unit column stride, row stride a "
+                             "multiple of 4, 16-byte aligned")
+        if q.requires_grad:
+            raise ValueError("GeneratorLossFn: teacher rows carry no gradient (detach them)")
+    return list(teachers)
+
+
 class GeneratorLossFn(torch.autograd.Function):
     """sum_i coef_i * KLDiv(log_softmax(x_i W_i^T + b_i), smooth(y_i)) / norm_i  — Generator (mtn.py:62-69) +
     LabelSmoothing (label_smoothing.py) + SimpleLossCompute's weighted sum (data_utils.py:133-144) as: one grouped cast,
     one grouped GEMM (logits), one row kernel (log-sum-exp + closed-form KL); backward: one row kernel (dlogits), two
     grouped GEMMs (dX, dW+db).  `spec`: targets, norms (device float scalars), coefs, gens [(w_lp, bias, grad_w, grad_b)],
-    vocab, pad, smoothing, lp_dtype.  Generator gradients are written to the flat gradient buffer (not returned)."""
+    vocab, pad, smoothing, lp_dtype.  Generator gradients are written to the flat gradient buffer (not returned).
+    Knowledge distillation: ``spec["teacher"]`` = per stream a (rows_i, V) fp32 device tensor of teacher logits / log-probabilities or
+    None, with ``spec["alpha"]`` and ``spec["temperature"]``.  With any teacher present the row kernels are mtn_distill_fwd / _bwd
+    (csrc/distill.hip; include/mtn_hip.h) in the place of the two loss-head calls, casts and GEMMs unchanged, and ``spec["kd_sum"]`` is
+    left holding the device scalar sum_rows kd; with none the calls are exactly the loss head's."""
 
     @staticmethod
     def forward(ctx, spec, *xs):
@@ -1552,7 +1579,8 @@ class GeneratorLossFn(torch.autograd.Function):
             p.bias, p.gate_scale, p.out_f32, p.ldc = bias.data_ptr(), 1.0, logits[o:].data_ptr(), V
             probs.append(p)
         gemm(code, probs)
-        A = L.LossHeadArgs()
+        teachers = _distill_teachers(spec, rows, V, dev)
+        A = L.LossHeadArgs() if teachers is None else L.DistillHeadArgs()
         A.n_seg = len(xs)
         norms = [n.float().reshape(1) if n.dtype != torch.float32 or n.dim() == 0 else n for n in spec["norms"]]
         targets = [t.contiguous().view(-1) for t in spec["targets"]]
@@ -1562,8 +1590,17 @@ class GeneratorLossFn(torch.autograd.Function):
         lse = torch.empty(R, device=dev, dtype=torch.float32)
         rowloss = torch.empty(R, device=dev, dtype=torch.float32)
         A.logits, A.lse, A.rowloss = logits.data_ptr(), lse.data_ptr(), rowloss.data_ptr()
-        L.check(lib.mtn_losshead_fwd(C.byref(A), L.stream_ptr()))
-        ctx.args, ctx.keep = A, (x_lp, logits, lse, norms, targets)
+        if teachers is None:
+            L.check(lib.mtn_losshead_fwd(C.byref(A), L.stream_ptr()))
+        else:
+            rowkd = torch.empty(R, device=dev, dtype=torch.float32)
+            for i, q in enumerate(teachers):
+                if q is not None:
+                    A.teacher[i], A.ldq[i] = q.data_ptr(), q.stride(0)
+            A.alpha, A.temperature, A.rowkd = float(spec.get("alpha", 0.5)), float(spec.get("temperature", 1.0)), rowkd.data_ptr()
+            L.check(lib.mtn_distill_fwd(C.byref(A), L.stream_ptr()))
+            spec["kd_sum"] = rowkd.sum()
+        ctx.args, ctx.keep = A, (x_lp, logits, lse, norms, targets, teachers)
         ctx.meta = (spec, segs, rows, offs, d, V, R, code, [x.shape for x in xs])
         return rowloss.sum()
 
@@ -1571,14 +1608,17 @@ class GeneratorLossFn(torch.autograd.Function):
     def backward(ctx, g):
         lib = L.load()
         spec, segs, rows, offs, d, V, R, code, shapes = ctx.meta
-        x_lp, logits, lse, norms, targets = ctx.keep
+        x_lp, logits, lse, norms, targets, teachers = ctx.keep
         lp = spec["lp_dtype"]
         dev = x_lp.device
         A = ctx.args
         gl = g.contiguous().float().reshape(1)
         dlogits = torch.empty(R, V, device=dev, dtype=lp)
         A.gloss, A.dlogits, A.ldd = gl.data_ptr(), dlogits.data_ptr(), V
-        L.check(lib.mtn_losshead_bwd(code, C.byref(A), L.stream_ptr()))
+        if teachers is None:
+            L.check(lib.mtn_losshead_bwd(code, C.byref(A), L.stream_ptr()))
+        else:
+            L.check(lib.mtn_distill_bwd(code, C.byref(A), L.stream_ptr()))
         dx = torch.empty(R, d, device=dev, dtype=torch.float32)
         p_dx, p_dw = [], []
         for o, r, (w_lp, bias, gw, gb, *rest) in segs:

@@ -82,7 +82,115 @@ def parse(argv=None):
                    help="> 0: train on a synthetic ragged CORPUS of that many videos (10 turns each) through the reference's "
                         "epoch loop — batch planning, device-side batch assembly, one eager step per batch — instead of "
                         "replaying one fixed-shape batch")
-    return p.parse_args(argv)
+    # knowledge distillation (word level): frozen teacher checkpoints whose next-token distribution the student is trained against
+    p.add_argument("--distill-model", default=[], nargs="+", type=str, metavar="PREFIX",
+                   help="teacher checkpoint prefix(es) (<prefix>.pth.tar, as generate.py's --model), at most 8; several form an ensemble teacher")
+    p.add_argument("--distill-conf", default=[], nargs="+", type=str, metavar="CONF",
+                   help="the teachers' <model>.conf: one per --distill-model entry, or one for all")
+    p.add_argument("--distill-weights", default=None, nargs="+", type=float, help="one weight >= 0 per teacher (default: uniform)")
+    p.add_argument("--distill-mode", default="prob", choices=["prob", "logprob"], help="how several teachers are combined (generate.py --ensemble-mode)")
+    p.add_argument("--distill-alpha", default=0.5, type=float, help="loss = (1 - alpha) * label-smoothed KL + alpha * T^2 * KL(teacher || student)")
+    p.add_argument("--distill-temperature", default=1.0, type=float, help="T: both distributions are softmax(. / T) in the soft term")
+    args = p.parse_args(argv)
+    err = distill_flag_error(args)
+    if err:
+        p.error(err)
+    return args
+
+
+DISTILL_MAX_TEACHERS = 8
+
+
+def distill_flag_error(args):
+    """What is wrong with the --distill-* flags, as one line (None: nothing)."""
+    import math
+    n = len(args.distill_model)
+    if args.distill_conf and not n:
+        return "--distill-conf needs --distill-model"
+    if not (0.0 <= args.distill_alpha <= 1.0):
+        return "--distill-alpha must lie in [0, 1] (got %r)" % args.distill_alpha
+    if not (args.distill_temperature > 0.0 and math.isfinite(args.distill_temperature)):
+        return "--distill-temperature must be finite and > 0 (got %r)" % args.distill_temperature
+    if not n:
+        if args.distill_weights is not None:
+            return "--distill-weights needs --distill-model"
+        return None
+    if n > DISTILL_MAX_TEACHERS:
+        return "--distill-model takes at most %d teachers (%d given)" % (DISTILL_MAX_TEACHERS, n)
+    if not args.distill_conf:
+        return "--distill-model needs --distill-conf (the teachers' <model>.conf)"
+    if len(args.distill_conf) not in (1, n):
+        return "--distill-conf takes one conf per --distill-model entry or one for all (%d given for %d)" % (len(args.distill_conf), n)
+    w = args.distill_weights
+    if w is not None:
+        if len(w) != n:
+            return "--distill-weights takes one weight per --distill-model entry (%d given for %d)" % (len(w), n)
+        if not all(math.isfinite(x) and x >= 0 for x in w) or not any(x > 0 for x in w):
+            return "--distill-weights must be finite and >= 0, and not all 0"
+    return None
+
+
+def vocab_difference(student, teacher):
+    """The first word (in the student's id order, then the teacher's) whose id differs between two word -> id maps, as a phrase; None
+    when the maps are equal."""
+    for w, i in sorted(student.items(), key=lambda kv: kv[1]):
+        if w not in teacher:
+            return "word %r (id %d) is missing from it" % (w, i)
+        if teacher[w] != i:
+            return "word %r has id %d there and %d here" % (w, teacher[w], i)
+    for w, i in sorted(teacher.items(), key=lambda kv: kv[1]):
+        if w not in student:
+            return "its word %r (id %d) is not in the student's vocabulary" % (w, i)
+    return None
+
+
+def check_distill_confs(confs, names, vocab, args):
+    """A teacher scores the student's batches: its word -> id map must be the student's (``vocab``; None on synthetic data, where only
+    the size can be compared) and, when the student reads a data set, the data-shaping fields generate.check_ensemble_confs compares
+    must equal the student's arguments.  SystemExit naming the first teacher and the first difference."""
+    from .generate import ENSEMBLE_DATA_FIELDS
+    for (tv, ta), name in zip(confs, names):
+        if vocab is not None:
+            diff = vocab_difference(dict(vocab), dict(tv))
+            if diff is not None:
+                raise SystemExit("distillation: the vocabulary of %s differs from the student's: %s" % (name, diff))
+            for f in ENSEMBLE_DATA_FIELDS:
+                if getattr(ta, f) != getattr(args, f):
+                    raise SystemExit("distillation: %s of %s is %r, the student's is %r: teacher and student read the same data"
+                                     % (f, name, getattr(ta, f), getattr(args, f)))
+        elif len(tv) != args.vocab_size:
+            raise SystemExit("distillation: the vocabulary of %s has %d words, the student's %d" % (name, len(tv), args.vocab_size))
+
+
+def load_teacher(args, vocab, dev):
+    """The --distill-model checkpoints as one frozen teacher: a model, or a decode.Ensemble of them (None without the flag).  Loaded as
+    generate.py loads --model / --ensemble-model; a teacher at weight 0 is not loaded."""
+    if not args.distill_model:
+        return None
+    from . import generate as gen
+    n = len(args.distill_model)
+    paths = list(args.distill_conf) * (n if len(args.distill_conf) == 1 else 1)
+    confs = [gen.load_conf(c) for c in paths]
+    check_distill_confs(confs, ["%s (teacher %d)" % (c, i) for i, c in enumerate(paths)], vocab, args)
+    weights = list(args.distill_weights) if args.distill_weights is not None else [1.0] * n
+    members = []
+    for prefix, (tv, ta), w in zip(args.distill_model, confs, weights):
+        if w == 0:
+            logging.info("distillation: %s has weight 0 and is not loaded", prefix)
+            continue
+        logging.info("Loading teacher params from " + prefix)
+        members.append(gen.build_model(tv, ta, args.ft_sizes, gen.load_state_dict(prefix + ".pth.tar"), args.compute_dtype, dev))
+    for m in members:
+        for q in m.parameters():
+            q.requires_grad_(False)
+    if len(members) == 1:
+        teacher = members[0]
+    else:
+        from .decode import Ensemble
+        teacher = Ensemble(members, [w for w in weights if w != 0], args.distill_mode)
+    logging.info("distillation: %d teacher(s), mode %s, alpha %g, temperature %g", len(members), args.distill_mode, args.distill_alpha,
+                 args.distill_temperature)
+    return teacher
 
 
 def synthetic_corpus(n_videos, vocab, ft_sizes, seed, turns=10, max_answer=18, max_question=20):
@@ -115,14 +223,16 @@ def cut_a_applies(args) -> bool:
     return bool(args.cut_a) and corpus_mode
 
 
-def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=None):
+def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=None, stats=None):
     """The same epoch on captured graphs (train_step.BucketedTrainer): lengths rounded up to the bucket, one graph per padded
     shape, batches assembled in place on the device; the host only syncs at the report interval.  ``cut``: the --cut-a
-    RandomState (None = no truncation).  Returns (mean loss per token, target tokens of the epoch over all ranks)."""
+    RandomState (None = no truncation).  Returns (mean loss per token, target tokens of the epoch over all ranks).  ``stats``: a dict
+    that receives "kd", the epoch's mean distillation KL per token, when the trainer has a teacher."""
     order = list(range(len(indices)))
     rng.shuffle(order)
     dev = trainer.corpus.device
     loss_sum = torch.zeros((), device=dev)
+    kd_sum = torch.zeros((), device=dev) if trainer.teacher is not None else None
     tok_sum = torch.zeros((), device=dev, dtype=torch.int64)
     t0, tok0 = time.time(), 0
     for j, k in enumerate(order):
@@ -132,6 +242,8 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
         n_glob = b._norms_global[0].to(torch.int64)
         loss_sum += loss * n_glob
         tok_sum += n_glob
+        if kd_sum is not None:
+            kd_sum += trainer.last_kd * n_glob
         if (j + 1) % report_interval == 0 and rank == 0:
             ntok = int(tok_sum)
             dt = time.time() - t0
@@ -139,7 +251,11 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
             t0, tok0 = time.time(), ntok
     if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
         torch.distributed.all_reduce(loss_sum)
+        if kd_sum is not None:
+            torch.distributed.all_reduce(kd_sum)
     ntok = int(tok_sum)
+    if kd_sum is not None and stats is not None:
+        stats["kd"] = float(kd_sum) / max(1, ntok)
     return float(loss_sum) / max(1, ntok), ntok
 
 
@@ -173,22 +289,31 @@ def global_norms(b, ae_y, sync):
     return norms, local_ntok
 
 
-def run_epoch(corpus, indices, model, loss_compute, ae_ft, epoch, report_interval, rank, rng, cut=None):
+def run_epoch(corpus, indices, model, loss_compute, ae_ft, epoch, report_interval, rank, rng, cut=None, distill=None, stats=None):
     """train.py:23-50: shuffle the planned batches, assemble each on the device, forward, loss + backward + optimiser.
     Data parallel: the loss normalisers are the GLOBAL token counts of the step (all ranks' batches), so that the summed
     gradients are those of one rank on the concatenated batch (dp.py) — as the captured schedule does (TrainStep._norms).
-    ``cut``: the --cut-a RandomState (None = no truncation).  Returns (mean loss per token, target tokens over all ranks)."""
+    ``cut``: the --cut-a RandomState (None = no truncation).  Returns (mean loss per token, target tokens over all ranks).
+    ``distill``: (teacher, alpha, temperature) — the teacher's rows are computed before the student's forward (train_step.teacher_rows);
+    ``stats`` then receives "kd", this rank's mean distillation KL per token."""
     from .data_handler import make_batch
+    from .train_step import teacher_rows
     order = list(range(len(indices)))
     rng.shuffle(order)
     t0, tokens, total_loss, total_tokens, global_tokens = time.time(), 0, 0.0, 0, 0
     sync = loss_compute.grad_sync
+    kd_total = 0.0
     for j, k in enumerate(order):
         b = make_batch(corpus, indices[k], 1, separate_caption=True, cut_a=cut is not None, rng=cut)
+        kw = {}
+        if distill is not None:
+            kw = dict(teacher_logp=teacher_rows(distill[0], b), alpha=distill[1], temperature=distill[2])
         out, ae_out = model.forward(b)
         ae_y = b.cap if ae_ft in ("caption", "summary") else b.query
         norms, local_ntok = global_norms(b, ae_y, sync)
-        loss = loss_compute(out, b.trg_y, norms[0], ae_out, ae_y, norms[1])     # = normalised loss x global target tokens
+        loss = loss_compute(out, b.trg_y, norms[0], ae_out, ae_y, norms[1], **kw)     # = normalised loss x global target tokens
+        if distill is not None and loss_compute.last_kd_sum is not None:
+            kd_total += float(loss_compute.last_kd_sum)
         n_glob = float(norms[0])
         loss = loss * local_ntok / n_glob                                       # this rank's share, for the epoch mean below
         total_loss += loss
@@ -199,6 +324,8 @@ def run_epoch(corpus, indices, model, loss_compute, ae_ft, epoch, report_interva
             dt = time.time() - t0
             print("Epoch: %d Step: %d Loss: %f Tokens per Sec: %f" % (epoch + 1, j + 1, loss / float(b.ntokens), tokens / dt))
             t0, tokens = time.time(), 0
+    if distill is not None and stats is not None:
+        stats["kd"] = kd_total / max(1, total_tokens)
     return total_loss / max(1, total_tokens), global_tokens
 
 
@@ -246,6 +373,8 @@ def main(argv=None):
                        diff_gen=bool(args.diff_gen), auto_encoder_ft=args.auto_encoder_ft, compute_dtype=args.compute_dtype)
     model.to(dev).train()
     model.prepare()
+    teacher = load_teacher(args, vocab, dev)
+    distill = dict(teacher=teacher, distill_alpha=args.distill_alpha, distill_temperature=args.distill_temperature) if teacher is not None else {}
     sync = None
     if world > 1:
         sync = dp.GradSync(lambda: model.flat_buffers()[2])
@@ -277,7 +406,7 @@ def main(argv=None):
         else:
             from .train_step import BucketedTrainer
             trainer = BucketedTrainer(model, corpus, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l,
-                                      bucket=args.bucket, grad_sync=sync)
+                                      bucket=args.bucket, grad_sync=sync, **distill)
         valid = None
         if args.valid_videos > 0 or valid_data is not None:
             vdata = valid_data if valid_data is not None else synthetic_corpus(args.valid_videos, args.vocab_size, args.ft_sizes, args.rand_seed + 1000)
@@ -292,15 +421,19 @@ def main(argv=None):
             the_opt.load_state_dict(torch.load(args.resume + "_opt.pth.tar"))
             logging.info("resumed from %s at optimiser step %d", args.resume, the_opt.step_count())
         for epoch in range(args.num_epochs):
+            stats = {}
             if args.eager:
-                mean, ntok = run_epoch(corpus, indices, model, lc, args.auto_encoder_ft, epoch, args.report_interval, rank, rng, cut)
+                mean, ntok = run_epoch(corpus, indices, model, lc, args.auto_encoder_ft, epoch, args.report_interval, rank, rng, cut,
+                                       distill=(teacher, args.distill_alpha, args.distill_temperature) if teacher is not None else None, stats=stats)
             else:
-                mean, ntok = run_epoch_graphed(trainer, indices, epoch, args.report_interval, rank, rng, cut)
+                mean, ntok = run_epoch_graphed(trainer, indices, epoch, args.report_interval, rank, rng, cut, stats=stats)
             means.append(mean)
             if rank == 0:
                 logging.info("epoch %d: %d target tokens trained%s", epoch + 1, ntok, " (answers cut at random)" if cut_a else "")
             if rank == 0:
                 print("epoch %d mean train loss per token: %f" % (epoch + 1, mean))
+                if "kd" in stats:
+                    print("epoch %d mean distillation KL per token: %f" % (epoch + 1, stats["kd"]))
             if args.model:
                 # EVERY rank builds the optimiser state: with the sharded optimiser (dp.ShardedOptimizerSync) a rank holds the
                 # Adam moments of its shards only (and, with the compute-dtype gather, the current fp32 masters of its shards
@@ -327,18 +460,26 @@ def main(argv=None):
         return means
     Q, H, C, T, V = args.lens
     batch = synthetic_batch(args.vocab_size, args.batch_size, Q, H, C, T, [V] * len(args.ft_sizes), args.ft_sizes, device=dev, seed=1 + rank)
-    step = TrainStep(model, batch, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l, grad_sync=sync)
+    step = TrainStep(model, batch, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l, grad_sync=sync, **distill)
     ntok = int(batch.ntokens) * world
     for epoch in range(args.num_epochs):
         t0, tokens = time.time(), 0
+        kd_sum = torch.zeros((), device=dev) if teacher is not None else None
         for j in range(args.steps_per_epoch):
             loss = step()
             tokens += ntok
+            if kd_sum is not None:
+                kd_sum += step.last_kd
             if (j + 1) % args.report_interval == 0 and rank == 0:
                 torch.cuda.synchronize()
                 dt = time.time() - t0
                 print("Epoch: %d Step: %d Loss: %f Tokens per Sec: %f" % (epoch + 1, j + 1, float(loss), tokens / dt))   # train.py:46
                 t0, tokens = time.time(), 0
+        if kd_sum is not None:
+            if world > 1:
+                torch.distributed.all_reduce(kd_sum)
+            if rank == 0:
+                print("epoch %d mean distillation KL per token: %f" % (epoch + 1, float(kd_sum) / max(1, args.steps_per_epoch)))
         if args.model:
             model_state = model.state_dict()      # every rank: under the sharded optimiser's compute-dtype gather this gathers the fp32
             if rank == 0:                         # masters of the other ranks' shards (a collective) — rank 0 alone writes

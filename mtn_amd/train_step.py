@@ -27,17 +27,53 @@ CAPTURE_MODE = os.environ.get("MTN_CAPTURE_MODE", "thread_local")
 _CUT_GACC = True      # gradients across a layer cut meet in the memory-gradient buffer (no autograd add)
 
 
+def teacher_members(teacher):
+    """(active members, weights or None, mode) of a teacher: a model is an ensemble of one (the combining kernel normalises)."""
+    from .decode import Ensemble
+    if isinstance(teacher, Ensemble):
+        return list(teacher.active), list(teacher.active_weights), teacher.mode
+    if isinstance(teacher, torch.nn.Module) and hasattr(teacher, "generator") and hasattr(teacher, "forward"):
+        return [teacher], None, "prob"
+    raise ValueError("distillation: teacher is a model or a decode.Ensemble")
+
+
+def teacher_rows(teacher, batch, out=None):
+    """The teacher's next-token log-probabilities for every target position of ``batch``, (rows, V) fp32: each active member's eval()
+    forward under no_grad, its generator logits, then ONE ops.ensemble_rows launch over the members.  Nothing is left behind:
+    no dropout stream is advanced, nothing enters a parameter-gradient queue, every forward flushes its rider work."""
+    from . import ops
+    members, weights, mode = teacher_members(teacher)
+    rows = []
+    with torch.no_grad():
+        for m in members:
+            if m.training:
+                m.eval()
+            o, _ = m.forward(batch)
+            z = m.generator.logits(o)
+            rows.append(z.reshape(-1, z.size(-1)))
+        return ops.ensemble_rows(rows, weights, mode, out=out)
+
+
 class TrainStep:
     def __init__(self, model, batch, vocab: int, pad: int = 1, warmup: int = 4000, factor: float = 1.0, lam: float = 1.0,
                  smoothing: float = 0.1, grad_sync=None, use_graph: bool = True, overlap: Optional[bool] = None, opt=None,
-                 dynamic_norms: bool = False, fuse_optimizer: Optional[bool] = None):
+                 dynamic_norms: bool = False, fuse_optimizer: Optional[bool] = None, teacher=None, distill_alpha: float = 0.5,
+                 distill_temperature: float = 1.0):
         """``opt``: share an existing NoamOpt (several TrainSteps over one model, e.g. one per batch shape).
         ``dynamic_norms``: the batch tensors are refilled in place between steps, so the loss normalisers (token counts,
         train.py:35-39) are recomputed from them inside the step instead of once at construction.
         ``fuse_optimizer``: None = on one rank, apply Adam to the sublayer weight matrices inside their parameter-gradient
         GEMMs (FusedAdam.fuse_into_backward; those gradients are then never written to ``.grad``); False = always the
-        separate optimiser pass (gradients of every parameter are left in ``.grad`` after the step)."""
+        separate optimiser pass (gradients of every parameter are left in ``.grad`` after the step).
+        ``teacher``: word-level knowledge distillation — a frozen model, or a decode.Ensemble of them, on the student's device and
+        with its vocabulary size.  Inside the step (and its captured graph) every active member runs an eval() forward on the step's
+        batch under no_grad, the members' generator logits are combined by ops.ensemble_rows into one row of log-probabilities
+        per target position, and the MAIN decoder stream's loss becomes (1 - distill_alpha) * label-smoothed KL + distill_alpha *
+        T^2 * KL(teacher_T || student_T) (csrc/distill.hip; the auto-encoder streams keep the plain loss).  The teacher pass runs
+        to completion before the student's forward starts and leaves nothing behind, so with distill_alpha == 0 the step is the
+        undistilled step bit for bit.  ``last_kd``: device scalar, the step's summed row KL over its target-token normaliser."""
         self.model, self.batch = model, batch
+        self._init_teacher(teacher, distill_alpha, distill_temperature, vocab)
         self.opt = opt if opt is not None else NoamOpt(model.decoder.layers[0].size, factor, warmup, FusedAdam(model))
         self.dynamic_norms = dynamic_norms
         self.crit = LabelSmoothing(vocab, pad, smoothing)
@@ -98,9 +134,52 @@ class TrainStep:
             self.grad_sync.all_reduce_scalars(n)
             self._norms.copy_(n)
 
+    # ---- knowledge distillation
+    def _init_teacher(self, teacher, alpha, temperature, vocab):
+        self.teacher, self._teacher_rows, self.last_kd = teacher, None, None
+        self.distill_alpha, self.distill_temperature = float(alpha), float(temperature)
+        if teacher is None:
+            return
+        members, _, _ = teacher_members(teacher)
+        if not (0.0 <= self.distill_alpha <= 1.0):
+            raise ValueError("TrainStep: distill_alpha in [0, 1]")
+        if not (0.0 < self.distill_temperature < float("inf")):
+            raise ValueError("TrainStep: distill_temperature is finite and > 0")
+        dev = next(self.model.parameters()).device
+        for m in members:
+            if m is self.model:
+                raise ValueError("TrainStep: the teacher is the student itself (pass a frozen copy)")
+            if int(m.generator.proj.weight.size(0)) != int(vocab):
+                raise ValueError(f"TrainStep: a teacher's vocabulary size ({int(m.generator.proj.weight.size(0))}) is not the student's ({vocab})")
+            if next(m.parameters()).device != dev:
+                raise ValueError("TrainStep: the teacher is not on the student's device")
+            m.eval()
+            m.prepare()
+        self._teacher_rows = torch.empty(self.batch.trg_y.numel(), int(vocab), device=dev, dtype=torch.float32)
+        self.last_kd = torch.zeros((), device=dev)
+
+    def _teacher_pass(self):
+        """The teacher's rows for this batch, into the buffer allocated once; returns it (None without a teacher).  eval() forwards
+        under no_grad: no dropout stream is advanced, nothing enters a parameter-gradient queue, and every forward ends by flushing
+        its rider work (EncoderDecoder.forward), so the student's launches that follow are those of the undistilled step."""
+        if self._teacher_rows is None:
+            return None
+        return teacher_rows(self.teacher, self.batch, out=self._teacher_rows)
+
+    def _loss_of(self, out, ae_out, teacher_rows):
+        """The step's loss, for both schedules (monolithic _fwd_bwd, the segmented top())."""
+        if teacher_rows is None:
+            return self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1])
+        loss = self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], teacher_logp=teacher_rows,
+                            alpha=self.distill_alpha, temperature=self.distill_temperature)
+        kd = self.lc.last_kd_sum
+        self.last_kd = kd / self._norms[0] if kd is not None else torch.zeros_like(self._norms[0])
+        return loss
+
     def _fwd_bwd(self, fuse: bool = False):
         m, b = self.model, self.batch
         self._refresh_norms()
+        teacher_rows = self._teacher_pass()
         m.zero_glue_grads()
         if m._queue is not None and (m._queue.gemm or m._queue.ln or m._queue._armed):
             m._queue.reset()               # left over from a step that raised: never mix it into this one
@@ -110,7 +189,7 @@ class TrainStep:
             self.opt.begin_fused_step()
         try:
             out, ae_out = m.forward(b)
-            loss = self.lc.loss(out, b.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1])
+            loss = self._loss_of(out, ae_out, teacher_rows)
             loss.backward(self._unit_grad(loss))          # (a kept ones scalar: autograd would launch a fill for the implicit one)
         except BaseException:
             if m._queue is not None:
@@ -178,10 +257,11 @@ class TrainStep:
         def top():
             b = self.batch
             self._refresh_norms()
+            teacher_rows = self._teacher_pass()
             m.zero_glue_grads()
             st = m.forward_segmented(b)
             self._st = st
-            loss = self.lc.loss(st["out"], b.trg_y, self._norms[0], st["ae_out"], self._ae_y, self._norms[1])
+            loss = self._loss_of(st["out"], st["ae_out"], teacher_rows)
             loss.backward(self._unit_grad(loss))                # loss head + final LayerNorms
             ins, outs = st["layers"][N - 1]
             bwd(outs, st["top_in"])                             # top decoder layer
@@ -372,11 +452,13 @@ class BucketedTrainer:
     place on the device (data_handler.make_batch(out=...)) and replays its graph.  One optimiser state for all shapes."""
 
     def __init__(self, model, corpus, vocab_size: int, pad: int = 1, warmup: int = 4000, lam: float = 1.0, bucket: int = 8,
-                 grad_sync=None, max_shapes: int = 64):
+                 grad_sync=None, max_shapes: int = 64, teacher=None, distill_alpha: float = 0.5, distill_temperature: float = 1.0):
         self.model, self.corpus, self.vocab, self.pad, self.lam = model, corpus, vocab_size, pad, lam
+        self.teacher, self.distill_alpha, self.distill_temperature = teacher, distill_alpha, distill_temperature
         self.bucket, self.grad_sync, self.max_shapes = bucket, grad_sync, max_shapes
         self.opt = NoamOpt(model.decoder.layers[0].size, 1.0, warmup, FusedAdam(model))
         self.steps = {}
+        self.last_kd = None
 
     def _padded(self, index):
         up = lambda v: -(-int(v) // self.bucket) * self.bucket
@@ -396,10 +478,13 @@ class BucketedTrainer:
                 self.steps.pop(next(iter(self.steps)))
             batch = make_batch(self.corpus, pidx, self.pad, separate_caption=True, cut_a=cut_a, rng=rng)
             ts = TrainStep(self.model, batch, self.vocab, pad=self.pad, lam=self.lam, grad_sync=self.grad_sync, opt=self.opt,
-                           dynamic_norms=True)
+                           dynamic_norms=True, teacher=self.teacher, distill_alpha=self.distill_alpha,
+                           distill_temperature=self.distill_temperature)
             self.steps[key] = hit = (batch, ts)
         else:
             make_batch(self.corpus, pidx, self.pad, separate_caption=True, out=hit[0], cut_a=cut_a, rng=rng)
         hit[1].refresh_norms_eager()
+        loss = hit[1]()
+        self.last_kd = hit[1].last_kd               # (device scalar; None without a teacher)
         hit[0]._norms_global = hit[1]._norms        # [target tokens, auto-encoder tokens] the step's loss is divided by (all ranks)
-        return hit[1](), hit[0]
+        return loss, hit[0]
