@@ -24,12 +24,33 @@ from __future__ import annotations
 
 from typing import List, Optional, Sequence
 
+import copy
+import ctypes as C
+import logging
+import math
 import os
 
+import numpy as np
 import torch
 
+from . import lib as L
 from . import ops
 from .data_utils import subsequent_mask
+
+
+def _capture(body):
+    """``body`` as a graph: one warm-up run on a side stream (lazy allocations and library set-up happen outside the capture), then the
+    capture itself — the body runs exactly twice.  The caller replays the returned graph."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        body()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        body()
+    return g
 
 
 class DecodeSession:
@@ -114,7 +135,6 @@ class DecodeSession:
                     self._load_body(self._static)
                 self._load_graph = g
             except Exception as e:                          # never lose a decode to the faster path
-                import logging
                 logging.getLogger("mtn_amd").warning("decode: capturing the encoder-side pass failed (%s); it stays eager", e)
                 self._load_graph = False
                 torch.cuda.synchronize()
@@ -125,7 +145,6 @@ class DecodeSession:
 
     def _stage(self, b):
         """Copy a dialogue's inputs into the session's static Batch (created from the first one staged)."""
-        import copy
         tensors = lambda x: [x.query, x.query_mask, x.his, x.his_mask, x.cap, x.cap_mask] + list(x.fts or []) + list(x.fts_mask or [])
         if self._static is None:
             st = copy.copy(b)
@@ -211,7 +230,8 @@ class DecodeSession:
     def _pass(self):
         self._head(self._target_rows())
 
-    def _target_rows(self):
+    def _decoder_rows(self):
+        """The full-prefix pass up to the decoder's final norm: (rows, max_len, d) activations of self.tokens under the causal mask."""
         m = self.model
         cap_mask, his_mask, q_mask = self.masks
         x = m.embed_target(self.tokens)
@@ -222,8 +242,10 @@ class DecodeSession:
                                          m.auto_encoder_ft)
         finally:
             m.clear_memory_kv()
-        x = m.decoder.norm(x)
-        last = x.index_select(1, self.pos).squeeze(1)               # (width, d): the position being extended
+        return m.decoder.norm(x)
+
+    def _target_rows(self):
+        last = self._decoder_rows().index_select(1, self.pos).squeeze(1)     # (width, d): the position being extended
         return self._generate(last)                                 # (width, V)
 
     def _pass_cached(self, cur: int):
@@ -253,23 +275,40 @@ class DecodeSession:
         x = m.decoder.norm(x)
         return self._generate(x.squeeze(1))
 
-    def _step_cached(self, prefix_lists):
+    def _check_prefixes(self, prefix_lists):
+        """The common length of a step's prefixes, checked against the session's shape."""
+        if len(prefix_lists) != self.D:
+            raise ValueError("one prefix list per dialogue of the session")
         l = len(prefix_lists[0][0])
+        if max(len(p) for p in prefix_lists) > self.width or l > self.max_len:
+            raise ValueError("more hypotheses / longer prefix than the session was built for")
+        return l
+
+    def _stage_prefixes(self, prefix_lists):
+        """The checked prefixes of a step into self.tokens (dialogue d's from row d * width on, pad elsewhere) and their last position
+        into self.pos; returns their length."""
+        l = self._check_prefixes(prefix_lists)
         W = self.width
-        host_tok = torch.full((self.D * W, self.max_len), self.pad, dtype=torch.long)
-        parent = torch.arange(self.D * W)
+        host = torch.full((self.D * W, self.max_len), self.pad, dtype=torch.long)
         for d, prefixes in enumerate(prefix_lists):
-            host_tok[d * W:d * W + len(prefixes), :l] = torch.tensor(prefixes, dtype=torch.long)
-            if l > 1:
+            host[d * W:d * W + len(prefixes), :l] = torch.tensor(prefixes, dtype=torch.long)
+        self.tokens.copy_(host, non_blocking=False)
+        self.pos.fill_(l - 1)
+        return l
+
+    def _step_cached(self, prefix_lists):
+        l = self._stage_prefixes(prefix_lists)
+        W = self.width
+        parent = torch.arange(self.D * W)
+        if l > 1:
+            for d, prefixes in enumerate(prefix_lists):
                 prev = self._prev[d]
                 # the hypothesis this one extends (same tokens but the last).  Two groups of a diverse search may hold the same prefix: the
                 # lookup finds the first of them, whose cache rows hold the same values
                 for i, p in enumerate(prefixes):
                     parent[d * W + i] = d * W + prev.index(list(p[:-1]))
         self._prev = [[list(p) for p in prefixes] for prefixes in prefix_lists]
-        self.tokens.copy_(host_tok)
         self._parent.copy_(parent)
-        self.pos.fill_(l - 1)
         cur = self._cur
         with torch.no_grad():
             if not self.use_graph:
@@ -277,15 +316,7 @@ class DecodeSession:
             else:
                 g = self._graphs.get(cur)
                 if g is None:
-                    side = torch.cuda.Stream()
-                    side.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(side):
-                        self._pass_cached(cur)
-                    torch.cuda.current_stream().wait_stream(side)
-                    torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        self._pass_cached(cur)
+                    g = _capture(lambda: self._pass_cached(cur))
                     g = self._graphs[cur] = (g, self.logp, self.top)          # each graph writes its own output buffers
                 g[0].replay()
                 self.logp, self.top = g[1], g[2]
@@ -299,32 +330,15 @@ class DecodeSession:
     def step_many(self, prefix_lists: Sequence[Sequence[Sequence[int]]]):
         """One decode step for all dialogues of the session: prefix_lists[d] = live prefixes of dialogue d (same length
         everywhere, at most `width` per dialogue) -> list of (n_d, V) log-probability tensors."""
-        if len(prefix_lists) != self.D:
-            raise ValueError("one prefix list per dialogue of the session")
-        l = len(prefix_lists[0][0])
-        if max(len(p) for p in prefix_lists) > self.width or l > self.max_len:
-            raise ValueError("more hypotheses / longer prefix than the session was built for")
         if self.kv_cache:
             return self._step_cached(prefix_lists)
-        host = torch.full((self.D * self.width, self.max_len), self.pad, dtype=torch.long)
-        for d, prefixes in enumerate(prefix_lists):
-            host[d * self.width:d * self.width + len(prefixes), :l] = torch.tensor(prefixes, dtype=torch.long)
-        self.tokens.copy_(host, non_blocking=False)
-        self.pos.fill_(l - 1)
+        self._stage_prefixes(prefix_lists)
         with torch.no_grad():
             if not self.use_graph:
                 self._pass()
             else:
                 if self._graph is None:
-                    side = torch.cuda.Stream()
-                    side.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(side):
-                        self._pass()
-                    torch.cuda.current_stream().wait_stream(side)
-                    torch.cuda.synchronize()
-                    self._graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self._graph):
-                        self._pass()
+                    self._graph = _capture(self._pass)
                 self._graph.replay()
         return [self.logp[d * self.width:d * self.width + len(p)] for d, p in enumerate(prefix_lists)]
 
@@ -334,18 +348,7 @@ class DecodeSession:
         ops.score_rows(self._score_logits(), self._score_target, self.pad, out=self._score_out)
 
     def _score_logits(self):
-        m = self.model
-        cap_mask, his_mask, q_mask = self.masks
-        x = m.embed_target(self.tokens)
-        m.attach_memory_kv(self._kv_pairs)
-        try:
-            for k, layer in enumerate(m.decoder.layers):
-                x = layer.forward_target(x, self.cp, cap_mask, self.hs, his_mask, self.q, q_mask, self.trg_mask, self.aes[k],
-                                         m.auto_encoder_ft)
-        finally:
-            m.clear_memory_kv()
-        x = m.decoder.norm(x)
-        z = m.generator.logits(x)                                   # (D * width, max_len, V) fp32
+        z = self.model.generator.logits(self._decoder_rows())       # (D * width, max_len, V) fp32
         return z.view(-1, z.size(-1))
 
     def score(self, rows_tokens: Sequence[Sequence[int]], start: int, eos: int):
@@ -374,15 +377,7 @@ class DecodeSession:
                 self._pass_score()
             else:
                 if self._score_graph is None:
-                    side = torch.cuda.Stream()
-                    side.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(side):
-                        self._pass_score()
-                    torch.cuda.current_stream().wait_stream(side)
-                    torch.cuda.synchronize()
-                    self._score_graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self._score_graph):
-                        self._pass_score()
+                    self._score_graph = _capture(self._pass_score)
                 self._score_graph.replay()
         return tuple(t.cpu().numpy() for t in self._score_out)
 
@@ -439,7 +434,6 @@ class MegaDecodeSession(DecodeSession):
 
     def __init__(self, model, batch, max_len, width, pad=1, use_graph=True, select=None, share=None):
         super().__init__(model, batch, max_len, width, pad=pad, use_graph=use_graph, kv_cache=False, select=select, share=share)
-        from . import lib as L
         dev = batch.query.device
         layers = model.decoder.layers
         d, h = layers[0].size, layers[0].self_attn.h
@@ -463,7 +457,6 @@ class MegaDecodeSession(DecodeSession):
             self._devblk = torch.zeros(nbytes, device=dev, dtype=torch.uint8)
         else:                               # (same W and max_len: the same layout) this launch reads the block the sharer's bookkeeping writes
             self._host, self._devblk = share._host, share._devblk
-        import numpy as np
         hb = self._host.numpy()                       # numpy views of the pinned block: the per-step bookkeeping below is plain numpy slicing
         self._h_tok = hb[:8 * W].view(np.int64)
         self._h_pos = hb[self._off_pos:self._off_pos + 8].view(np.int32)
@@ -491,7 +484,6 @@ class MegaDecodeSession(DecodeSession):
         target stream — self-attention, history, caption | query (order by auto_encoder_ft), one attention per auto-encoder stream,
         feed-forward — every attention followed by its output projection; pointers into the model's flat buffers and this session's
         hoisted K|V / masks (all refreshed IN PLACE by load(), so the table is built once)."""
-        import ctypes as C
         m = self.model
         cap_mask, his_mask, q_mask = self.masks
         kvmap = {id(sc): kv for sc, kv in self._kv_pairs}
@@ -538,15 +530,11 @@ class MegaDecodeSession(DecodeSession):
         self._stages_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self._x.device)
 
     def _pass_mega(self):
-        import ctypes as C
-        from . import lib as L
-        m = self.model
         # the step's host inputs and (with device-side selection) its host outputs travel INSIDE the pass — copy nodes of the captured graph —
         # so a generated token costs the host one replay and one stream synchronisation
         self._devblk.copy_(self._host, non_blocking=True)
-        self.logp = self._step_rows()                                                    # (W, V) fp32 log-probabilities (mtn.py:68-69)
+        self._head(self._step_rows())                                                    # (W, V) fp32 log-probabilities (mtn.py:68-69)
         if self.select is not None:
-            self.top = ops.topk_rows(self.logp, min(self.select[0], self.logp.size(1)), self.select[1])
             if self._top_host is None:
                 self._top_host = torch.empty(self.top.shape, dtype=self.top.dtype).pin_memory()
             self._top_host.copy_(self.top, non_blocking=True)
@@ -554,8 +542,6 @@ class MegaDecodeSession(DecodeSession):
     def _step_rows(self, logits=False):
         """One persistent decode step on the shared [tokens | pos | anc] block and the generator on its output rows: (W, V) fp32
         log-probabilities, or the logits (a member of an Ensemble session: csrc/ensemble.hip normalises them)."""
-        import ctypes as C
-        from . import lib as L
         L.check(L.load().mtn_decode_step(C.byref(self._args), self._stages_dev.data_ptr(), self._grid, L.stream_ptr()))
         g = self.model.generator._fused
         return (ops.generator_logits if logits else ops.generator_log_probs)(self._out_lp, g["w_lp"], g["bias"])
@@ -572,29 +558,25 @@ class MegaDecodeSession(DecodeSession):
         if log is None:
             return None
         par, tok, n_old, n_new, score, done_sc, flags = log
-        results = []
-        if G > 1:
-            # diverse beam search: the log holds D x G pseudo-dialogues of width beam / G (group g of dialogue d owns rows d * width + g * Bp ..);
-            # a dialogue's finished hypotheses are pooled in the order the stepped path appends them: step, group, hypothesis
-            Bp = self.width // G
-            for d_ in range(self.D):
-                outs, done = [[[]] for _ in range(G)], []
-                for l in range(self.max_len):
-                    for g in range(G):
-                        p, base = d_ * G + g, d_ * self.width + g * Bp
-                        if l >= min_len:
-                            done += [(outs[g][h], float(done_sc[l, base + h])) for h in range(int(n_old[l, p]))]
-                        outs[g] = [outs[g][int(par[l, base + i])] + [int(tok[l, base + i])] for i in range(int(n_new[l, p]))]
-                results.append(_pool_groups(done, nbest))
-            return results
-        for d_ in range(self.D):
-            base = d_ * self.width
-            outs, done = [[]], []
+
+        def finished(base, p):
+            """Per step, the hypotheses of the log's pseudo-dialogue p (its rows start at ``base``) that finished there, with their scores."""
+            outs = [[]]
             for l in range(self.max_len):
-                if l >= min_len:
-                    done += [(outs[h], float(done_sc[l, base + h])) for h in range(int(n_old[l, d_]))]
-                outs = [outs[int(par[l, base + i])] + [int(tok[l, base + i])] for i in range(int(n_new[l, d_]))]
-            if done:
+                yield [(outs[h], float(done_sc[l, base + h])) for h in range(int(n_old[l, p]))] if l >= min_len else []
+                outs = [outs[int(par[l, base + i])] + [int(tok[l, base + i])] for i in range(int(n_new[l, p]))]
+
+        # diverse beam search: the log holds D x G pseudo-dialogues of width beam / G (group g of dialogue d owns rows d * width + g * Bp ..);
+        # a dialogue's finished hypotheses are pooled in the order the stepped path appends them: step, group, hypothesis.  One group: the
+        # dialogue itself, its finished hypotheses in step order, and the plain search's result (_Beam.result)
+        Bp = self.width // G
+        results = []
+        for d_ in range(self.D):
+            groups = [finished(d_ * self.width + g * Bp, d_ * G + g) for g in range(G)]
+            done = [h for step in zip(*groups) for group in step for h in group]
+            if G > 1:
+                results.append(_pool_groups(done, nbest))
+            elif done:
                 results.append((sorted(done, key=lambda h: -h[1])[:nbest], max(h[1] for h in done)))
             else:
                 results.append(([([], 0)], None))
@@ -610,6 +592,17 @@ class MegaDecodeSession(DecodeSession):
             return None
         return [[int(t) for t in log[1][:self.max_len - 1, d_ * self.width]] for d_ in range(self.D)]
 
+    def _block_image(self, start, stride):
+        """The pinned [tokens | pos | anc] block of a captured search before its first step: ``start`` in every ``stride``-th row and pad in
+        the others, position 0, every row its own cache slots (identity ancestors)."""
+        W = self._W
+        blk = np.zeros(self._host.numel(), dtype=np.uint8)
+        tok = blk[:8 * W].view(np.int64)
+        tok[:] = self.pad
+        tok[::stride] = start
+        blk[self._off_anc:].view(np.int32).reshape(W, self.max_len)[:] = np.arange(W, dtype=np.int32)[:, None]
+        return torch.from_numpy(blk).pin_memory()
+
     def _search_log(self, beam, k, start, unk, eos, penalty, min_len, extra_col, no_repeat_ngram=0, repetition_penalty=1.0, groups=1, diversity=0.0):
         """A whole beam search (data_utils.py:188-242) for every dialogue of the session as ONE graph replay: max_len x [persistent decode
         step, generator, row heads (csrc/select.hip topk_rows), hypothesis bookkeeping on the device (mtn_beam_advance)], the step log
@@ -623,9 +616,6 @@ class MegaDecodeSession(DecodeSession):
         of the search key; with one group nothing here differs from the plain search.
         Returns None when a row's head held an exact tie (the reference's visiting order then comes from the full row: the caller runs the
         search step by step) or when the device-side selection does not apply."""
-        import ctypes as C
-        import numpy as np
-        from . import lib as L
         k_top = k + 1
         if self.select is None or self.select[0] != k_top or self.select[1] != extra_col or beam > self.width or k_top > SELECT_MAX_K or not self.use_graph:
             return None
@@ -647,12 +637,7 @@ class MegaDecodeSession(DecodeSession):
             init = np.zeros(nst, dtype=np.uint8)
             init[8 * W:8 * W + 4 * D].view(np.int32)[:] = 1
             self._bstate_init = torch.from_numpy(init).pin_memory()
-            blk = np.zeros(self._host.numel(), dtype=np.uint8)               # [tokens | pos | anc] before the first step: <sos> in every dialogue's row 0
-            tok = blk[:8 * W].view(np.int64)
-            tok[:] = self.pad
-            tok[::Wd] = start
-            blk[self._off_anc:].view(np.int32).reshape(W, Lm)[:] = np.arange(W, dtype=np.int32)[:, None]
-            self._blk_init = torch.from_numpy(blk).pin_memory()
+            self._blk_init = self._block_image(start, Wd)                    # <sos> in every dialogue's row 0
             # the step log: [parent | tok (int32 L x W each) | n_old | n_new (int32 L x D each) | score | done (double L x W each) | flags (2 x int32)]
             o_par, o_tok = 0, 4 * Lm * W
             o_nold, o_nnew = 8 * Lm * W, 8 * Lm * W + 4 * Lm * D
@@ -697,15 +682,7 @@ class MegaDecodeSession(DecodeSession):
                 self._log_host.copy_(self._log, non_blocking=True)
 
             with torch.no_grad():
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    body()
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                self._search_graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._search_graph):
-                    body()
+                self._search_graph = _capture(body)
             self._search_key = key
         self._search_graph.replay()
         self._prev = None
@@ -726,9 +703,6 @@ class MegaDecodeSession(DecodeSession):
         are set d, read from the token log in device memory; its outputs are copied out next to the log, and the host still synchronises once.
         Returns the three host views (with mbr two more: expected utilities (D, width) and order (D, width)), or None after a poll timeout
         (timed_out() tells)."""
-        import ctypes as C
-        import numpy as np
-        from . import lib as L
         if not self.use_graph:
             raise ValueError("the sampling search on the persistent step is a captured graph")
         W, Lm = self._W, self.max_len
@@ -744,10 +718,7 @@ class MegaDecodeSession(DecodeSession):
             self._sstate_host = torch.zeros(nst, dtype=torch.uint8).pin_memory()
             hs = self._sstate_host.numpy()
             self._h_seed, self._h_keys = hs[:8].view(np.int64), hs[8:8 + 8 * W].view(np.int64)
-            blk = np.zeros(self._host.numel(), dtype=np.uint8)               # [tokens | pos | anc] before the first step: <sos> in every row
-            blk[:8 * W].view(np.int64)[:] = start
-            blk[self._off_anc:].view(np.int32).reshape(W, Lm)[:] = np.arange(W, dtype=np.int32)[:, None]
-            self._sblk_init = torch.from_numpy(blk).pin_memory()
+            self._sblk_init = self._block_image(start, 1)                    # <sos> in every row
             self._slog = torch.zeros(3, Lm, W, device=dev, dtype=torch.int32)   # (the two float logs are viewed as such)
             self._slog_host = torch.zeros(3, Lm, W, dtype=torch.int32).pin_memory()
             hl = self._slog_host.numpy()
@@ -779,15 +750,7 @@ class MegaDecodeSession(DecodeSession):
 
             self._h_seed[0], self._h_keys[:] = 0, 0
             with torch.no_grad():
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    body()
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                self._sample_graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._sample_graph):
-                    body()
+                self._sample_graph = _capture(body)
             self._sample_key = key
         self._h_seed[0] = seed
         self._h_keys[:] = keys
@@ -836,24 +799,12 @@ class MegaDecodeSession(DecodeSession):
                 self._pass_mega()
             else:
                 if self._graph is None:
-                    side = torch.cuda.Stream()
-                    side.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(side):
-                        self._pass_mega()
-                    torch.cuda.current_stream().wait_stream(side)
-                    torch.cuda.synchronize()
-                    self._graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self._graph):
-                        self._pass_mega()
+                    self._graph = _capture(self._pass_mega)
                 self._graph.replay()
 
     def step_many(self, prefix_lists):
-        if len(prefix_lists) != self.D:
-            raise ValueError("one prefix list per dialogue of the session")
-        l = len(prefix_lists[0][0])
+        l = self._check_prefixes(prefix_lists)
         W = self.width
-        if max(len(p) for p in prefix_lists) > W or l > self.max_len:
-            raise ValueError("more hypotheses / longer prefix than the session was built for")
         anc_old = self._h_anc.copy() if l > 1 else None
         self._h_tok[:] = self.pad
         for d_, prefixes in enumerate(prefix_lists):
@@ -1074,7 +1025,6 @@ class _Beam:
         """logp: (n_hyp, V) log-probabilities on the host — or None when ``top`` = (values (n,k), indices (n,k), eos column (n,))
         carries each row's k = beam+2 best entries in descending order: at most `beam` candidates per hypothesis can enter the
         new beam and at most two (<unk>, <eos>) are skipped, so the rest of the vocabulary is never looked at."""
-        import numpy as np
         new, par, argmin = [], [], 0
         for h, (out, lp, st) in enumerate(self.hyps):
             if top is None:
@@ -1136,17 +1086,20 @@ def beam_search_decode_many(model, batch, max_len, start_symbol, unk_symbol, end
         kv_cache = max_len > KV_CACHE_FROM
     args = (model, batch, max_len, start_symbol, unk_symbol, end_symbol, pad_symbol, beam, penalty, nbest, min_len, use_graph, kv_cache)
     kw = dict(ngram=ngram, theta=theta, groups=G, lam=lam) if G > 1 else dict(ngram=ngram, theta=theta)
-    res = _beam_search_many(*args, mega=auto, **kw)
-    if res is None:                  # a poll of the persistent step timed out (compute units held by another kernel): the launch-per-sublayer pass
-        res = _beam_search_many(*args, mega=False, **kw)
-    return res
+    return _with_fallback(lambda mega: _beam_search_many(*args, mega=mega, **kw), auto)
+
+
+def _with_fallback(search, auto):
+    """``search(mega)`` on the pass the caller left to us (``auto``: the persistent step where it applies).  None: a poll of the persistent
+    step timed out (compute units held by another kernel) — the search runs again on the launch-per-sublayer pass."""
+    res = search(auto)
+    return search(False) if res is None else res
 
 
 def _mega_failed(sess) -> bool:
     """After a search on a persistent-step session: True (and the session is made consistent again) if one of its polls timed out."""
     if not sess.timed_out():
         return False
-    import logging
     logging.getLogger("mtn_amd").warning("decode: the persistent step timed out (not every workgroup was resident); re-running on the launch-per-sublayer pass")
     sess.recover()
     MegaDecodeSession.FALLBACKS += 1
@@ -1231,7 +1184,6 @@ def _beam_search_many(model, batch, max_len, start_symbol, unk_symbol, end_symbo
 
 def _diverse(beam, beam_groups, diversity_penalty):
     """(G, lambda) of a beam search's diversity keywords, checked."""
-    import math
     G, lam = int(beam_groups), float(diversity_penalty)
     if G != beam_groups or G < 1 or int(beam) % G:
         raise ValueError("beam_groups is an integer >= 1 that divides beam")
@@ -1262,7 +1214,6 @@ def _diverse_advance(beams, G, l, lam, vals, idx, eos, k, rows, tie):
     / eos: the live rows' heads in the beams' order; they are penalised, re-sorted (stable, descending) and their first k entries walked.
     A tie inside a head, before the penalty (``tie``) or after it, sends the WHOLE step down the full-row path (``rows()``: the live rows,
     fp32): the groups are put back as they were and advanced again on the penalised full rows, whose argsort is the reference's order."""
-    import numpy as np
     f32 = np.float32
 
     def run(full):
@@ -1317,43 +1268,9 @@ def greedy_decode(model, batch, max_len, start_symbol, pad_symbol=1, use_graph=T
     """data_utils.py:159-186 (the reference's own greedy_decode cannot run: it calls decode() with the wrong arity, SURVEY
     §8c) — pinned to: argmax of the generator's log-probabilities at every step, (1, max_len) tokens incl. <sos>.
     no_repeat_ngram / repetition_penalty (off by default): the argmax is taken over the constrained row, as in beam_search_decode_many."""
-    ngram, theta, _ = _constraints(no_repeat_ngram, repetition_penalty)
-    auto = kv_cache is None
-    ys = _greedy(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto, ngram, theta)
-    if ys is None:                   # the persistent step timed out: the launch-per-sublayer pass
-        ys = _greedy(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, False, ngram, theta)
-    return torch.tensor([ys], dtype=batch.query.dtype, device=batch.query.device)
-
-
-def _greedy(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto, ngram=0, theta=1.0):
-    constrained = ngram > 0 or theta != 1.0
-    sess = _session(model, batch, max_len, 1, pad_symbol, use_graph, max_len > KV_CACHE_FROM if kv_cache is None else kv_cache,
-                    select=_pass_select(model, batch, max_len, 1, auto, (2, 0) if auto else None, constrained), mega=auto)
-    ys = [start_symbol]
-    if isinstance(sess, MegaDecodeSession) and sess.select is not None:
-        # the whole decode as one graph replay (None: a tie in some row's head)
-        toks = sess.greedy(start_symbol, ngram, theta)
-        toks = None if toks is None else toks[0]
-        if toks is None:
-            # step by step: the row's head (largest log-probability, its column) arrives in a pinned block — one replay and one
-            # stream synchronisation per token, no argmax launch, no .item()
-            for l in range(1, max_len):
-                sess.step_extend(l, [0], [ys[-1]], [0])
-                if constrained:          # (the head the pass took is of the unconstrained row)
-                    _constrain_step(sess, [(0, ys[1:])], ngram, theta)
-                    ys.append(int(ops.topk_rows(sess.logp, 2, 0)[0, 2].item()))
-                else:
-                    ys.append(int(sess.top_host()[0, 2]))
-        else:
-            ys += toks
-        return None if _mega_failed(sess) else ys
-    for _ in range(max_len - 1):
-        logp = sess.step([ys])
-        if constrained:
-            _constrain_step(sess, [(0, ys[1:])], ngram, theta)          # (in place: `logp` is a view of the session's rows)
-        nxt = int(logp.argmax(dim=-1)[0])
-        ys.append(nxt)
-    return ys
+    if batch.query.size(0) != 1:
+        raise ValueError("greedy_decode works on one dialogue (data_utils.py:159); use greedy_decode_many for a batch")
+    return greedy_decode_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, no_repeat_ngram, repetition_penalty)
 
 
 def greedy_decode_many(model, batch, max_len, start_symbol, pad_symbol=1, use_graph=True, kv_cache=None, no_repeat_ngram=0,
@@ -1362,10 +1279,8 @@ def greedy_decode_many(model, batch, max_len, start_symbol, pad_symbol=1, use_gr
     dialogue d alone.  On the persistent step the D argmax searches are ONE graph replay; otherwise the D rows are the batch
     dimension of one target-stream pass per token.  no_repeat_ngram / repetition_penalty: as greedy_decode."""
     ngram, theta, _ = _constraints(no_repeat_ngram, repetition_penalty)
-    auto = kv_cache is None
-    ys = _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, auto, ngram, theta)
-    if ys is None:                   # the persistent step timed out: the launch-per-sublayer pass
-        ys = _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, False, ngram, theta)
+    ys = _with_fallback(lambda mega: _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_cache, mega, ngram, theta),
+                        kv_cache is None)
     return torch.tensor(ys, dtype=batch.query.dtype, device=batch.query.device)
 
 
@@ -1376,13 +1291,15 @@ def _greedy_many(model, batch, max_len, start_symbol, pad_symbol, use_graph, kv_
     D = sess.D
     ys = [[start_symbol] for _ in range(D)]
     if isinstance(sess, MegaDecodeSession) and sess.select is not None:
+        # the whole decode as one graph replay (None: a tie in some row's head)
         toks = sess.greedy(start_symbol, ngram, theta)
         if toks is None:
-            # a tie in some row's head: step by step, every dialogue's row head from the pinned block (row d = dialogue d at width 1)
+            # step by step: every dialogue's row head (largest log-probability, its column; row d = dialogue d at width 1) arrives in a
+            # pinned block — one replay and one stream synchronisation per token, no argmax launch, no .item()
             rows = list(range(D))
             for l in range(1, max_len):
                 sess.step_extend(l, rows, [y[-1] for y in ys], rows)
-                if constrained:
+                if constrained:          # (the head the pass took is of the unconstrained row)
                     _constrain_step(sess, [(d_, ys[d_][1:]) for d_ in rows], ngram, theta)
                     top = ops.topk_rows(sess.logp, 2, 0).cpu().numpy()
                 else:
@@ -1438,10 +1355,8 @@ def sample_decode_many(model, batch, max_len, start, eos, pad, *, samples=1, tem
     row_keys = [k * S + s for k in keys for s in range(S)]
     params = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), banned=tuple(int(b) for b in banned), eos=int(eos),
                   min_len=int(min_len))
-    auto = kv_cache is None
-    log = _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, auto, ngram, theta, mbr)
-    if log is None:                  # a poll of the persistent step timed out: the launch-per-sublayer pass
-        log = _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, False, ngram, theta, mbr)
+    log = _with_fallback(lambda mega: _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, mega,
+                                                     ngram, theta, mbr), kv_cache is None)
     tok, lp, u = log[:3]
     if trace is not None:
         trace.append((list(row_keys), tok.copy(), lp.copy(), u.copy()))
@@ -1465,7 +1380,6 @@ def sample_decode_many(model, batch, max_len, start, eos, pad, *, samples=1, tem
 def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, mega, ngram=0, theta=1.0, mbr=0):
     """The step log (tokens, log-probabilities, u — numpy, (max_len, rows)) of one sampling search, or None after a persistent-step timeout.
     With ``mbr`` the selection's expected utilities and order, each (D, S), follow the log."""
-    import numpy as np
     sess = _session(model, batch, max_len, S, pad, use_graph, max_len > KV_CACHE_FROM if kv_cache is None else kv_cache, select=None,
                     mega=mega and use_graph, mode="sample")
     if isinstance(sess, MegaDecodeSession):
@@ -1501,7 +1415,6 @@ def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params,
 
 def mbr_weights(scores, temperature=1.0):
     """The ``score`` weights of mbr_rerank: w_j = exp((s_j - max s) / temperature) / sum, float64, the sum in ascending j."""
-    import math
     top = max(scores)
     e = [math.exp((float(v) - float(top)) / float(temperature)) for v in scores]
     z = 0.0
@@ -1516,7 +1429,6 @@ def mbr_rerank(lists, ngram, weights="uniform", temperature=1.0, device=None):
     differ in length or be empty).  One launch for all dialogues.  ``ngram``: the maximum n-gram order, 1..4.  ``weights``: "uniform", or
     "score" — w_j = exp((s_j - max s) / temperature) / sum over the list, computed here in float64.
     Returns per dialogue its (tokens, score, expected utility) triples, largest expected utility first, equal ones in input order."""
-    import numpy as np
     lists = [list(l) for l in lists]
     if weights not in ("uniform", "score"):
         raise ValueError("mbr_rerank: weights is 'uniform' or 'score'")
@@ -1555,7 +1467,6 @@ def evaluate_responses(hyps, refs, device=None):
     most 128 tokens (ValueError names the first item that breaks a bound).  The whole corpus is one call whatever its size: the document
     frequencies are the corpus'.  Returns dict(Bleu_1 .. Bleu_4, ROUGE_L, CIDEr: floats; hyp_len, ref_len: the corpus sums of hypothesis
     and closest reference lengths; stats (Q, 10) int32, rouge (Q,), cider (Q,) float64 numpy arrays, per item)."""
-    import numpy as np
     hyps, refs = [list(h) for h in hyps], [[list(r) for r in rs] for rs in refs]
     if len(hyps) != len(refs):
         raise ValueError("evaluate_responses: one reference list per hypothesis (%d and %d)" % (len(hyps), len(refs)))

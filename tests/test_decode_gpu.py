@@ -440,3 +440,47 @@ def test_persistent_decode_falls_back_when_compute_units_are_taken(dev):
     assert D.MegaDecodeSession.FALLBACKS == before + 1 and not sess[0].timed_out()
     assert again == clean
     D._SESSIONS.clear()
+
+
+def many_dialogues(c, seeds):
+    """The one-dialogue batches of ``seeds``, and the same dialogues as ONE batch."""
+    raws = [one_dialogue(c, seed=s) for s in seeds]
+    cat = {k: (np.concatenate([r[k] for r in raws], 0) if k != "fts" else [np.concatenate([r["fts"][i] for r in raws], 0) for i in range(len(raws[0]["fts"]))])
+           for k in raws[0]}
+    return raws, cat
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16-persistent", "fp32-launch"])
+def test_greedy_decode_refuses_a_batch(dev, dtype):
+    """greedy_decode is the one-dialogue call (as beam_search_decode is): a batch of two raises ValueError on the persistent step, which
+    used to return dialogue 0 alone, and on the launch-per-sublayer pass alike."""
+    from mtn_amd import decode as D
+    c = fx.GOLDEN_CONFIGS["cfg1_query"]
+    model = build_model(c, dtype, dev).eval()
+    b = dev_batch(many_dialogues(c, (3, 6))[1], dev)
+    assert D.MegaDecodeSession.supported(model, b, 8, 1) == (dtype == torch.bfloat16)
+    with pytest.raises(ValueError):
+        D.greedy_decode(model, b, 8, fx.SOS, fx.PAD)
+    D._SESSIONS.clear()
+
+
+@pytest.mark.parametrize("ngram", [0, 2], ids=["plain", "no-repeat-2"])
+@pytest.mark.parametrize("dtype,use_graph", [(torch.float32, True), (torch.float32, False), (torch.bfloat16, True)],
+                         ids=["fp32-graph", "fp32-eager", "bf16-persistent"])
+def test_greedy_decode_is_row_of_greedy_decode_many(dev, dtype, use_graph, ngram):
+    """greedy_decode is greedy_decode_many on a batch of one: each of three dialogues decoded alone gives, token for token, its row of
+    the three decoded side by side.  The dialogues (seeds 3, 6, 9) are chosen on the oracle: over all their greedy steps the two largest
+    log-probabilities of a row are at least 0.028 apart (0.024 under no_repeat_ngram = 2, which rewrites two of the three rows), so no
+    argmax hangs on a tie."""
+    from mtn_amd import decode as D
+    c = fx.GOLDEN_CONFIGS["cfg1_query"]
+    model = build_model(c, dtype, dev).eval()
+    raws, cat = many_dialogues(c, (3, 6, 9))
+    D._SESSIONS.clear()
+    many = D.greedy_decode_many(model, dev_batch(cat, dev), 8, fx.SOS, fx.PAD, use_graph=use_graph, no_repeat_ngram=ngram)
+    assert many.shape == (3, 8)
+    assert any(isinstance(s[0], D.MegaDecodeSession) for s in D._SESSIONS.values()) == (dtype == torch.bfloat16)
+    for d, raw in enumerate(raws):
+        one = D.greedy_decode(model, dev_batch(raw, dev), 8, fx.SOS, fx.PAD, use_graph=use_graph, no_repeat_ngram=ngram)
+        assert one.shape == (1, 8) and torch.equal(one[0], many[d]), d
+    D._SESSIONS.clear()
