@@ -45,7 +45,8 @@ const char* mtn_last_error(void);
  * compute-unit count and bounds its polls in time (see there).
  * 114: mtn_assemble_tokens_desc gained the trailing field `row_len` (NULL = no cut; a zeroed struct keeps meaning that).
  * 115: new entry point mtn_sample_rows.  116: new entry point mtn_score_rows.  117: new entry point mtn_constrain_rows.
- * 121: new entry point mtn_mbr_select.  122: new entry points mtn_eval_metrics and mtn_eval_workspace_bytes. */
+ * 121: new entry point mtn_mbr_select.  122: new entry points mtn_eval_metrics and mtn_eval_workspace_bytes.
+ * 123: new entry points mtn_distill_fwd / _bwd.  124: new entry points mtn_lerp_f32, mtn_ema_step and mtn_swap_f32. */
 int mtn_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -581,6 +582,24 @@ int mtn_adam_step(int dtype, long n, float* p, const float* g, float* m, float* 
  * 4096): the parameters that the GEMM optimiser epilogue (mtn_adam_fuse) does not cover. */
 int mtn_adam_step_chunks(int dtype, int n_chunks, const long* off, const int* len, float* p, const float* g, float* m, float* v,
                          void* p_lp, const float* state, const float* grad_scale, float beta1, float beta2, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Averaging in weight space (version 124; csrc/average.hip), over fp32 buffers of n elements.  Stream-ordered, capturable into a
+ * hipGraph; nothing is allocated or synchronised.  Base pointers are 16-byte aligned; nothing outside [0, n) is touched.
+ *   mtn_lerp_f32: acc[i] = acc[i] + coef * (x[i] - acc[i]) as THREE separately rounded fp32 operations (subtract, multiply, add; never
+ *     an fma), so that numpy float32 reproduces it bit for bit.  x is read only.  The running mean of K inputs is K calls with
+ *     coef = w_k / (w_1 + ... + w_k).
+ *   mtn_ema_step: the same arithmetic with x = p and the coefficient computed on the device from the optimiser state mtn_noam_tick
+ *     maintains: t = state[0] (the step number after the tick: 1 on the first step), c = max(1 - decay, 9 / (10 + t)) in fp32, which is
+ *     1 - min(decay, (1 + t) / (10 + t)) — the usual warm-up, so that early steps do not pin the average to the initial weights.  Every
+ *     thread computes c itself (no second launch); coef_out (optional device float) receives it.  p and state are read only.
+ *   mtn_swap_f32: a[i] <-> b[i] in one pass.
+ * MTN_ERR_ARG, nothing launched: n < 0; a null or misaligned pointer (coef_out may be NULL); acc == x, ema == p or a == b; coef outside
+ * [0, 1] or not finite; decay outside [0, 1) or not finite.  n == 0 returns MTN_OK with nothing launched.
+ * ------------------------------------------------------------------------------------------ */
+int mtn_lerp_f32(long n, float* acc, const float* x, float coef, void* stream);
+int mtn_ema_step(long n, float* ema, const float* p, const float* state, float decay, float* coef_out, void* stream);
+int mtn_swap_f32(long n, float* a, float* b, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Device-side batch assembly (replaces the host padding of data_handler.py:206-274 `make_batch` and the mask passes of

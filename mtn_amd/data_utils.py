@@ -8,6 +8,8 @@ tensors stay on whatever device they were created on (no hard-coded ``.cuda()``)
 """
 from __future__ import annotations
 
+import contextlib
+import logging
 import os
 
 from typing import List, Optional
@@ -100,6 +102,8 @@ class FusedAdam:
         self.param_groups = [{"lr": 0.0, "params": list(model.parameters())}]
         self.grad_scale: Optional[torch.Tensor] = None                        # device scalar multiplied into every gradient
         self._aux_cache = {}                      # host-side chunk lists of the table launch's front tiles (ops.ParamGradQueue._table_aux)
+        self.ema: Optional[torch.Tensor] = None   # exponential moving average of the fp32 masters (enable_ema); None = off: nothing is launched
+        self.ema_decay = 0.0
 
     def tick(self, factor: float, model_size: int, warmup: int):
         L.check(L.load().mtn_noam_tick(self.state.data_ptr(), factor, model_size, warmup, self.betas[0], self.betas[1], L.stream_ptr()))
@@ -111,11 +115,31 @@ class FusedAdam:
             raise L.MtnHipError("model was re-flattened after the optimiser was built")
         return flat, flat_lp, grad, (None if flat_lp is flat else flat_lp.data_ptr())
 
+    # ---- averaging in weight space: an EMA of the masters, a per-element buffer like the moments
+    def enable_ema(self, decay: float):
+        """Keep ema <- ema + c (p - ema) after every update of the masters, c = max(1 - decay, 9 / (10 + step)) computed on the device
+        (include/mtn_hip.h mtn_ema_step), starting from a copy of the current masters.  The launches sit inside step() / step_rest() /
+        step_range(), so they are captured with the step and every TrainStep that shares this optimiser updates the one buffer."""
+        decay = float(decay)
+        if not 0.0 < decay < 1.0:
+            raise ValueError("FusedAdam.enable_ema: 0 < decay < 1, got %r" % (decay,))
+        flat, _, _ = self.model.flat_buffers()
+        if self.m.numel() != flat.numel() or self.m.device != flat.device:
+            raise L.MtnHipError("model was re-flattened after the optimiser was built")
+        self.ema, self.ema_decay = flat.detach().clone(), decay
+        return self
+
+    def _ema_update(self, flat, off: int, n: int):
+        if self.ema is not None:
+            L.check(L.load().mtn_ema_step(n, self.ema.data_ptr() + 4 * off, flat.data_ptr() + 4 * off, self.state.data_ptr(), self.ema_decay,
+                                          None, L.stream_ptr()))
+
     def step(self):
         flat, flat_lp, grad, lp_ptr = self._buffers()
         L.check(L.load().mtn_adam_step(L.dtype_code(self.model.compute_dtype), flat.numel(), flat.data_ptr(), grad.data_ptr(),
                                        self.m.data_ptr(), self.v.data_ptr(), lp_ptr, self.state.data_ptr(),
                                        L.ptr(self.grad_scale), self.betas[0], self.betas[1], self.eps, L.stream_ptr()))
+        self._ema_update(flat, 0, flat.numel())
         self.model.refresh_transposed()
 
     def step_range(self, off: int, n: int, write_lp: bool = False):
@@ -131,6 +155,7 @@ class FusedAdam:
         L.check(L.load().mtn_adam_step(L.dtype_code(self.model.compute_dtype), n, flat.data_ptr() + 4 * off, grad.data_ptr() + 4 * off,
                                        self.m.data_ptr() + 4 * off, self.v.data_ptr() + 4 * off, lp, self.state.data_ptr(),
                                        L.ptr(self.grad_scale), self.betas[0], self.betas[1], self.eps, L.stream_ptr()))
+        self._ema_update(flat, off, n)
 
     def step_range_lp(self, off: int, n: int):
         self.step_range(off, n, write_lp=True)
@@ -187,6 +212,7 @@ class FusedAdam:
             L.check(L.load().mtn_adam_step_chunks(L.dtype_code(m.compute_dtype), n, off.data_ptr(), ln.data_ptr(), flat.data_ptr(),
                                                   grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), lp_ptr, self.state.data_ptr(),
                                                   L.ptr(self.grad_scale), self.betas[0], self.betas[1], self.eps, L.stream_ptr()))
+        self._ema_update(flat, 0, flat.numel())    # by now the table launch and the GEMM epilogues have written every master
         if trest is not None:
             m.refresh_transposed(trest)
 
@@ -203,13 +229,65 @@ class FusedAdam:
             sh.gather(self.m)
             sh.gather(self.v)
             self.gather_masters()
+            if self.ema is not None:
+                sh.gather(self.ema)
         out = {"schedule": self.state.detach().cpu().clone(), "exp_avg": {}, "exp_avg_sq": {}}
+        if self.ema is not None:
+            out["ema"], out["ema_decay"] = {}, self.ema_decay
         names = {id(p): n for n, p in self.model.named_parameters()}
         for p, o in zip(self.model._flat_params, self.model._flat_offsets):
             n = names[id(p)]
             out["exp_avg"][n] = self.m[o:o + p.numel()].view(p.shape).detach().cpu().clone()
             out["exp_avg_sq"][n] = self.v[o:o + p.numel()].view(p.shape).detach().cpu().clone()
+            if self.ema is not None:
+                out["ema"][n] = self.ema[o:o + p.numel()].view(p.shape).detach().cpu().clone()
         return out
+
+    def _gather_average(self):
+        """Data parallel with the sharded optimiser: a rank updates the average of its own shards only, as it does the moments — make
+        the masters and the average whole on every rank.  A collective."""
+        sh = getattr(self, "_sharded", None)
+        if sh is not None:
+            self.gather_masters()
+            sh.gather(self.ema)
+
+    def ema_state_dict(self):
+        """The model's state dict in the reference's key schema with every parameter replaced by its average (what generate.py
+        loads); entries that are not parameters are the model's.  A collective under data parallelism: every rank calls it."""
+        if self.ema is None:
+            raise L.MtnHipError("ema_state_dict(): the average is off (enable_ema)")
+        self._buffers()
+        self._gather_average()
+        out = self.model.state_dict()
+        offs = {id(p): o for p, o in zip(self.model._flat_params, self.model._flat_offsets)}
+        for n, p in self.model.named_parameters(remove_duplicate=False):
+            if n in out:
+                o = offs[id(p)]
+                out[n] = self.ema[o:o + p.numel()].view(p.shape).detach().clone()
+        return out
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside the block the model computes with the averaged weights: masters and average are exchanged in place (mtn_swap_f32, no
+        third buffer) and the compute-dtype copy, the transposed copies and the LayerNorm fold vectors follow, as after
+        load_state_dict; on exit they are exchanged back, every byte as it was.  A collective under data parallelism."""
+        if self.ema is None:
+            raise L.MtnHipError("averaged_weights(): the average is off (enable_ema)")
+        self._buffers()
+        self._gather_average()
+        self._swap_average()
+        try:
+            yield self
+        finally:
+            self._swap_average()
+
+    def _swap_average(self):
+        m = self.model
+        flat = m._flat
+        L.check(L.load().mtn_swap_f32(flat.numel(), flat.data_ptr(), self.ema.data_ptr(), L.stream_ptr()))
+        m._flat_version = -1               # the masters changed under the model: recast and re-transpose, as prepare() does after load_state_dict
+        m._ln_fold_stale = True
+        m.prepare()
 
     def gather_masters(self):
         """Data parallel with the compute-dtype gather (dp.ShardedOptimizerSync): a rank keeps the fp32 master of its own shard of
@@ -227,6 +305,15 @@ class FusedAdam:
             n = names[id(p)]
             self.m[o:o + p.numel()].copy_(sd["exp_avg"][n].reshape(-1).to(self.m.device))
             self.v[o:o + p.numel()].copy_(sd["exp_avg_sq"][n].reshape(-1).to(self.v.device))
+        if self.ema is None:                       # the average is off here: a file that carries one loads as any other
+            return
+        if sd.get("ema") is not None:
+            for p, o in zip(self.model._flat_params, self.model._flat_offsets):
+                self.ema[o:o + p.numel()].copy_(sd["ema"][names[id(p)]].reshape(-1).to(self.ema.device))
+        else:
+            logging.getLogger("mtn_amd").info("optimiser state carries no weight average: the average starts from the loaded weights")
+            self.gather_masters()                  # (data parallel: foreign masters may be stale; every rank loads the same file)
+            self.ema.copy_(self.model.flat_buffers()[0])
 
 
 class NoamOpt:

@@ -298,6 +298,9 @@ SYMBOLS = {
     "mtn_noam_tick": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, _P]),
     "mtn_adam_step": (C.c_int, [C.c_int, C.c_long, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P]),
     "mtn_adam_step_chunks": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P]),
+    "mtn_lerp_f32": (C.c_int, [C.c_long, _P, _P, C.c_float, _P]),
+    "mtn_ema_step": (C.c_int, [C.c_long, _P, _P, _P, C.c_float, _P, _P]),
+    "mtn_swap_f32": (C.c_int, [C.c_long, _P, _P, _P]),
 }
 
 _lib = None

@@ -13,6 +13,7 @@ Three modes:
 One process per GPU under torchrun gives data parallelism (RCCL all-reduce of the flat gradient buffer).
 """
 import argparse
+import copy
 import logging
 import time
 
@@ -91,8 +92,13 @@ def parse(argv=None):
     p.add_argument("--distill-mode", default="prob", choices=["prob", "logprob"], help="how several teachers are combined (generate.py --ensemble-mode)")
     p.add_argument("--distill-alpha", default=0.5, type=float, help="loss = (1 - alpha) * label-smoothed KL + alpha * T^2 * KL(teacher || student)")
     p.add_argument("--distill-temperature", default=1.0, type=float, help="T: both distributions are softmax(. / T) in the soft term")
+    # averaging in weight space: an exponential moving average of the weights kept by the optimiser inside the step
+    p.add_argument("--ema-decay", default=0.0, type=float, metavar="D",
+                   help="0 < D < 1: keep ema += max(1 - D, 9 / (10 + step)) * (weights - ema) after every optimiser step; with --model every epoch "
+                        "also writes <model>_N_ema, validation runs a second time under the averaged weights and its best is kept as "
+                        "<model>_best_ema (0: off)")
     args = p.parse_args(argv)
-    err = distill_flag_error(args)
+    err = distill_flag_error(args) or ema_flag_error(args)
     if err:
         p.error(err)
     return args
@@ -127,6 +133,14 @@ def distill_flag_error(args):
             return "--distill-weights takes one weight per --distill-model entry (%d given for %d)" % (len(w), n)
         if not all(math.isfinite(x) and x >= 0 for x in w) or not any(x > 0 for x in w):
             return "--distill-weights must be finite and >= 0, and not all 0"
+    return None
+
+
+def ema_flag_error(args):
+    """What is wrong with --ema-decay, as one line (None: nothing).  0 = off."""
+    d = args.ema_decay
+    if d != 0.0 and not (0.0 < d < 1.0):           # (nan fails both comparisons)
+        return "--ema-decay must be 0 (off) or lie in (0, 1) (got %r)" % d
     return None
 
 
@@ -401,19 +415,21 @@ def main(argv=None):
         means = []
         if args.eager:
             opt = NoamOpt(args.d_model, 1, args.warmup_steps, FusedAdam(model))
+            if args.ema_decay:
+                opt.optimizer.enable_ema(args.ema_decay)
             lc = SimpleLossCompute(model.generator, model.auto_encoder_generator, LabelSmoothing(args.vocab_size, 1, 0.1), opt=opt,
                                    l=args.loss_l, grad_sync=sync)
         else:
             from .train_step import BucketedTrainer
             trainer = BucketedTrainer(model, corpus, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l,
-                                      bucket=args.bucket, grad_sync=sync, **distill)
+                                      bucket=args.bucket, grad_sync=sync, ema_decay=args.ema_decay, **distill)
         valid = None
         if args.valid_videos > 0 or valid_data is not None:
             vdata = valid_data if valid_data is not None else synthetic_corpus(args.valid_videos, args.vocab_size, args.ft_sizes, args.rand_seed + 1000)
             vidx, vn = make_batch_indices(vdata, batchsize=args.batch_size, max_length=max_len, separate_caption=True)
             valid = (DeviceCorpus(vdata, dev), vidx)
             logging.info("#validation sample = %d  #validation batch = %d", vn, len(vidx))
-        min_valid = 1.0e10
+        min_valid = min_valid_ema = 1.0e10
         the_opt = opt if args.eager else trainer.opt
         if args.resume:
             model.load_state_dict(torch.load(args.resume + ".pth.tar", map_location=dev), strict=False)
@@ -444,9 +460,16 @@ def main(argv=None):
                     torch.save(model_state, f"{args.model}_{epoch + 1}.pth.tar")
                     torch.save(opt_state, f"{args.model}_{epoch + 1}_opt.pth.tar")
                 del opt_state, model_state
+                if args.ema_decay:
+                    ema_state = the_opt.optimizer.ema_state_dict()       # (collective: every rank)
+                    if rank == 0:
+                        torch.save(ema_state, f"{args.model}_{epoch + 1}_ema.pth.tar")
+                    del ema_state
             if valid is not None:
                 best_state = model.state_dict() if args.model else None    # (collective) written by rank 0 alone if validation improves
                 from .data_utils import LabelSmoothing as _LS
+                # --cut-a: the second validation sees the truncations of the first and takes no draw from the run's stream
+                cut_ema = copy.deepcopy(cut) if args.ema_decay else None
                 vloss = validate(valid[0], valid[1], model, _LS(args.vocab_size, 1, 0.1), args.auto_encoder_ft, args.loss_l, cut)
                 if rank == 0:
                     print("epoch: %d validation loss: %f" % (epoch + 1, vloss))          # train.py:210
@@ -455,12 +478,27 @@ def main(argv=None):
                         min_valid = vloss
                         if args.model:
                             torch.save(best_state, f"{args.model}_best.pth.tar")
+                del best_state
+                if args.ema_decay:
+                    # the same validation under the averaged weights, with a minimum of its own; <model>_best stays chosen by the raw weights
+                    best_ema = the_opt.optimizer.ema_state_dict() if args.model else None      # (collective)
+                    with the_opt.optimizer.averaged_weights():
+                        vloss_ema = validate(valid[0], valid[1], model, _LS(args.vocab_size, 1, 0.1), args.auto_encoder_ft, args.loss_l, cut_ema)
+                    if rank == 0:
+                        print("epoch: %d validation loss (averaged weights): %f" % (epoch + 1, vloss_ema))
+                        if vloss_ema < min_valid_ema:
+                            print("validation loss (averaged weights) reduced %.4f -> %.4f" % (min_valid_ema, vloss_ema))
+                            min_valid_ema = vloss_ema
+                            if args.model:
+                                torch.save(best_ema, f"{args.model}_best_ema.pth.tar")
+                    del best_ema
         if world > 1:
             torch.distributed.destroy_process_group()
         return means
     Q, H, C, T, V = args.lens
     batch = synthetic_batch(args.vocab_size, args.batch_size, Q, H, C, T, [V] * len(args.ft_sizes), args.ft_sizes, device=dev, seed=1 + rank)
-    step = TrainStep(model, batch, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l, grad_sync=sync, **distill)
+    step = TrainStep(model, batch, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l, grad_sync=sync, ema_decay=args.ema_decay,
+                     **distill)
     ntok = int(batch.ntokens) * world
     for epoch in range(args.num_epochs):
         t0, tokens = time.time(), 0
@@ -485,6 +523,11 @@ def main(argv=None):
             if rank == 0:                         # masters of the other ranks' shards (a collective) — rank 0 alone writes
                 torch.save(model_state, f"{args.model}_{epoch + 1}.pth.tar")      # reference key schema
             del model_state
+            if args.ema_decay:
+                ema_state = step.opt.optimizer.ema_state_dict()
+                if rank == 0:
+                    torch.save(ema_state, f"{args.model}_{epoch + 1}_ema.pth.tar")
+                del ema_state
     if world > 1:
         torch.distributed.destroy_process_group()
 

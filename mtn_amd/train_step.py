@@ -58,7 +58,7 @@ class TrainStep:
     def __init__(self, model, batch, vocab: int, pad: int = 1, warmup: int = 4000, factor: float = 1.0, lam: float = 1.0,
                  smoothing: float = 0.1, grad_sync=None, use_graph: bool = True, overlap: Optional[bool] = None, opt=None,
                  dynamic_norms: bool = False, fuse_optimizer: Optional[bool] = None, teacher=None, distill_alpha: float = 0.5,
-                 distill_temperature: float = 1.0):
+                 distill_temperature: float = 1.0, ema_decay: float = 0.0):
         """``opt``: share an existing NoamOpt (several TrainSteps over one model, e.g. one per batch shape).
         ``dynamic_norms``: the batch tensors are refilled in place between steps, so the loss normalisers (token counts,
         train.py:35-39) are recomputed from them inside the step instead of once at construction.
@@ -71,10 +71,16 @@ class TrainStep:
         per target position, and the MAIN decoder stream's loss becomes (1 - distill_alpha) * label-smoothed KL + distill_alpha *
         T^2 * KL(teacher_T || student_T) (csrc/distill.hip; the auto-encoder streams keep the plain loss).  The teacher pass runs
         to completion before the student's forward starts and leaves nothing behind, so with distill_alpha == 0 the step is the
-        undistilled step bit for bit.  ``last_kd``: device scalar, the step's summed row KL over its target-token normaliser."""
+        undistilled step bit for bit.  ``last_kd``: device scalar, the step's summed row KL over its target-token normaliser.
+        ``ema_decay``: > 0 = the optimiser built here keeps an exponential moving average of the weights (FusedAdam.enable_ema); a
+        shared ``opt`` keeps whatever its owner enabled."""
         self.model, self.batch = model, batch
         self._init_teacher(teacher, distill_alpha, distill_temperature, vocab)
-        self.opt = opt if opt is not None else NoamOpt(model.decoder.layers[0].size, factor, warmup, FusedAdam(model))
+        if opt is None:
+            opt = NoamOpt(model.decoder.layers[0].size, factor, warmup, FusedAdam(model))
+            if ema_decay:
+                opt.optimizer.enable_ema(ema_decay)
+        self.opt = opt
         self.dynamic_norms = dynamic_norms
         self.crit = LabelSmoothing(vocab, pad, smoothing)
         self.lc = SimpleLossCompute(model.generator, model.auto_encoder_generator, self.crit, opt=None, l=lam, sync=False)
@@ -452,11 +458,14 @@ class BucketedTrainer:
     place on the device (data_handler.make_batch(out=...)) and replays its graph.  One optimiser state for all shapes."""
 
     def __init__(self, model, corpus, vocab_size: int, pad: int = 1, warmup: int = 4000, lam: float = 1.0, bucket: int = 8,
-                 grad_sync=None, max_shapes: int = 64, teacher=None, distill_alpha: float = 0.5, distill_temperature: float = 1.0):
+                 grad_sync=None, max_shapes: int = 64, teacher=None, distill_alpha: float = 0.5, distill_temperature: float = 1.0,
+                 ema_decay: float = 0.0):
         self.model, self.corpus, self.vocab, self.pad, self.lam = model, corpus, vocab_size, pad, lam
         self.teacher, self.distill_alpha, self.distill_temperature = teacher, distill_alpha, distill_temperature
         self.bucket, self.grad_sync, self.max_shapes = bucket, grad_sync, max_shapes
         self.opt = NoamOpt(model.decoder.layers[0].size, 1.0, warmup, FusedAdam(model))
+        if ema_decay:
+            self.opt.optimizer.enable_ema(ema_decay)
         self.steps = {}
         self.last_kd = None
 
