@@ -46,7 +46,8 @@ const char* mtn_last_error(void);
  * 114: mtn_assemble_tokens_desc gained the trailing field `row_len` (NULL = no cut; a zeroed struct keeps meaning that).
  * 115: new entry point mtn_sample_rows.  116: new entry point mtn_score_rows.  117: new entry point mtn_constrain_rows.
  * 121: new entry point mtn_mbr_select.  122: new entry points mtn_eval_metrics and mtn_eval_workspace_bytes.
- * 123: new entry points mtn_distill_fwd / _bwd.  124: new entry points mtn_lerp_f32, mtn_ema_step and mtn_swap_f32. */
+ * 123: new entry points mtn_distill_fwd / _bwd.  124: new entry points mtn_lerp_f32, mtn_ema_step and mtn_swap_f32.
+ * 125: new entry points mtn_wlosshead_fwd / _bwd, mtn_eval_table_build, mtn_eval_score_rows, mtn_scst_assemble and mtn_scst_advantage. */
 int mtn_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -554,6 +555,39 @@ typedef struct {
 int mtn_distill_fwd(const mtn_distill_args* args, void* stream);
 int mtn_distill_bwd(int dtype, const mtn_distill_args* args, void* stream);
 
+/* Loss head with signed row weights (version 125; csrc/scst.hip): the policy-gradient loss of self-critical sequence training
+ * (Rennie et al. 2017), where a sampled row's weight is -(reward - baseline).  Every field of mtn_losshead_args keeps its meaning.
+ * roww[s] is a device array of rows[s] floats, 4-byte aligned, NULL = every weight of segment s is 1.  smoothing_seg[s] >= 0 is the label
+ * smoothing of segment s (0: KL_ls = -log p(target) on a live row); smoothing_seg[s] < 0 = the segment takes `smoothing`.  With KL_ls, td
+ * and the zeroed rows the loss head's (the lone-<pad> quirk included) at the segment's smoothing, scale = coef[s] / *norm[s], w = roww[s][row]:
+ *   rowloss = scale w KL_ls                                 lse = as mtn_losshead_fwd writes it (it does not depend on w)
+ *   bwd:      dlogits_j = *gloss scale w (softmax_j(z) sum(td) - td_j); columns V..ldd-1 are +0.0
+ * w may be negative or zero; a row with w == 0 writes rowloss = +0.0 and a dlogits row of +0.0, as a zeroed <pad> row does.  A non-finite
+ * weight is device data and is NOT checked: its rowloss and dlogits row are not finite.
+ * A segment with roww == NULL and the loss head's smoothing runs losshead.hip's arithmetic, statement for statement: lse, rowloss and dlogits
+ * are those of mtn_losshead_fwd / _bwd on the same inputs bit for bit.
+ * MTN_ERR_ARG, nothing launched: whatever mtn_losshead_fwd / _bwd refuse; a roww pointer that is not 4-byte aligned; a smoothing_seg that is
+ * NaN. */
+typedef struct {
+    int n_seg;
+    int rows[MTN_LOSSHEAD_MAX_SEG];
+    const long* target[MTN_LOSSHEAD_MAX_SEG];
+    const float* norm[MTN_LOSSHEAD_MAX_SEG];
+    float coef[MTN_LOSSHEAD_MAX_SEG];
+    int V, ldz, pad;
+    float smoothing;
+    const float* logits;
+    float* lse;
+    float* rowloss;
+    const float* gloss; /* backward: device scalar dL/dloss */
+    void* dlogits;
+    int ldd;
+    const float* roww[MTN_LOSSHEAD_MAX_SEG];
+    float smoothing_seg[MTN_LOSSHEAD_MAX_SEG];
+} mtn_wlosshead_args;
+int mtn_wlosshead_fwd(const mtn_wlosshead_args* args, void* stream);
+int mtn_wlosshead_bwd(int dtype, const mtn_wlosshead_args* args, void* stream);
+
 /* Transposed compute-dtype weight copies (operand of dX = dY W on the LDS-DMA GEMM path): for each descriptor the
  * [rows, cols] matrix at src+off is written as [cols, rows] at dst+dst_off (v111: the copies have a compact buffer of
  * their own — by default only the W_o^T matrices are kept).  `descs_device` is a DEVICE array (built once),
@@ -873,6 +907,64 @@ typedef struct {
 } mtn_eval_args;
 long mtn_eval_workspace_bytes(int Q, int R, int L);
 int mtn_eval_metrics(const mtn_eval_args* args /* host */, void* stream);
+/* Rewards against a FIXED reference corpus (version 125; csrc/scst.hip with the device code of mtn_eval_metrics, csrc/eval_common.h).
+ * mtn_eval_metrics rebuilds its document-frequency table from the evaluated items on every call; a training loop scores a few sampled
+ * rows per step against a corpus that never changes.  The corpus is Qc items laid out as mtn_eval_args' ref / ref_len / n_ref (ref
+ * [Qc][R][ldl], the same clamping, R <= 8, L <= 128) and stays in device memory, untouched, as long as the table is used: the table's keys
+ * point into it.
+ *   mtn_eval_table_build   two launches (clear, table): the df table of mtn_eval_metrics over the Qc items, into `workspace` (16-byte
+ *                          aligned, at least mtn_eval_workspace_bytes(Qc, R, L) bytes).  Reads none of the fields from N on.
+ *   mtn_eval_score_rows    ONE launch, a workgroup per hypothesis: hyp [N][ldl] with hyp_len [N] (clamped to [0, L]); hypothesis n is
+ *                          scored against the references of corpus item item[n] (device int32; any order, repeats allowed; clamped to
+ *                          [0, Qc) on the device).  stats [N][10], rouge [N] and cider [N] are, definition for definition, the per-item
+ *                          outputs of mtn_eval_metrics with Q = Qc and df = the corpus table's; with N = Qc, item[n] = n they are its bytes.
+ *                          The launch reads the table and writes nothing into it; no atomics; all arithmetic is double with fixed-order
+ *                          sums: two calls give the same bytes.  `workspace` must hold what mtn_eval_table_build left for the same
+ *                          Qc, R, L, ldl and ref (not checked: device memory).
+ * MTN_ERR_ARG (nothing is launched): a null required buffer, Qc < 1, R outside 1..8, L outside 1..128, ldl < L, Qc R L > 2^28, a workspace
+ * that is null, misaligned or too small; for mtn_eval_score_rows also N < 1. */
+typedef struct {
+    int Qc, R, L; long ldl;
+    const int* ref; const int* ref_len; const int* n_ref;         /* device: [Qc][R][ldl], [Qc][R], [Qc] */
+    void* workspace; long workspace_bytes;                        /* device: the table */
+    int N;
+    const int* hyp; const int* hyp_len; const int* item;          /* device: [N][ldl], [N], [N] */
+    int* stats; double* rouge; double* cider;                     /* device: [N][10], [N], [N] */
+} mtn_eval_rows_args;
+int mtn_eval_table_build(const mtn_eval_rows_args* args /* host */, void* stream);
+int mtn_eval_score_rows(const mtn_eval_rows_args* args /* host */, void* stream);
+/* Self-critical sequence training, the two launches between the sampling search and the train step (version 125; csrc/scst.hip).
+ * mtn_scst_assemble: the sample log log_tok [L][rows] (as mtn_sample_rows writes it) -> teacher-forcing targets and reward inputs, one
+ * launch, a wave per row.  Row r is cut at its first <eos>: n = the smallest l with log_tok[l][r] == eos, or L - 1 when there is none (a
+ * row without <eos> keeps L - 1 tokens: decode.py sample_decode_many's rule); y = log_tok[0..n-1][r].  Written, T >= L and ldh >= L:
+ *   trg   [rows][T] (int64)  = sos, y_0 .. y_{n-1}, then pad          trg_y [rows][T] (int64) = y_0 .. y_{n-1}, eos, then pad
+ *   hyp   [rows][ldh] (int32) = y_0 .. y_{n-1}, then pad up to column L - 1 (columns L..ldh-1 are left alone);  hyp_len [rows] = n
+ * MTN_ERR_ARG (nothing is launched): a null buffer, rows < 1, L < 1, T < L, ldh < L.
+ * mtn_scst_advantage: rewards -> the signed row weights mtn_wlosshead reads, one launch.  reward [D][S] (double) is the reward of sample s of
+ * dialogue d; b_ds = baseline[d] where `baseline` (double [D], e.g. the reward of the greedy response) is given, else the leave-one-out
+ * mean of the other S - 1 rewards of dialogue d (Luo 2020): (sum over s' != s, ascending s', in double) / (S - 1).  Written:
+ *   roww [D S][T] (float)   every target row of sample (d, s), i.e. roww[(d S + s) T + t] for all t: (float)(-(r_ds - b_ds))
+ *   adv  [D][S]   (double, optional)   r_ds - b_ds
+ *   mean_reward, mean_baseline (double device scalars)   (sum_d (sum_s x_ds)) / (D S), inner sums in ascending s, then ascending d
+ * A dialogue whose rewards are equal (and whose partial sums are exact, as for S = 2) gets weights of magnitude 0.
+ * MTN_ERR_ARG (nothing is launched): a null required buffer, D outside 1..1024, S outside 1..64, S < 2 without a baseline, T < 1. */
+typedef struct {
+    int rows, L, T;
+    const int* log_tok;                 /* device: [L][rows] */
+    int sos, eos, pad;
+    long* trg; long* trg_y;             /* device: [rows][T] */
+    int* hyp; long ldh; int* hyp_len;   /* device: [rows][ldh], [rows] */
+} mtn_scst_assemble_args;
+int mtn_scst_assemble(const mtn_scst_assemble_args* args /* host */, void* stream);
+typedef struct {
+    int D, S, T;
+    const double* reward;               /* device: [D][S] */
+    const double* baseline;             /* device: [D], or NULL = leave-one-out mean */
+    float* roww;                        /* device: [D S][T] */
+    double* adv;                        /* device: [D][S], or NULL */
+    double* mean_reward; double* mean_baseline; /* device scalars */
+} mtn_scst_advantage_args;
+int mtn_scst_advantage(const mtn_scst_advantage_args* args /* host */, void* stream);
 /* Generator (mtn.py:62-69) at inference: out[row][c] = x[row][c] - logsumexp(x[row][0..V-1]) over logit rows x [rows, V] (row
  * strides ldx / ldo; out may be x).  The logits themselves are one mtn_gemm (x W^T + b, fp32 out). */
 int mtn_log_softmax_rows(const float* x, int rows, int V, long ldx, float* out, long ldo, void* stream);

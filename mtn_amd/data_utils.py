@@ -379,7 +379,7 @@ class SimpleLossCompute:
         self.opt, self.l, self.sync, self.grad_sync, self.fused = opt, l, sync, grad_sync, fused
         self.last_kd_sum = None
 
-    def _fused_loss(self, x, y, norm, ae_x, ae_y, ae_norm, teacher_logp=None, alpha=0.0, temperature=1.0):
+    def _fused_loss(self, x, y, norm, ae_x, ae_y, ae_norm, teacher_logp=None, alpha=0.0, temperature=1.0, row_weights=None, smoothing=None):
         """Generator + log-softmax + label-smoothed KL + weighted sum as the fused HIP loss head (ops.GeneratorLossFn).
         Returns None when the fused path does not apply (CPU tensors, un-flattened model, vocab not a multiple of 8,
         foreign criterion): the caller then composes the same value from PyTorch ops."""
@@ -409,25 +409,59 @@ class SimpleLossCompute:
         if teacher_logp is not None:            # the main stream only: the auto-encoder streams keep the plain loss
             spec["teacher"] = [teacher_logp.reshape(-1, teacher_logp.size(-1))] + [None] * (len(xs) - 1)
             spec["alpha"], spec["temperature"] = float(alpha), float(temperature)
+        if row_weights is not None or smoothing is not None:      # the main stream only, as the teacher
+            w = None if row_weights is None else row_weights.detach().reshape(-1)
+            spec["row_weights"] = [w] + [None] * (len(xs) - 1)
+            spec["smoothing_seg"] = [smoothing] + [None] * (len(xs) - 1)
         out = ops.GeneratorLossFn.apply(spec, *xs)
         self.last_kd_sum = spec.get("kd_sum")
         return out
 
-    def loss(self, x, y, norm, ae_x=None, ae_y=None, ae_norm=None, teacher_logp=None, alpha=0.0, temperature=1.0):
+    def _weighted_rows(self, logp, y, row_weights, smoothing):
+        """The composed form of the weighted loss head (include/mtn_hip.h mtn_wlosshead_args): sum_rows w KL_ls at ``smoothing``."""
+        crit = self.criterion
+        V, pad = logp.size(-1), crit.padding_idx
+        sm = float(crit.smoothing if smoothing is None else smoothing)
+        td = torch.full_like(logp, sm / (V - 2))
+        td.scatter_(1, y.unsqueeze(1), 1.0 - sm)
+        td[:, pad] = 0
+        is_pad = y == pad
+        if int((torch.arange(y.numel(), device=y.device) * is_pad).sum()) > 0:      # label_smoothing.py:29, the lone-<pad> quirk
+            td[is_pad] = 0
+        kl = (td * (torch.where(td > 0, td, torch.ones_like(td)).log() - logp)).sum(1)
+        return kl.sum() if row_weights is None else (row_weights.detach().reshape(-1).to(kl.dtype) * kl).sum()
+
+    def loss(self, x, y, norm, ae_x=None, ae_y=None, ae_norm=None, teacher_logp=None, alpha=0.0, temperature=1.0, row_weights=None,
+             smoothing=None):
         """``teacher_logp``: (rows, V) fp32 teacher log-probabilities (or logits: they are normalised) for the main stream — word-level
         knowledge distillation, loss = (1 - alpha) KL_ls + alpha T^2 KL(softmax(q / T) || softmax(z / T)) over the rows whose target is
         not <pad>, both over ``norm`` (include/mtn_hip.h mtn_distill_args).  alpha == 0 is the plain loss.  ``last_kd_sum`` is left
-        holding the sum of the rows' KL (None without a teacher)."""
+        holding the sum of the rows' KL (None without a teacher).
+        ``row_weights``: one fp32 weight per main-stream row (signed; no gradient flows into it), loss = sum_rows w KL_ls / norm — the
+        policy-gradient loss of self-critical sequence training when w = -(reward - baseline); ``smoothing``: the main stream's label
+        smoothing in the place of the criterion's (0: KL_ls = -log p(target)).  The auto-encoder streams keep the plain loss.  Not
+        together with a teacher (include/mtn_hip.h mtn_wlosshead_args)."""
         if teacher_logp is not None and not (0.0 <= float(alpha) <= 1.0 and 0.0 < float(temperature) < float("inf")):
             raise ValueError("distillation: alpha in [0, 1] and a finite temperature > 0")
+        weighted = row_weights is not None or smoothing is not None
+        if weighted and teacher_logp is not None:
+            raise ValueError("row weights and teacher soft targets do not combine")
+        if smoothing is not None and not (0.0 <= float(smoothing) <= 1.0):
+            raise ValueError("smoothing in [0, 1]")
+        if row_weights is not None and row_weights.numel() != y.numel():
+            raise ValueError("row_weights: one weight per target row")
         self.last_kd_sum = None
-        fused = self._fused_loss(x, y, norm, ae_x, ae_y, ae_norm, teacher_logp, alpha, temperature) if self.fused else None
+        fused = self._fused_loss(x, y, norm, ae_x, ae_y, ae_norm, teacher_logp, alpha, temperature, row_weights,
+                                 None if smoothing is None else float(smoothing)) if self.fused else None
         if fused is not None:
             return fused
         if teacher_logp is not None and float(alpha) == 0.0:
             teacher_logp = None                 # as the fused head: the teacher is not read, nothing is multiplied by (1 - alpha)
         out = self.generator(x)
-        loss = self.criterion(out.reshape(-1, out.size(-1)), y.reshape(-1)) / norm.float()
+        if weighted:
+            loss = self._weighted_rows(out.reshape(-1, out.size(-1)), y.reshape(-1), row_weights, smoothing) / norm.float()
+        else:
+            loss = self.criterion(out.reshape(-1, out.size(-1)), y.reshape(-1)) / norm.float()
         if teacher_logp is not None:
             # the composed form of the fused head's soft term: the generator's output is log_softmax(z), and log_softmax(logp / T) ==
             # log_softmax(z / T) (the row's log-sum-exp is a common shift)

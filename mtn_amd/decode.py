@@ -1377,9 +1377,13 @@ def sample_decode_many(model, batch, max_len, start, eos, pad, *, samples=1, tem
     return results
 
 
-def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, mega, ngram=0, theta=1.0, mbr=0):
+def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params, use_graph, kv_cache, mega, ngram=0, theta=1.0, mbr=0,
+                   on_device=False):
     """The step log (tokens, log-probabilities, u — numpy, (max_len, rows)) of one sampling search, or None after a persistent-step timeout.
-    With ``mbr`` the selection's expected utilities and order, each (D, S), follow the log."""
+    With ``mbr`` the selection's expected utilities and order, each (D, S), follow the log.  ``on_device`` (launch-per-sublayer pass, no
+    mbr): the session's device log itself, valid until the session's next search — what the train step's reward launches read."""
+    if on_device and (mega or mbr):
+        raise ValueError("_sample_search: the device log is the launch-per-sublayer pass', without mbr")
     sess = _session(model, batch, max_len, S, pad, use_graph, max_len > KV_CACHE_FROM if kv_cache is None else kv_cache, select=None,
                     mega=mega and use_graph, mode="sample")
     if isinstance(sess, MegaDecodeSession):
@@ -1410,6 +1414,8 @@ def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params,
     if mbr:                          # once, after the token loop, on the device log
         expected, _, order, _ = ops.mbr_select(mbr, log_tok=log[0], sets=D, eos=params["eos"])
         return tuple(t.cpu().numpy() for t in log + (expected, order))
+    if on_device:
+        return log
     return tuple(t.cpu().numpy() for t in log)
 
 

@@ -100,6 +100,10 @@ class DistillHeadArgs(C.Structure):
                                         ("rowkd", C.c_void_p)]
 
 
+class WLossHeadArgs(C.Structure):
+    _fields_ = LossHeadArgs._fields_ + [("roww", C.c_void_p * 4), ("smoothing_seg", C.c_float * 4)]
+
+
 class TransposeDesc(C.Structure):
     _fields_ = [("off", C.c_long), ("rows", C.c_int), ("cols", C.c_int), ("tile_start", C.c_int), ("reserved", C.c_int), ("dst_off", C.c_long)]
 
@@ -199,6 +203,22 @@ class EvalArgs(C.Structure):
                 ("stats", C.c_void_p), ("rouge", C.c_void_p), ("cider", C.c_void_p), ("corpus", C.c_void_p), ("df_of_ref", C.c_void_p)]
 
 
+class EvalRowsArgs(C.Structure):
+    _fields_ = [("Qc", C.c_int), ("R", C.c_int), ("L", C.c_int), ("ldl", C.c_long), ("ref", C.c_void_p), ("ref_len", C.c_void_p),
+                ("n_ref", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_long), ("N", C.c_int), ("hyp", C.c_void_p),
+                ("hyp_len", C.c_void_p), ("item", C.c_void_p), ("stats", C.c_void_p), ("rouge", C.c_void_p), ("cider", C.c_void_p)]
+
+
+class ScstAssembleArgs(C.Structure):
+    _fields_ = [("rows", C.c_int), ("L", C.c_int), ("T", C.c_int), ("log_tok", C.c_void_p), ("sos", C.c_int), ("eos", C.c_int),
+                ("pad", C.c_int), ("trg", C.c_void_p), ("trg_y", C.c_void_p), ("hyp", C.c_void_p), ("ldh", C.c_long), ("hyp_len", C.c_void_p)]
+
+
+class ScstAdvantageArgs(C.Structure):
+    _fields_ = [("D", C.c_int), ("S", C.c_int), ("T", C.c_int), ("reward", C.c_void_p), ("baseline", C.c_void_p), ("roww", C.c_void_p),
+                ("adv", C.c_void_p), ("mean_reward", C.c_void_p), ("mean_baseline", C.c_void_p)]
+
+
 class LnFinalizeDesc(C.Structure):
     _fields_ = [("partial", C.c_void_p), ("nparts", C.c_int), ("d", C.c_int), ("da2", C.c_void_p), ("db2", C.c_void_p)]
 
@@ -294,6 +314,12 @@ SYMBOLS = {
     "mtn_losshead_bwd": (C.c_int, [C.c_int, C.POINTER(LossHeadArgs), _P]),
     "mtn_distill_fwd": (C.c_int, [C.POINTER(DistillHeadArgs), _P]),
     "mtn_distill_bwd": (C.c_int, [C.c_int, C.POINTER(DistillHeadArgs), _P]),
+    "mtn_wlosshead_fwd": (C.c_int, [C.POINTER(WLossHeadArgs), _P]),
+    "mtn_wlosshead_bwd": (C.c_int, [C.c_int, C.POINTER(WLossHeadArgs), _P]),
+    "mtn_eval_table_build": (C.c_int, [C.POINTER(EvalRowsArgs), _P]),
+    "mtn_eval_score_rows": (C.c_int, [C.POINTER(EvalRowsArgs), _P]),
+    "mtn_scst_assemble": (C.c_int, [C.POINTER(ScstAssembleArgs), _P]),
+    "mtn_scst_advantage": (C.c_int, [C.POINTER(ScstAdvantageArgs), _P]),
     "mtn_transpose_group": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
     "mtn_noam_tick": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, _P]),
     "mtn_adam_step": (C.c_int, [C.c_int, C.c_long, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P]),

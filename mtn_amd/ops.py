@@ -1266,6 +1266,144 @@ def eval_metrics(hyp, hyp_len, ref, ref_len, n_ref, *, workspace=None, out=None,
     return stats, rouge, cider, corpus, df_of_ref
 
 
+# ------------------------------------------------------------------------------------------ self-critical sequence training (csrc/scst.hip)
+def _eval_corpus_args(fn, ref, ref_len, n_ref, workspace):
+    """The corpus half of an EvalRowsArgs: ``ref`` (Qc, R, >= L) int32 as eval_metrics takes it, ``workspace`` a uint8 table or None."""
+    _require_cuda(ref, ref_len, n_ref)
+    if (ref.dim() != 3 or ref.dtype != torch.int32 or ref.numel() == 0 or (ref.size(2) > 1 and ref.stride(2) != 1)
+            or ref.stride(1) < ref.size(2) or ref.stride(0) != ref.size(1) * ref.stride(1)):
+        raise ValueError(fn + ": ref int32 (Qc, R, L), non-empty, with unit token stride and rows of one stride")
+    Qc, R, Lh = ref.shape
+    if not 1 <= R <= EVAL_MAX_REF or not 1 <= Lh <= EVAL_MAX_LEN:
+        raise ValueError(fn + ": at most 8 references per item, sentences of at most 128 tokens")
+    for t, shape, name in ((ref_len, (Qc, R), "ref_len (Qc, R)"), (n_ref, (Qc,), "n_ref (Qc,)")):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(fn + ": %s int32, contiguous" % name)
+    need = eval_workspace_bytes(Qc, R, Lh)
+    if need <= 0:
+        raise ValueError(fn + ": Qc * R * L is at most 2^28")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=ref.device)
+    _require_cuda(workspace)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 16:
+        raise ValueError(fn + ": workspace uint8, contiguous, 16-byte aligned, at least eval_workspace_bytes(Qc, R, L) = %d bytes" % need)
+    a = L.EvalRowsArgs()
+    a.Qc, a.R, a.L, a.ldl = Qc, R, Lh, ref.stride(1)
+    a.ref, a.ref_len, a.n_ref = ref.data_ptr(), ref_len.data_ptr(), n_ref.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    return a, workspace
+
+
+def eval_table_build(ref, ref_len, n_ref, workspace=None):
+    """The document-frequency table of a FIXED reference corpus (include/mtn_hip.h mtn_eval_table_build), built once: ``ref`` (Qc, R, >= L)
+    int32, ``ref_len`` (Qc, R), ``n_ref`` (Qc,) as eval_metrics takes them.  Returns the table (a uint8 tensor; ``workspace`` when given).
+    The table points into ``ref``: keep ref, ref_len and n_ref alive and unchanged for as long as eval_score_rows reads the table."""
+    a, workspace = _eval_corpus_args("eval_table_build", ref, ref_len, n_ref, workspace)
+    L.check(L.load().mtn_eval_table_build(C.byref(a), L.stream_ptr()))
+    return workspace
+
+
+def eval_score_rows(hyp, hyp_len, item, ref, ref_len, n_ref, table, out=None):
+    """CIDEr, ROUGE-L and the BLEU integers of N hypotheses, hypothesis n against corpus item ``item[n]`` with the corpus table's df and
+    Q = Qc (mtn_eval_score_rows: one launch, no atomics, equal bytes from equal inputs).  ``hyp`` (N, L) int32 with the row stride of
+    ``ref``, ``hyp_len`` and ``item`` (N,) int32, ``table`` = eval_table_build(ref, ref_len, n_ref).  ``out`` = (stats (N, 10) int32,
+    rouge (N,) float64, cider (N,) float64), allocated when None.  Returns (stats, rouge, cider)."""
+    a, _ = _eval_corpus_args("eval_score_rows", ref, ref_len, n_ref, table)
+    _require_cuda(hyp, hyp_len, item)
+    if hyp.dim() != 2 or hyp.dtype != torch.int32 or hyp.size(0) < 1 or hyp.size(1) != a.L or (a.L > 1 and hyp.stride(1) != 1) or (
+            hyp.size(0) > 1 and hyp.stride(0) != a.ldl):
+        raise ValueError("eval_score_rows: hyp int32 (N, L) with unit token stride and the row stride of ref")
+    N = hyp.size(0)
+    for t, name in ((hyp_len, "hyp_len"), (item, "item")):
+        if t.dtype != torch.int32 or tuple(t.shape) != (N,) or not t.is_contiguous():
+            raise ValueError("eval_score_rows: %s int32 (N,), contiguous" % name)
+    dev = ref.device
+    if out is None:
+        out = (torch.empty(N, 10, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.float64, device=dev),
+               torch.empty(N, dtype=torch.float64, device=dev))
+    stats, rouge, cider = out
+    _require_cuda(stats, rouge, cider)
+    if (stats.dtype != torch.int32 or tuple(stats.shape) != (N, 10) or rouge.dtype != torch.float64 or cider.dtype != torch.float64
+            or rouge.numel() != N or cider.numel() != N or not all(t.is_contiguous() for t in out)):
+        raise ValueError("eval_score_rows: out = (stats int32 (N, 10), rouge float64 (N,), cider float64 (N,)), contiguous")
+    a.N, a.hyp, a.hyp_len, a.item = N, hyp.data_ptr(), hyp_len.data_ptr(), item.data_ptr()
+    a.stats, a.rouge, a.cider = stats.data_ptr(), rouge.data_ptr(), cider.data_ptr()
+    L.check(L.load().mtn_eval_score_rows(C.byref(a), L.stream_ptr()))
+    return stats, rouge, cider
+
+
+def scst_assemble(log_tok, sos, eos, pad, T=None, out=None, hyp_stride=None):
+    """The sample log ``log_tok`` (L, rows) int32 (as sample_rows writes it) cut at each row's first <eos> (L - 1 tokens without one) and
+    written as teacher-forcing targets: (trg (rows, T) int64 = <sos>, y.., <pad>..; trg_y (rows, T) int64 = y.., <eos>, <pad>..;
+    hyp (rows, L) int32 with row stride ``hyp_stride`` (default L) = y.., <pad>..; hyp_len (rows,) int32), T >= L (default L).
+    ``out``: the four tensors, allocated when None.  One launch (mtn_scst_assemble), no host read."""
+    _require_cuda(log_tok)
+    if log_tok.dim() != 2 or log_tok.dtype != torch.int32 or not log_tok.is_contiguous() or log_tok.numel() == 0:
+        raise ValueError("scst_assemble: log_tok int32 (L, rows), contiguous, non-empty")
+    Lm, rows = log_tok.shape
+    T = Lm if T is None else int(T)
+    ldh = Lm if hyp_stride is None else int(hyp_stride)
+    if T < Lm or ldh < Lm:
+        raise ValueError("scst_assemble: T >= L and hyp_stride >= L")
+    dev = log_tok.device
+    if out is None:
+        out = (torch.empty(rows, T, dtype=torch.long, device=dev), torch.empty(rows, T, dtype=torch.long, device=dev),
+               torch.full((rows, ldh), int(pad), dtype=torch.int32, device=dev)[:, :Lm], torch.empty(rows, dtype=torch.int32, device=dev))
+    trg, trg_y, hyp, hyp_len = out
+    _require_cuda(trg, trg_y, hyp, hyp_len)
+    if any(t.dtype != torch.long or tuple(t.shape) != (rows, T) or not t.is_contiguous() for t in (trg, trg_y)):
+        raise ValueError("scst_assemble: trg, trg_y int64 (rows, T), contiguous")
+    if (hyp.dtype != torch.int32 or tuple(hyp.shape) != (rows, Lm) or (Lm > 1 and hyp.stride(1) != 1) or (rows > 1 and hyp.stride(0) != ldh)
+            or hyp_len.dtype != torch.int32 or tuple(hyp_len.shape) != (rows,) or not hyp_len.is_contiguous()):
+        raise ValueError("scst_assemble: hyp int32 (rows, L) with row stride hyp_stride, hyp_len int32 (rows,)")
+    a = L.ScstAssembleArgs()
+    a.rows, a.L, a.T, a.log_tok, a.sos, a.eos, a.pad = rows, Lm, T, log_tok.data_ptr(), int(sos), int(eos), int(pad)
+    a.trg, a.trg_y, a.hyp, a.ldh, a.hyp_len = trg.data_ptr(), trg_y.data_ptr(), hyp.data_ptr(), ldh, hyp_len.data_ptr()
+    L.check(L.load().mtn_scst_assemble(C.byref(a), L.stream_ptr()))
+    return trg, trg_y, hyp, hyp_len
+
+
+def scst_advantage(reward, T, baseline=None, roww=None, means=None, adv=None):
+    """Rewards -> signed row weights (mtn_scst_advantage): ``reward`` (D, S) float64; ``baseline`` (D,) float64 or None = the leave-one-out
+    mean of the dialogue's other rewards (S >= 2).  Writes ``roww`` — the first D * S * T floats of a contiguous float32 tensor, (D * S, T)
+    when allocated here — with -(r - b) on every target row of a sample, ``means`` (2,) float64 = mean reward, mean baseline, and ``adv``
+    (D, S) float64 = r - b when given (True allocates).  Returns (roww, means, adv or None)."""
+    _require_cuda(reward)
+    if reward.dim() != 2 or reward.dtype != torch.float64 or not reward.is_contiguous() or reward.numel() == 0:
+        raise ValueError("scst_advantage: reward float64 (D, S), contiguous, non-empty")
+    D, S = reward.shape
+    T = int(T)
+    if not (1 <= D <= 1024 and 1 <= S <= 64 and T >= 1) or (baseline is None and S < 2):
+        raise ValueError("scst_advantage: 1 <= D <= 1024, 1 <= S <= 64 (S >= 2 without a baseline), T >= 1")
+    dev = reward.device
+    a = L.ScstAdvantageArgs()
+    if baseline is not None:
+        _require_cuda(baseline)
+        if baseline.dtype != torch.float64 or baseline.numel() != D or not baseline.is_contiguous():
+            raise ValueError("scst_advantage: baseline float64 (D,), contiguous")
+        a.baseline = baseline.data_ptr()
+    if roww is None:
+        roww = torch.empty(D * S, T, dtype=torch.float32, device=dev)
+    if means is None:
+        means = torch.empty(2, dtype=torch.float64, device=dev)
+    if adv is True:
+        adv = torch.empty(D, S, dtype=torch.float64, device=dev)
+    _require_cuda(roww, means)
+    if roww.dtype != torch.float32 or not roww.is_contiguous() or roww.numel() < D * S * T:
+        raise ValueError("scst_advantage: roww float32, contiguous, at least D * S * T elements")
+    if means.dtype != torch.float64 or means.numel() != 2 or not means.is_contiguous():
+        raise ValueError("scst_advantage: means float64 (2,), contiguous")
+    if adv is not None:
+        _require_cuda(adv)
+        if adv.dtype != torch.float64 or adv.numel() != D * S or not adv.is_contiguous():
+            raise ValueError("scst_advantage: adv float64 (D, S), contiguous")
+        a.adv = adv.data_ptr()
+    a.D, a.S, a.T, a.reward, a.roww = D, S, T, reward.data_ptr(), roww.data_ptr()
+    a.mean_reward, a.mean_baseline = means.data_ptr(), means.data_ptr() + 8
+    L.check(L.load().mtn_scst_advantage(C.byref(a), L.stream_ptr()))
+    return roww, means, adv
+
+
 # ------------------------------------------------------------------------------------------ memory K/V, ahead of the layers
 def project_memories(items, lp_dtype, outs=None, n_now=None, order=None):
     """K|V projections (mtn.py:257-258) of CONSTANT memories for many sublayers at once: items = [(mem_lp (B,m,d) compute dtype,
@@ -1520,6 +1658,28 @@ def _distill_teachers(spec, rows, V, dev):
     return list(teachers)
 
 
+def _row_weights(spec, rows, dev):
+    """spec["row_weights"] / spec["smoothing_seg"] checked against the streams: None when neither is given (the plain loss head runs), else
+    (weights per stream: a tensor or None, smoothing per stream: a float, negative = the spec's smoothing)."""
+    weights, sms = spec.get("row_weights"), spec.get("smoothing_seg")
+    if (weights is None or all(w is None for w in weights)) and sms is None:
+        return None
+    weights = [None] * len(rows) if weights is None else list(weights)
+    sms = [-1.0] * len(rows) if sms is None else [-1.0 if s is None else float(s) for s in sms]
+    if len(weights) != len(rows) or len(sms) != len(rows):
+        raise ValueError("GeneratorLossFn: spec['row_weights'] and spec['smoothing_seg'] hold one entry per stream")
+    if any(math.isnan(s) for s in sms):
+        raise ValueError("GeneratorLossFn: a stream's smoothing is a number (negative: the spec's smoothing)")
+    for w, r in zip(weights, rows):
+        if w is None:
+            continue
+        if not (torch.is_tensor(w) and w.device == dev and w.dtype == torch.float32 and w.numel() == r and w.is_contiguous()):
+            raise ValueError("GeneratorLossFn: row weights are a contiguous fp32 tensor of one value per row on the logits' device")
+        if w.requires_grad:
+            raise ValueError("GeneratorLossFn: row weights carry no gradient (detach them)")
+    return weights, sms
+
+
 class GeneratorLossFn(torch.autograd.Function):
     """sum_i coef_i * KLDiv(log_softmax(x_i W_i^T + b_i), smooth(y_i)) / norm_i  — Generator (mtn.py:62-69) +
     LabelSmoothing (label_smoothing.py) + SimpleLossCompute's weighted sum (data_utils.py:133-144) as: one grouped cast,
@@ -1529,7 +1689,10 @@ class GeneratorLossFn(torch.autograd.Function):
     Knowledge distillation: ``spec["teacher"]`` = per stream a (rows_i, V) fp32 device tensor of teacher logits / log-probabilities or
     None, with ``spec["alpha"]`` and ``spec["temperature"]``.  With any teacher present the row kernels are mtn_distill_fwd / _bwd
     (csrc/distill.hip; include/mtn_hip.h) in the place of the two loss-head calls, casts and GEMMs unchanged, and ``spec["kd_sum"]`` is
-    left holding the device scalar sum_rows kd; with none the calls are exactly the loss head's."""
+    left holding the device scalar sum_rows kd; with none the calls are exactly the loss head's.
+    Signed row weights (self-critical sequence training): ``spec["row_weights"]`` = per stream a contiguous fp32 device tensor of one weight
+    per row or None (all ones), ``spec["smoothing_seg"]`` = per stream a smoothing or None (the spec's).  With either present the row
+    kernels are mtn_wlosshead_fwd / _bwd (csrc/scst.hip); not together with a teacher."""
 
     @staticmethod
     def forward(ctx, spec, *xs):
@@ -1580,7 +1743,10 @@ class GeneratorLossFn(torch.autograd.Function):
             probs.append(p)
         gemm(code, probs)
         teachers = _distill_teachers(spec, rows, V, dev)
-        A = L.LossHeadArgs() if teachers is None else L.DistillHeadArgs()
+        weighted = _row_weights(spec, rows, dev)
+        if teachers is not None and weighted is not None:
+            raise ValueError("GeneratorLossFn: row weights and teacher soft targets do not combine")
+        A = L.WLossHeadArgs() if weighted is not None else (L.LossHeadArgs() if teachers is None else L.DistillHeadArgs())
         A.n_seg = len(xs)
         norms = [n.float().reshape(1) if n.dtype != torch.float32 or n.dim() == 0 else n for n in spec["norms"]]
         targets = [t.contiguous().view(-1) for t in spec["targets"]]
@@ -1590,7 +1756,11 @@ class GeneratorLossFn(torch.autograd.Function):
         lse = torch.empty(R, device=dev, dtype=torch.float32)
         rowloss = torch.empty(R, device=dev, dtype=torch.float32)
         A.logits, A.lse, A.rowloss = logits.data_ptr(), lse.data_ptr(), rowloss.data_ptr()
-        if teachers is None:
+        if weighted is not None:
+            for i, (w, sm) in enumerate(zip(*weighted)):
+                A.roww[i], A.smoothing_seg[i] = L.ptr(w), sm
+            L.check(lib.mtn_wlosshead_fwd(C.byref(A), L.stream_ptr()))
+        elif teachers is None:
             L.check(lib.mtn_losshead_fwd(C.byref(A), L.stream_ptr()))
         else:
             rowkd = torch.empty(R, device=dev, dtype=torch.float32)
@@ -1600,7 +1770,7 @@ class GeneratorLossFn(torch.autograd.Function):
             A.alpha, A.temperature, A.rowkd = float(spec.get("alpha", 0.5)), float(spec.get("temperature", 1.0)), rowkd.data_ptr()
             L.check(lib.mtn_distill_fwd(C.byref(A), L.stream_ptr()))
             spec["kd_sum"] = rowkd.sum()
-        ctx.args, ctx.keep = A, (x_lp, logits, lse, norms, targets, teachers)
+        ctx.args, ctx.keep = A, (x_lp, logits, lse, norms, targets, teachers if weighted is None else weighted)
         ctx.meta = (spec, segs, rows, offs, d, V, R, code, [x.shape for x in xs])
         return rowloss.sum()
 
@@ -1615,7 +1785,9 @@ class GeneratorLossFn(torch.autograd.Function):
         gl = g.contiguous().float().reshape(1)
         dlogits = torch.empty(R, V, device=dev, dtype=lp)
         A.gloss, A.dlogits, A.ldd = gl.data_ptr(), dlogits.data_ptr(), V
-        if teachers is None:
+        if isinstance(A, L.WLossHeadArgs):
+            L.check(lib.mtn_wlosshead_bwd(code, C.byref(A), L.stream_ptr()))
+        elif teachers is None:
             L.check(lib.mtn_losshead_bwd(code, C.byref(A), L.stream_ptr()))
         else:
             L.check(lib.mtn_distill_bwd(code, C.byref(A), L.stream_ptr()))

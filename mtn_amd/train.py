@@ -97,8 +97,20 @@ def parse(argv=None):
                    help="0 < D < 1: keep ema += max(1 - D, 9 / (10 + step)) * (weights - ema) after every optimiser step; with --model every epoch "
                         "also writes <model>_N_ema, validation runs a second time under the averaged weights and its best is kept as "
                         "<model>_best_ema (0: off)")
+    # self-critical sequence training: sampled responses scored against the corpus' answers, row weight -(reward - baseline)
+    p.add_argument("--scst-samples", default=0, type=int, metavar="S",
+                   help="2..16: corpus mode trains on S sampled responses per dialogue, scored on the device against the corpus' answers "
+                        "(Rennie et al. 2017); responses have min(--max-length, 129) positions (0: off)")
+    p.add_argument("--scst-reward", default="cider", choices=["cider", "rouge"], help="the metric a sample is rewarded with")
+    p.add_argument("--scst-baseline", default="mean", choices=["mean", "greedy"],
+                   help="mean: the leave-one-out mean of the dialogue's other samples; greedy: the reward of the greedy response")
+    p.add_argument("--scst-temperature", default=1.0, type=float)
+    p.add_argument("--scst-top-k", default=0, type=int)
+    p.add_argument("--scst-top-p", default=1.0, type=float)
+    p.add_argument("--scst-xe-weight", default=0.0, type=float, metavar="W",
+                   help="> 0: the gold answer is one more row per dialogue with the constant weight W (smoothing 0)")
     args = p.parse_args(argv)
-    err = distill_flag_error(args) or ema_flag_error(args)
+    err = distill_flag_error(args) or ema_flag_error(args) or scst_flag_error(args)
     if err:
         p.error(err)
     return args
@@ -133,6 +145,38 @@ def distill_flag_error(args):
             return "--distill-weights takes one weight per --distill-model entry (%d given for %d)" % (len(w), n)
         if not all(math.isfinite(x) and x >= 0 for x in w) or not any(x > 0 for x in w):
             return "--distill-weights must be finite and >= 0, and not all 0"
+    return None
+
+
+def scst_flag_error(args, world=None):
+    """What is wrong with the --scst-* flags, or what they conflict with, as one line (None: nothing).  ``world``: the number of ranks
+    (None: what the launcher's WORLD_SIZE says)."""
+    import math
+    import os
+    S = args.scst_samples
+    if S == 0:
+        return None
+    if not 2 <= S <= 16:
+        return "--scst-samples must be 0 (off) or lie in 2..16 (got %r)" % S
+    if not (args.scst_temperature >= 0.0 and math.isfinite(args.scst_temperature)):
+        return "--scst-temperature must be finite and >= 0 (got %r)" % args.scst_temperature
+    if args.scst_top_k < 0:
+        return "--scst-top-k must be >= 0 (got %r)" % args.scst_top_k
+    if not 0.0 < args.scst_top_p <= 1.0:
+        return "--scst-top-p must lie in (0, 1] (got %r)" % args.scst_top_p
+    if not (args.scst_xe_weight >= 0.0 and math.isfinite(args.scst_xe_weight)):
+        return "--scst-xe-weight must be finite and >= 0 (got %r)" % args.scst_xe_weight
+    if args.max_length < 2:
+        return "--scst-samples needs --max-length >= 2, the positions of a sampled response (got %r)" % args.max_length
+    if args.distill_model:
+        return "--scst-samples does not combine with --distill-model: distillation under self-critical training is out of scope"
+    if world is None:
+        world = int(os.environ.get("WORLD_SIZE", "1") or 1)
+    if world > 1:
+        return "--scst-samples does not combine with more than one rank (%d): data parallelism under self-critical training is out of scope" % world
+    if not args.train_set and args.corpus_videos <= 0:
+        return ("--scst-samples does not combine with the fixed synthetic batch: rewards need a corpus of answers "
+                "(--train-set or --corpus-videos)")
     return None
 
 
@@ -241,11 +285,14 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
     """The same epoch on captured graphs (train_step.BucketedTrainer): lengths rounded up to the bucket, one graph per padded
     shape, batches assembled in place on the device; the host only syncs at the report interval.  ``cut``: the --cut-a
     RandomState (None = no truncation).  Returns (mean loss per token, target tokens of the epoch over all ranks).  ``stats``: a dict
-    that receives "kd", the epoch's mean distillation KL per token, when the trainer has a teacher."""
+    that receives "kd", the epoch's mean distillation KL per token, when the trainer has a teacher, and "reward" / "baseline", the
+    mean over the epoch's steps of the steps' mean reward and mean baseline, when it trains self-critically."""
     order = list(range(len(indices)))
     rng.shuffle(order)
     dev = trainer.corpus.device
     loss_sum = torch.zeros((), device=dev)
+    scst = getattr(trainer, "scst", None) is not None
+    rl_sum = torch.zeros(2, device=dev, dtype=torch.float64)
     kd_sum = torch.zeros((), device=dev) if trainer.teacher is not None else None
     tok_sum = torch.zeros((), device=dev, dtype=torch.int64)
     t0, tok0 = time.time(), 0
@@ -258,6 +305,8 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
         tok_sum += n_glob
         if kd_sum is not None:
             kd_sum += trainer.last_kd * n_glob
+        if scst:
+            rl_sum += torch.stack([trainer.last_reward, trainer.last_baseline])
         if (j + 1) % report_interval == 0 and rank == 0:
             ntok = int(tok_sum)
             dt = time.time() - t0
@@ -270,6 +319,8 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
     ntok = int(tok_sum)
     if kd_sum is not None and stats is not None:
         stats["kd"] = float(kd_sum) / max(1, ntok)
+    if scst and stats is not None:
+        stats["reward"], stats["baseline"] = (float(v) / max(1, len(order)) for v in rl_sum)
     return float(loss_sum) / max(1, ntok), ntok
 
 
@@ -348,6 +399,9 @@ def main(argv=None):
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(asctime)s %(levelname)s: %(message)s")
     cut_a = cut_a_applies(args)
     rank, world, local = dp.init_distributed()
+    err = scst_flag_error(args, world)
+    if err:
+        raise SystemExit("mtn_amd.train: " + err)
     local = local % torch.cuda.device_count()      # (several ranks may share a GPU in a gloo dry run)
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
@@ -413,7 +467,20 @@ def main(argv=None):
         # plan order), as the reference's global np.random after np.random.seed(--rand-seed) (train.py:109); per rank
         cut = cut_a_stream(args.rand_seed, rank) if cut_a else None
         means = []
-        if args.eager:
+        scst = None
+        if args.scst_samples:
+            # the corpus' tokenised answers, uploaded once, are the reference corpus: rewards are on model token ids, item = QA id
+            from .train_step import ScstConfig, corpus_reference
+            longest = -(-int(corpus.host_tok["trg"][2].max()) // args.bucket) * args.bucket if args.scst_xe_weight > 0 else 0
+            T = min(args.max_length, 129)                   # the metric kernels score sentences of at most 128 tokens
+            scst = ScstConfig(samples=args.scst_samples, reward=args.scst_reward, baseline=args.scst_baseline, temperature=args.scst_temperature,
+                              top_k=args.scst_top_k, top_p=args.scst_top_p, xe_weight=args.scst_xe_weight, max_length=T, sos=2, eos=3,
+                              seed=args.rand_seed, refs=corpus_reference(corpus, min_len=max(T, longest)))
+            if longest > 129:
+                raise SystemExit("mtn_amd.train: --scst-xe-weight needs answers of at most 128 tokens (the metric kernels' longest sentence)")
+            logging.info("self-critical training: %d samples per dialogue, reward %s, baseline %s, %d reference answers on the device",
+                         scst.samples, scst.reward, scst.baseline, corpus.n_dialogs)
+        if args.eager and scst is None:
             opt = NoamOpt(args.d_model, 1, args.warmup_steps, FusedAdam(model))
             if args.ema_decay:
                 opt.optimizer.enable_ema(args.ema_decay)
@@ -422,7 +489,8 @@ def main(argv=None):
         else:
             from .train_step import BucketedTrainer
             trainer = BucketedTrainer(model, corpus, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l,
-                                      bucket=args.bucket, grad_sync=sync, ema_decay=args.ema_decay, **distill)
+                                      bucket=args.bucket, grad_sync=sync, ema_decay=args.ema_decay, scst=scst,
+                                      use_graph=not (args.eager and scst is not None), **distill)
         valid = None
         if args.valid_videos > 0 or valid_data is not None:
             vdata = valid_data if valid_data is not None else synthetic_corpus(args.valid_videos, args.vocab_size, args.ft_sizes, args.rand_seed + 1000)
@@ -430,15 +498,18 @@ def main(argv=None):
             valid = (DeviceCorpus(vdata, dev), vidx)
             logging.info("#validation sample = %d  #validation batch = %d", vn, len(vidx))
         min_valid = min_valid_ema = 1.0e10
-        the_opt = opt if args.eager else trainer.opt
+        graphed = not args.eager or scst is not None           # (self-critical --eager: the trainer's steps, run eagerly)
+        the_opt = trainer.opt if graphed else opt
         if args.resume:
             model.load_state_dict(torch.load(args.resume + ".pth.tar", map_location=dev), strict=False)
             model.prepare()
             the_opt.load_state_dict(torch.load(args.resume + "_opt.pth.tar"))
             logging.info("resumed from %s at optimiser step %d", args.resume, the_opt.step_count())
+            if scst is not None:
+                trainer.rl_steps = the_opt.step_count()        # the draws go on where the resumed run's would
         for epoch in range(args.num_epochs):
             stats = {}
-            if args.eager:
+            if not graphed:
                 mean, ntok = run_epoch(corpus, indices, model, lc, args.auto_encoder_ft, epoch, args.report_interval, rank, rng, cut,
                                        distill=(teacher, args.distill_alpha, args.distill_temperature) if teacher is not None else None, stats=stats)
             else:
@@ -450,6 +521,8 @@ def main(argv=None):
                 print("epoch %d mean train loss per token: %f" % (epoch + 1, mean))
                 if "kd" in stats:
                     print("epoch %d mean distillation KL per token: %f" % (epoch + 1, stats["kd"]))
+                if "reward" in stats:
+                    print("epoch %d mean reward: %f mean baseline: %f" % (epoch + 1, stats["reward"], stats["baseline"]))
             if args.model:
                 # EVERY rank builds the optimiser state: with the sharded optimiser (dp.ShardedOptimizerSync) a rank holds the
                 # Adam moments of its shards only (and, with the compute-dtype gather, the current fp32 masters of its shards

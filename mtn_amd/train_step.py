@@ -54,11 +54,41 @@ def teacher_rows(teacher, batch, out=None):
         return ops.ensemble_rows(rows, weights, mode, out=out)
 
 
+class ScstConfig:
+    """Self-critical sequence training (Rennie et al. 2017) for TrainStep(scst=...): ``samples`` S responses per dialogue are drawn from
+    the current weights (temperature / top_k / top_p as decode.sample_decode_many takes them), scored against the reference corpus
+    ``refs`` = (ref (Qc, R, L) int32, ref_len (Qc, R) int32, n_ref (Qc,) int32) on the device by ``reward`` ("cider" | "rouge"), and
+    trained on with the row weight -(reward - baseline): ``baseline`` "mean" = the leave-one-out mean of the dialogue's other samples
+    (Luo 2020), "greedy" = the reward of the greedy response.  ``xe_weight`` > 0 adds the gold answer as one more row per dialogue with
+    that constant weight.  Every target row has ``max_length`` positions; sampled and gold rows are -log p(target) (smoothing 0).
+    ``sos`` / ``eos``: the start and end symbols; ``seed``: of the first step's draws, advanced by one per step."""
+
+    def __init__(self, samples: int = 2, reward: str = "cider", baseline: str = "mean", temperature: float = 1.0, top_k: int = 0,
+                 top_p: float = 1.0, xe_weight: float = 0.0, max_length: int = 20, sos: int = 2, eos: int = 3, seed: int = 0, refs=None):
+        if not 2 <= int(samples) <= 16:
+            raise ValueError("scst: 2 to 16 samples per dialogue")
+        if reward not in ("cider", "rouge") or baseline not in ("mean", "greedy"):
+            raise ValueError("scst: reward is cider or rouge, baseline is mean or greedy")
+        if not (float(temperature) >= 0.0 and 0.0 < float(top_p) <= 1.0 and int(top_k) >= 0 and float(xe_weight) >= 0.0 and int(max_length) >= 2):
+            raise ValueError("scst: temperature >= 0, top_k >= 0, 0 < top_p <= 1, xe_weight >= 0, max_length >= 2")
+        self.samples, self.reward, self.baseline = int(samples), reward, baseline
+        self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
+        self.xe_weight, self.max_length, self.sos, self.eos, self.seed, self.refs = float(xe_weight), int(max_length), int(sos), int(eos), int(seed), refs
+        self._table = None               # the corpus' document-frequency table, built once and shared by every step over this config
+
+    def with_max_length(self, max_length: int):
+        """A copy for another number of target positions; the reference corpus and its table are shared."""
+        import copy
+        c = copy.copy(self)
+        c.max_length = int(max_length)
+        return c
+
+
 class TrainStep:
     def __init__(self, model, batch, vocab: int, pad: int = 1, warmup: int = 4000, factor: float = 1.0, lam: float = 1.0,
                  smoothing: float = 0.1, grad_sync=None, use_graph: bool = True, overlap: Optional[bool] = None, opt=None,
                  dynamic_norms: bool = False, fuse_optimizer: Optional[bool] = None, teacher=None, distill_alpha: float = 0.5,
-                 distill_temperature: float = 1.0, ema_decay: float = 0.0):
+                 distill_temperature: float = 1.0, ema_decay: float = 0.0, scst: Optional[ScstConfig] = None):
         """``opt``: share an existing NoamOpt (several TrainSteps over one model, e.g. one per batch shape).
         ``dynamic_norms``: the batch tensors are refilled in place between steps, so the loss normalisers (token counts,
         train.py:35-39) are recomputed from them inside the step instead of once at construction.
@@ -73,9 +103,30 @@ class TrainStep:
         to completion before the student's forward starts and leaves nothing behind, so with distill_alpha == 0 the step is the
         undistilled step bit for bit.  ``last_kd``: device scalar, the step's summed row KL over its target-token normaliser.
         ``ema_decay``: > 0 = the optimiser built here keeps an exponential moving average of the weights (FusedAdam.enable_ema); a
-        shared ``opt`` keeps whatever its owner enabled."""
+        shared ``opt`` keeps whatever its owner enabled.
+        ``scst``: self-critical sequence training (ScstConfig) on ONE rank, without a teacher.  ``batch`` is then the SOURCE of B
+        dialogues (its answers are the gold rows); the step trains on a static batch of its own (``self.batch``: B * S sampled rows
+        d * S + s, then B gold rows when xe_weight > 0, max_length target positions each).  ``rl_step(items)`` is one step: the
+        sampling search under eval() / no_grad on the current weights, the assemble, reward and advantage launches (csrc/scst.hip),
+        the source's encoder-side tensors replicated into the static batch, then the (captured) forward, weighted loss head
+        (mtn_wlosshead_fwd / _bwd), backward and optimiser.  The search reads the drawn tokens once per position, as
+        decode.sample_decode_many does on the launch-per-sublayer pass; from its last token to the optimiser nothing is read on the
+        host.  The sampling pass reads the COMPUTE-DTYPE copies of the weights (the matrices' bf16 images and the generator's): the
+        optimiser of the previous step rewrites them with the masters (FusedAdam writes p_lp next to p), and rl_step calls
+        model.prepare() before the search, which casts whatever a load_state_dict / EMA swap changed behind the optimiser's back.
+        The main stream's normaliser is the count of non-<pad> SAMPLED targets, recomputed inside the step (``dynamic_norms``), so the
+        learning-rate scale is cross-entropy's; the auto-encoder streams keep the plain loss, at ``smoothing``, which the main stream
+        does not use under scst (its rows are -log p(target): smoothing 0).  ``last_reward`` / ``last_baseline``:
+        device scalars (float64), the step's mean reward and mean baseline.  ``load_rows(trg, trg_y, weights)``: the test entry that
+        puts fixed rows in the place of the samples."""
         self.model, self.batch = model, batch
         self._init_teacher(teacher, distill_alpha, distill_temperature, vocab)
+        self.scst = scst
+        if scst is not None:
+            if teacher is not None or grad_sync is not None:
+                raise ValueError("TrainStep: scst does not combine with a teacher (distillation) or with data parallelism")
+            self._init_scst(batch, pad)
+            batch, dynamic_norms = self.batch, True
         if opt is None:
             opt = NoamOpt(model.decoder.layers[0].size, factor, warmup, FusedAdam(model))
             if ema_decay:
@@ -126,6 +177,8 @@ class TrainStep:
     # ---- pieces
     def local_norms(self):
         b = self.batch
+        if self.scst is not None:            # the sampled rows alone: gold rows ride on the same normaliser
+            return torch.stack([(b.trg_y[:self._n_sampled] != self.pad).sum(), (self._ae_y != self.pad).sum()]).float()
         return torch.stack([(b.trg_y != self.pad).sum(), (self._ae_y != self.pad).sum()]).float()
 
     def _refresh_norms(self):
@@ -172,8 +225,172 @@ class TrainStep:
             return None
         return teacher_rows(self.teacher, self.batch, out=self._teacher_rows)
 
+    # ---- self-critical sequence training
+    def _init_scst(self, src, pad):
+        from .data_utils import Batch
+        cfg = self.scst
+        B, S, T = src.query.size(0), cfg.samples, cfg.max_length
+        gold = cfg.xe_weight > 0
+        if gold and (getattr(src, "trg", None) is None or src.trg.size(1) > T):
+            raise ValueError("TrainStep: scst with xe_weight needs the source batch's answers, of at most max_length positions")
+        dev = src.query.device
+        self.src, self._n_sampled = src, B * S
+        idx = torch.arange(B, device=dev).repeat_interleave(S)
+        if gold:
+            idx = torch.cat([idx, torch.arange(B, device=dev)])
+        self._rep_idx = idx
+        rows = idx.numel()
+        trg = torch.full((rows, T), pad, dtype=torch.long, device=dev)
+        trg_y = torch.full((rows, T), pad, dtype=torch.long, device=dev)
+        trg[:, 0], trg_y[:, 0] = cfg.sos, cfg.eos                      # empty responses until rows are loaded or drawn
+        b = Batch(src.query[idx], src.his[idx], None, None, None if src.cap is None else src.cap[idx], trg, trg_y, pad=pad, device=dev)
+        if src.fts is not None:
+            b.fts, b.fts_mask = [f[idx].contiguous() for f in src.fts], [m[idx].contiguous() for m in src.fts_mask]
+        self.batch = b
+        self._roww = torch.zeros(rows, T, dtype=torch.float32, device=dev)
+        self._means = torch.zeros(2, dtype=torch.float64, device=dev)
+        self.last_reward, self.last_baseline = self._means[0], self._means[1]
+        self._hyp_len = torch.zeros(B * S, dtype=torch.int32, device=dev)
+        self._item = torch.zeros(B * S, dtype=torch.int32, device=dev)
+        self._rl_steps = 0
+        self._pad_scst = pad
+        self._replicate()
+
+    def _replicate(self):
+        """The source batch's encoder-side tensors (and, with xe_weight, its answers as the gold rows) into the static batch, in place:
+        the masks' kernel images (ops.prepare_masks) follow."""
+        src, b, idx, n, pad = self.src, self.batch, self._rep_idx, self._n_sampled, self._pad_scst
+
+        def put(dst, rows):
+            dst.copy_(rows)
+            u8 = getattr(dst, "_mtn_u8", None)
+            if u8 is not None:
+                u8.copy_(rows)
+
+        for name in ("query", "his") + (("cap",) if src.cap is not None else ()):
+            getattr(b, name).copy_(getattr(src, name)[idx])
+            put(getattr(b, name + "_mask"), getattr(src, name + "_mask")[idx])
+        if src.fts is not None:
+            for f, m, sf, sm in zip(b.fts, b.fts_mask, src.fts, src.fts_mask):
+                f.copy_(sf[idx])
+                put(m, sm[idx])
+        if idx.numel() > n:
+            Tg = src.trg.size(1)
+            b.trg[n:].fill_(pad)
+            b.trg_y[n:].fill_(pad)
+            b.trg[n:, :Tg].copy_(src.trg)
+            b.trg_y[n:, :Tg].copy_(src.trg_y)
+            self._roww[n:].fill_(self.scst.xe_weight)
+        self._refresh_target_mask()
+
+    def _refresh_target_mask(self):
+        from .data_utils import Batch
+        b = self.batch
+        m = Batch.make_std_mask(b.trg, self._pad_scst)
+        b.trg_mask.copy_(m)
+        u8 = getattr(b.trg_mask, "_mtn_u8", None)
+        if u8 is not None:
+            u8.copy_(m)
+
+    def load_rows(self, trg, trg_y, weights):
+        """Test entry: fixed rows in the place of the samples.  ``trg`` / ``trg_y`` (n, max_length) int64 for the first n rows of the
+        static batch (n = B * S, or every row), ``weights`` (n,) or (n, max_length) float: one weight per row or per target position."""
+        b, n = self.batch, trg.size(0)
+        if n not in (self._n_sampled, b.trg.size(0)) or tuple(trg.shape) != tuple(b.trg[:n].shape) or tuple(trg_y.shape) != tuple(trg.shape):
+            raise ValueError("load_rows: (B * S, max_length) or (every row, max_length) int64 targets")
+        b.trg[:n].copy_(trg)
+        b.trg_y[:n].copy_(trg_y)
+        w = torch.as_tensor(weights, dtype=torch.float32).to(self._roww.device)
+        self._roww[:n].copy_(w.reshape(n, -1).expand(n, self._roww.size(1)))
+        self._refresh_target_mask()
+
+    def _sample_log(self, items, seed):
+        """The token log (max_length, B * S) int32 of one sampling search over the source batch, left on the device."""
+        from . import decode as dec
+        cfg, S = self.scst, self.scst.samples
+        T = cfg.max_length
+        temperature, top_k = (1.0, 1) if cfg.temperature == 0.0 else (cfg.temperature, cfg.top_k)
+        banned = (self._pad_scst, cfg.sos)                             # neither can stand inside a target row
+        params = dict(temperature=temperature, top_k=top_k, top_p=cfg.top_p, banned=banned, eos=cfg.eos, min_len=0)
+        row_keys = [int(k) * S + s for k in items for s in range(S)]
+        log = dec._sample_search(self.model, self.src, T, cfg.sos, self._pad_scst, S, seed, row_keys, params, True,
+                                 T > dec.KV_CACHE_FROM, False, on_device=True)
+        return log[0]
+
+    def _rewards(self, log_tok, item, trg=None, trg_y=None):
+        """Assemble + reward launches for a (max_length, n) token log: the chosen reward, (n,) float64 on the device."""
+        from . import ops
+        cfg, T = self.scst, self.scst.max_length
+        ref, ref_len, n_ref = cfg.refs
+        n, dev = log_tok.size(1), log_tok.device
+        if ref.stride(1) < T or ref.size(2) < T - 1:
+            raise ValueError("TrainStep: scst needs reference rows of at least max_length - 1 tokens with a row stride >= max_length")
+        if cfg._table is None:
+            cfg._table = ops.eval_table_build(ref, ref_len, n_ref)
+        hyp = torch.empty(n, ref.stride(1), dtype=torch.int32, device=dev)
+        hyp_len = torch.empty(n, dtype=torch.int32, device=dev)
+        if trg is None:
+            trg, trg_y = torch.empty(n, T, dtype=torch.long, device=dev), torch.empty(n, T, dtype=torch.long, device=dev)
+        ops.scst_assemble(log_tok, cfg.sos, cfg.eos, self._pad_scst, T=T, out=(trg, trg_y, hyp[:, :T], hyp_len), hyp_stride=ref.stride(1))
+        _, rouge, cider = ops.eval_score_rows(hyp[:, :ref.size(2)], hyp_len, item, ref, ref_len, n_ref, cfg._table)
+        return cider if cfg.reward == "cider" else rouge
+
+    def rl_step(self, items, seed=None, timings=None):
+        """One self-critical step on the source batch; ``items``: per dialogue its index in the reference corpus (also the sampling keys).
+        ``seed``: of this step's draws (None: the config's seed + the steps this TrainStep has run).  With the greedy baseline the greedy
+        search runs FIRST (it hands its tokens over the host), then the sampling search.  Returns the device tensor of the step's loss;
+        ``last_reward`` / ``last_baseline`` hold the means.  ``timings``: a dict that accumulates the wall-clock ms of the step's three
+        parts under "search", "reward" and "step" — a measuring aid (tools/scst_bench.py): the device is synchronised between them."""
+        import time
+        from . import decode as dec
+
+        def lap(name, t0):
+            if timings is None:
+                return t0
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + (t1 - t0) * 1e3
+            return t1
+        from . import ops
+        cfg, m, b = self.scst, self.model, self.batch
+        if cfg.refs is None:
+            raise ValueError("TrainStep: rl_step needs ScstConfig.refs, the reference corpus on the device")
+        B, S, T, n = self.src.query.size(0), cfg.samples, cfg.max_length, self._n_sampled
+        if len(items) != B:
+            raise ValueError("rl_step: one corpus item per dialogue of the source batch")
+        dev = self._roww.device
+        dlg_item = torch.tensor([int(i) for i in items], dtype=torch.int32).to(dev)
+        self._item.copy_(dlg_item.repeat_interleave(S))
+        t0 = lap("reward", time.perf_counter()) if timings is not None else 0.0
+        training = m.training
+        m.eval()
+        m.prepare()                       # the compute-dtype copies the search reads are current (see __init__)
+        try:
+            with torch.no_grad():
+                base = None
+                if cfg.baseline == "greedy":
+                    ys = dec.greedy_decode_many(m, self.src, T, cfg.sos, self._pad_scst)
+                    glog = torch.cat([ys[:, 1:].to(torch.int32), torch.full((B, 1), cfg.eos, dtype=torch.int32, device=dev)], 1).t().contiguous()
+                    base = self._rewards(glog, dlg_item)
+                log_tok = self._sample_log(items, cfg.seed + self._rl_steps if seed is None else int(seed))
+        finally:
+            if training:
+                m.train()
+        t0 = lap("search", t0)
+        reward = self._rewards(log_tok, self._item, b.trg[:n], b.trg_y[:n])
+        ops.scst_advantage(reward.view(B, S), T, baseline=base, roww=self._roww, means=self._means)
+        self._replicate()
+        self._rl_steps += 1
+        t0 = lap("reward", t0)
+        loss = self()
+        lap("step", t0)
+        return loss
+
     def _loss_of(self, out, ae_out, teacher_rows):
         """The step's loss, for both schedules (monolithic _fwd_bwd, the segmented top())."""
+        if self.scst is not None:
+            return self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], row_weights=self._roww,
+                                smoothing=0.0)
         if teacher_rows is None:
             return self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1])
         loss = self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], teacher_logp=teacher_rows,
@@ -459,7 +676,16 @@ class BucketedTrainer:
 
     def __init__(self, model, corpus, vocab_size: int, pad: int = 1, warmup: int = 4000, lam: float = 1.0, bucket: int = 8,
                  grad_sync=None, max_shapes: int = 64, teacher=None, distill_alpha: float = 0.5, distill_temperature: float = 1.0,
-                 ema_decay: float = 0.0):
+                 ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, use_graph: bool = True):
+        """``scst``: self-critical sequence training — every padded shape keeps, next to its static source Batch, a TrainStep(scst=...)
+        whose own static batch holds the drawn rows; a step refills the source in place and calls rl_step with the batch's QA ids as
+        corpus items and sampling keys and the seed ``scst.seed + rl_steps`` (``rl_steps``: steps taken; set it after a resume).  With
+        xe_weight the rows have max(scst.max_length, the shape's padded answer length) positions.  ``last_reward`` / ``last_baseline``:
+        the last step's device scalars.  ``use_graph`` = False: the same steps run eagerly."""
+        if scst is not None and (teacher is not None or grad_sync is not None):
+            raise ValueError("BucketedTrainer: scst does not combine with a teacher (distillation) or with data parallelism")
+        self.scst, self.use_graph, self.rl_steps = scst, use_graph, 0
+        self.last_reward = self.last_baseline = None
         self.model, self.corpus, self.vocab, self.pad, self.lam = model, corpus, vocab_size, pad, lam
         self.teacher, self.distill_alpha, self.distill_temperature = teacher, distill_alpha, distill_temperature
         self.bucket, self.grad_sync, self.max_shapes = bucket, grad_sync, max_shapes
@@ -474,26 +700,61 @@ class BucketedTrainer:
         x_len, h_len, q_len, a_len, c_len, n = index[2:]
         return (index[0], index[1], [up(v) for v in x_len], up(h_len), up(q_len), up(a_len), up(c_len), n)
 
+    def _key(self, index):
+        """The padded shape an index entry falls into: the key of ``steps``."""
+        pidx = self._padded(index)
+        return (tuple(pidx[2]),) + tuple(pidx[3:])
+
     def step(self, index, cut_a: bool = False, rng=None):
         """One optimiser step on the batch described by ``index`` (an entry of data_handler.make_batch_indices with
         separate_caption=True).  Returns (device loss tensor, the static Batch that now holds this batch).  ``cut_a``: the
         reference's random answer truncation, drawn once per step from ``rng`` (data_handler.draw_cuts; None = np.random)."""
         from .data_handler import make_batch
         pidx = self._padded(index)
-        key = (tuple(pidx[2]),) + tuple(pidx[3:])
+        key = (tuple(pidx[2]),) + tuple(pidx[3:])                    # (== self._key(index))
         hit = self.steps.get(key)
         if hit is None:
             if len(self.steps) >= self.max_shapes:
                 self.steps.pop(next(iter(self.steps)))
             batch = make_batch(self.corpus, pidx, self.pad, separate_caption=True, cut_a=cut_a, rng=rng)
+            cfg = self.scst
+            if cfg is not None and cfg._table is None:           # once, before any per-shape copy of the config is made
+                from . import ops
+                cfg._table = ops.eval_table_build(*cfg.refs)
+            if cfg is not None and cfg.xe_weight > 0 and batch.trg.size(1) > cfg.max_length:
+                cfg = cfg.with_max_length(batch.trg.size(1))
             ts = TrainStep(self.model, batch, self.vocab, pad=self.pad, lam=self.lam, grad_sync=self.grad_sync, opt=self.opt,
                            dynamic_norms=True, teacher=self.teacher, distill_alpha=self.distill_alpha,
-                           distill_temperature=self.distill_temperature)
+                           distill_temperature=self.distill_temperature, scst=cfg, use_graph=self.use_graph)
             self.steps[key] = hit = (batch, ts)
         else:
             make_batch(self.corpus, pidx, self.pad, separate_caption=True, out=hit[0], cut_a=cut_a, rng=rng)
         hit[1].refresh_norms_eager()
+        if self.scst is not None:
+            loss = hit[1].rl_step(list(index[1]), seed=self.scst.seed + self.rl_steps)
+            self.rl_steps += 1
+            self.last_reward, self.last_baseline = hit[1].last_reward, hit[1].last_baseline
+            hit[1].batch._norms_global = hit[1]._norms
+            return loss, hit[1].batch
         loss = hit[1]()
         self.last_kd = hit[1].last_kd               # (device scalar; None without a teacher)
         hit[0]._norms_global = hit[1]._norms        # [target tokens, auto-encoder tokens] the step's loss is divided by (all ranks)
         return loss, hit[0]
+
+
+def corpus_reference(corpus, min_len: int = 0, max_len: int = 128):
+    """The corpus' tokenised answers as the reference corpus of ScstConfig.refs, uploaded once: item q = QA id q, one reference each, the
+    answer's model token ids without <sos> / <eos> (cut at ``max_len`` = 128 tokens, the metric kernels' longest sentence).  Rows hold
+    max(longest answer, ``min_len`` - 1) tokens with a row stride >= ``min_len``, what a step of ``min_len`` target positions needs.
+    Returns (ref (Qc, 1, L) int32, ref_len (Qc, 1) int32, n_ref (Qc,) int32) on the corpus' device."""
+    import numpy as np
+    flat, start, lens = corpus.host_tok["trg_y"]                      # y.., <eos>
+    n = np.minimum(np.maximum(lens.astype(np.int64) - 1, 0), max_len)
+    Lr = int(min(max_len, max(int(n.max()) if len(n) else 1, min_len - 1, 1)))
+    ld = -(-max(Lr, min_len) // 8) * 8
+    ref = np.full((len(n), 1, ld), 1, dtype=np.int32)
+    for q in range(len(n)):
+        ref[q, 0, :n[q]] = flat[start[q]:start[q] + n[q]]
+    dev = corpus.device
+    return (torch.from_numpy(ref).to(dev)[:, :, :Lr], torch.from_numpy(n.astype(np.int32).reshape(-1, 1)).to(dev),
+            torch.ones(len(n), dtype=torch.int32, device=dev))
