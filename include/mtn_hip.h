@@ -512,7 +512,7 @@ typedef struct {
 int mtn_losshead_fwd(const mtn_losshead_args* args, void* stream);
 int mtn_losshead_bwd(int dtype, const mtn_losshead_args* args, void* stream);
 
-/* Loss head with teacher soft targets (version 123; csrc/distill.hip): word-level knowledge distillation.  Every field of
+/* Loss head with teacher soft targets (version 123; csrc/losshead.hip): word-level knowledge distillation.  Every field of
  * mtn_losshead_args keeps its meaning.  teacher[s] is a device matrix [rows[s]][ldq[s]] of float, 16-byte aligned, ldq >= V and
  * ldq % 4 == 0 (columns V..ldq-1 are never read), NULL = segment s has no teacher.  A teacher row holds log-probabilities or logits:
  * it is normalised here, as mtn_ensemble_rows normalises its members.  With z the student row, q the teacher row, t the target,
@@ -555,7 +555,7 @@ typedef struct {
 int mtn_distill_fwd(const mtn_distill_args* args, void* stream);
 int mtn_distill_bwd(int dtype, const mtn_distill_args* args, void* stream);
 
-/* Loss head with signed row weights (version 125; csrc/scst.hip): the policy-gradient loss of self-critical sequence training
+/* Loss head with signed row weights (version 125; csrc/losshead.hip): the policy-gradient loss of self-critical sequence training
  * (Rennie et al. 2017), where a sampled row's weight is -(reward - baseline).  Every field of mtn_losshead_args keeps its meaning.
  * roww[s] is a device array of rows[s] floats, 4-byte aligned, NULL = every weight of segment s is 1.  smoothing_seg[s] >= 0 is the label
  * smoothing of segment s (0: KL_ls = -log p(target) on a live row); smoothing_seg[s] < 0 = the segment takes `smoothing`.  With KL_ls, td
@@ -564,7 +564,7 @@ int mtn_distill_bwd(int dtype, const mtn_distill_args* args, void* stream);
  *   bwd:      dlogits_j = *gloss scale w (softmax_j(z) sum(td) - td_j); columns V..ldd-1 are +0.0
  * w may be negative or zero; a row with w == 0 writes rowloss = +0.0 and a dlogits row of +0.0, as a zeroed <pad> row does.  A non-finite
  * weight is device data and is NOT checked: its rowloss and dlogits row are not finite.
- * A segment with roww == NULL and the loss head's smoothing runs losshead.hip's arithmetic, statement for statement: lse, rowloss and dlogits
+ * A segment with roww == NULL and the loss head's smoothing runs the same code as the plain loss head: lse, rowloss and dlogits
  * are those of mtn_losshead_fwd / _bwd on the same inputs bit for bit.
  * MTN_ERR_ARG, nothing launched: whatever mtn_losshead_fwd / _bwd refuse; a roww pointer that is not 4-byte aligned; a smoothing_seg that is
  * NaN. */

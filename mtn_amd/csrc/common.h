@@ -216,3 +216,25 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+
+// running (max, sum of exp(x - max)) of a lane after one / four more columns; -inf entries contribute nothing
+__device__ __forceinline__ void online1(float& m, float& s, float a) {
+    const float mn = fmaxf(m, a);
+    if (mn > -INFINITY) {
+        s = s * __expf(m - mn) + __expf(a - mn);
+        m = mn;
+    }
+}
+__device__ __forceinline__ void online4(float& m, float& s, const float4& v) {
+    const float mn = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+    if (mn > -INFINITY) {
+        s = s * __expf(m - mn) + ((__expf(v.x - mn) + __expf(v.y - mn)) + (__expf(v.z - mn) + __expf(v.w - mn)));
+        m = mn;
+    }
+}
+// a lane's pair -> its wave's: the row's log-sum-exp is m + log s
+__device__ __forceinline__ void online_wave(float& m, float& s) {
+    const float M = wave_max(m);
+    s = wave_sum(m > -INFINITY ? s * __expf(m - M) : 0.f);
+    m = M;
+}

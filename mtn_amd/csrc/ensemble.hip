@@ -30,25 +30,10 @@ struct EnsArgs {                                              // the weighted me
     float* out; long ldo;
 };
 
-__device__ __forceinline__ void ens_online1(float& m, float& s, float a) {
-    const float mn = fmaxf(m, a);
-    if (mn > -INFINITY) {
-        s = s * __expf(m - mn) + __expf(a - mn);
-        m = mn;
-    }
-}
-__device__ __forceinline__ void ens_online4(float& m, float& s, const float4& v) {
-    const float mn = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
-    if (mn > -INFINITY) {
-        s = s * __expf(m - mn) + ((__expf(v.x - mn) + __expf(v.y - mn)) + (__expf(v.z - mn) + __expf(v.w - mn)));
-        m = mn;
-    }
-}
 // a thread's (max, sum-exp) -> its wave's, left in LDS by lane 0
 __device__ __forceinline__ void ens_wave_put(float m, float s, float (*red)[ENS_WAVES], int lane, int wave) {
-    const float Mw = wave_max(m);
-    const float Sw = wave_sum(m > -INFINITY ? s * __expf(m - Mw) : 0.f);
-    if (lane == 0) { red[0][wave] = Mw; red[1][wave] = Sw; }
+    online_wave(m, s);
+    if (lane == 0) { red[0][wave] = m; red[1][wave] = s; }
 }
 // ... and, after a barrier, the row's logsumexp from the waves' pairs in wave order (every thread computes the same bits)
 __device__ __forceinline__ float ens_row_lse(const float (*red)[ENS_WAVES]) {
@@ -98,8 +83,8 @@ __global__ __launch_bounds__(ENS_THREADS) void ensemble_rows_kernel(const EnsArg
         if (m < M) {
             const float* x = A.x[m] + (size_t)row * A.ld[m];
             float mx = -INFINITY, s = 0.f;
-            for (int i = tid; i < V4; i += ENS_THREADS) ens_online4(mx, s, ((const float4*)x)[i]);
-            for (int c = V4 * 4 + tid; c < V; c += ENS_THREADS) ens_online1(mx, s, x[c]);
+            for (int i = tid; i < V4; i += ENS_THREADS) online4(mx, s, ((const float4*)x)[i]);
+            for (int c = V4 * 4 + tid; c < V; c += ENS_THREADS) online1(mx, s, x[c]);
             ens_wave_put(mx, s, s_red[m], lane, wave);
         }
     }
@@ -130,7 +115,7 @@ __global__ __launch_bounds__(ENS_THREADS) void ensemble_rows_kernel(const EnsArg
         for (int m = 0; m < ENS_MAX_M; ++m) v[m] = m < M ? xv[m].w : 0.f;
         o.w = ens_combine(A, v, lse);
         ((float4*)orow)[i] = o;
-        if (A.mode == 1) ens_online4(smx, ssum, o);
+        if (A.mode == 1) online4(smx, ssum, o);
     }
     for (int c = V4 * 4 + tid; c < V; c += ENS_THREADS) {
         float v[ENS_MAX_M];
@@ -138,7 +123,7 @@ __global__ __launch_bounds__(ENS_THREADS) void ensemble_rows_kernel(const EnsArg
         for (int m = 0; m < ENS_MAX_M; ++m) v[m] = m < M ? A.x[m][(size_t)row * A.ld[m] + c] : 0.f;
         const float o = ens_combine(A, v, lse);
         orow[c] = o;
-        if (A.mode == 1) ens_online1(smx, ssum, o);
+        if (A.mode == 1) online1(smx, ssum, o);
     }
     if (A.mode == 0) return;                                  // (uniform: a kernel argument)
 

@@ -14,21 +14,6 @@
 
 static constexpr int SCORE_WAVES = 8;
 
-// running (max, sum of exp(x - max)) of a lane after four more columns
-__device__ __forceinline__ void score_online4(float& m, float& s, float a, float b, float c, float d) {
-    const float mn = fmaxf(fmaxf(m, fmaxf(a, b)), fmaxf(c, d));
-    if (mn > -INFINITY) {
-        s = s * __expf(m - mn) + ((__expf(a - mn) + __expf(b - mn)) + (__expf(c - mn) + __expf(d - mn)));
-        m = mn;
-    }
-}
-__device__ __forceinline__ void score_online1(float& m, float& s, float a) {
-    const float mn = fmaxf(m, a);
-    if (mn > -INFINITY) {
-        s = s * __expf(m - mn) + __expf(a - mn);
-        m = mn;
-    }
-}
 __device__ __forceinline__ int score_wave_isum(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -60,17 +45,16 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void score_rows_kernel(const mtn_
                 // columns [0, head) bring the row to a 16-byte boundary, [head, body_end) go four at a time, the rest one by one
                 const int head = min(V, (int)((4 - (((uintptr_t)z >> 2) & 3)) & 3));
                 const int body_end = head + ((V - head) & ~3);
-                if (lane < head) { const float x = z[lane]; score_online1(m, s, x); count(x, lane); }
+                if (lane < head) { const float x = z[lane]; online1(m, s, x); count(x, lane); }
                 for (int c = head + lane * 4; c < body_end; c += 256) {
                     const float4 v = *(const float4*)(z + c);
-                    score_online4(m, s, v.x, v.y, v.z, v.w);
+                    online4(m, s, v);
                     count(v.x, c); count(v.y, c + 1); count(v.z, c + 2); count(v.w, c + 3);
                 }
-                if (body_end + lane < V) { const float x = z[body_end + lane]; score_online1(m, s, x); count(x, body_end + lane); }
-                const float M = wave_max(m);
-                const float S = wave_sum(m > -INFINITY ? s * __expf(m - M) : 0.f);
+                if (body_end + lane < V) { const float x = z[body_end + lane]; online1(m, s, x); count(x, body_end + lane); }
+                online_wave(m, s);
                 rank = score_wave_isum(above);
-                lp = (zt - M) - logf(S);
+                lp = (zt - m) - logf(s);
                 counted = 1;
             }
             if (lane == 0) { A.tok_logp[at] = lp; A.tok_rank[at] = rank; }

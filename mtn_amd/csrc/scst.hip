@@ -5,173 +5,10 @@
 //   mtn_eval_score_rows       N hypotheses, each against the references of the corpus item it names (eval_common.h's item body: the
 //                             launch reads the table and never writes it, no atomics, double with fixed-order sums)
 //   mtn_scst_advantage        rewards -> signed row weights -(r - b), b a given baseline or the leave-one-out mean
-//   mtn_wlosshead_fwd / _bwd  the loss head with a signed weight per row and a smoothing per segment.  A segment without weights at the
-//                             loss head's smoothing runs losshead.hip's arithmetic, statement for statement (the weight is applied by
-//                             a multiplication of its own, which cannot be contracted into anything), so its bits are the loss head's.
-// One 64-lane wave per loss-head row, float4 loads, wave-shuffle reductions in a fixed order, no atomics; HBM/L2-bound as losshead.hip.
+// The loss head that reads those weights (mtn_wlosshead_fwd / _bwd) is an instantiation of losshead.hip.
 #include "eval_common.h"
 
 #include <math.h>
-
-// ------------------------------------------------------------------------------------------ weighted loss head
-struct WRow {
-    int seg, local;      // segment (stream) and row inside it
-    long t;
-    float scale;         // coef / norm
-    float eps, conf;     // the segment's smoothing
-    bool zero_row, t_is_pad;
-    bool weighted;       // the segment has weights
-    float w;
-};
-
-__device__ __forceinline__ WRow wrow_info(const mtn_wlosshead_args& A, int row, int lane) {
-    WRow r;
-    int base = 0;
-    r.seg = 0;
-    for (int s = 0; s < A.n_seg; ++s) {
-        if (row >= base && row < base + A.rows[s]) { r.seg = s; break; }
-        base += A.rows[s];
-    }
-    r.local = row - base;
-    r.t = A.target[r.seg][r.local];
-    r.scale = A.coef[r.seg] / *A.norm[r.seg];
-    r.t_is_pad = (r.t == A.pad);
-    r.zero_row = false;
-    if (r.t_is_pad) {
-        if (r.local > 0) r.zero_row = true;                 // its own index makes the index sum positive
-        else {                                              // flat row 0: zeroed only if another <pad> row exists
-            int any = 0;
-            for (int i = 1 + lane; i < A.rows[r.seg]; i += 64) any |= (A.target[r.seg][i] == A.pad);
-            r.zero_row = __any(any);
-        }
-    }
-    const float sm = A.smoothing_seg[r.seg] >= 0.f ? A.smoothing_seg[r.seg] : A.smoothing;
-    r.eps = sm / (float)(A.V - 2);
-    r.conf = 1.0f - sm;
-    r.weighted = A.roww[r.seg] != nullptr;
-    r.w = r.weighted ? A.roww[r.seg][r.local] : 1.0f;
-    if (r.w == 0.f) r.zero_row = true;                      // +0.0 everywhere, whatever the row holds
-    return r;
-}
-
-__global__ __launch_bounds__(256) void wlosshead_fwd_kernel(const mtn_wlosshead_args A, int total_rows) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= total_rows) return;
-    const WRow r = wrow_info(A, row, lane);
-    const float* z = A.logits + (size_t)row * A.ldz;
-    const int V = A.V;
-    float mx = -INFINITY, S = 0.f;
-    for (int c = lane * 4; c < V; c += 256) {
-        float4 v = *(const float4*)(z + c);                 // V % 4 == 0 (checked on the host)
-        mx = fmaxf(fmaxf(mx, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
-        S += (v.x + v.y) + (v.z + v.w);
-    }
-    mx = wave_max(mx);
-    S = wave_sum(S);
-    float se = 0.f;
-    for (int c = lane * 4; c < V; c += 256) {
-        float4 v = *(const float4*)(z + c);
-        se += (__expf(v.x - mx) + __expf(v.y - mx)) + (__expf(v.z - mx) + __expf(v.w - mx));
-    }
-    const float lse = mx + __logf(wave_sum(se));
-    if (lane == 0) {
-        A.lse[row] = lse;
-        float loss = 0.f;
-        if (!r.zero_row) {
-            const float eps = r.eps, conf = r.conf;
-            const float zt = z[r.t], zp = z[A.pad];
-            float n_eps, sum_tdz, sum_td, sum_tdlog;
-            if (!r.t_is_pad) {
-                n_eps = (float)(V - 2);
-                sum_tdz = eps * (S - zt - zp) + conf * zt;
-                sum_td = n_eps * eps + conf;
-                sum_tdlog = (eps > 0.f ? n_eps * eps * __logf(eps) : 0.f) + (conf > 0.f ? conf * __logf(conf) : 0.f);
-            } else {
-                n_eps = (float)(V - 1);
-                sum_tdz = eps * (S - zp);
-                sum_td = n_eps * eps;
-                sum_tdlog = eps > 0.f ? n_eps * eps * __logf(eps) : 0.f;
-            }
-            const float sw = r.weighted ? r.scale * r.w : r.scale;
-            loss = (sum_tdlog - sum_tdz + lse * sum_td) * sw;
-        }
-        A.rowloss[row] = loss;
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void wlosshead_bwd_kernel(const mtn_wlosshead_args A, int total_rows) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= total_rows) return;
-    const WRow r = wrow_info(A, row, lane);
-    const float* z = A.logits + (size_t)row * A.ldz;
-    T* dz = (T*)A.dlogits + (size_t)row * A.ldd;
-    const int V = A.V;
-    float g = (*A.gloss) * r.scale;
-    if (r.weighted) g = g * r.w;
-    const float eps = r.eps, conf = r.conf;
-    const float sum_td = r.zero_row ? 0.f : (r.t_is_pad ? (float)(V - 1) * eps : (float)(V - 2) * eps + conf);
-    const float lse = A.lse[row];
-    for (int c = lane * 4; c < A.ldd; c += 256) {
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < V && !r.zero_row) {
-            float4 v = *(const float4*)(z + c);
-            float* ov = &o.x;
-            const float* vv = &v.x;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int j = c + k;
-                float td = eps;
-                if (j == A.pad) td = 0.f;
-                else if (j == r.t) td = conf;
-                ov[k] = g * (__expf(vv[k] - lse) * sum_td - td);
-            }
-        }
-        store_lp4<T>(dz + c, o);
-    }
-}
-
-// everything mtn_losshead_fwd / _bwd refuse, then the weights and the smoothings
-static int wlosshead_check(const char* fn, const mtn_wlosshead_args* A, bool bwd, int dtype, int* total) {
-#define WL_CHECK(cond, msg) do { if (!(cond)) { mtn_set_error("%s: %s", fn, msg); return MTN_ERR_ARG; } } while (0)
-    WL_CHECK(!bwd || dtype == MTN_F32 || dtype == MTN_BF16, "bad dtype");
-    WL_CHECK(A && A->n_seg >= 1 && A->n_seg <= MTN_LOSSHEAD_MAX_SEG, "bad segment count");
-    WL_CHECK(A->V >= 4 && A->V % 4 == 0 && A->ldz % 4 == 0 && A->ldz >= A->V, "V and ldz must be multiples of 4, ldz >= V >= 4");
-    WL_CHECK(!bwd || (A->ldd % 4 == 0 && A->ldd >= A->V), "ldd must be a multiple of 4, ldd >= V");
-    WL_CHECK(A->pad >= 0 && A->pad < A->V, "pad outside [0, V)");
-    WL_CHECK(A->logits && A->lse && (bwd ? (A->gloss && A->dlogits) : A->rowloss != nullptr), "null buffer");
-    *total = 0;
-    for (int s = 0; s < A->n_seg; ++s) {
-        WL_CHECK(A->rows[s] > 0 && A->target[s] && A->norm[s], "bad segment");
-        WL_CHECK(((uintptr_t)A->roww[s] & 3) == 0, "row weights must be 4-byte aligned");
-        WL_CHECK(!isnan(A->smoothing_seg[s]), "smoothing_seg is NaN");
-        *total += A->rows[s];
-    }
-#undef WL_CHECK
-    return MTN_OK;
-}
-
-extern "C" int mtn_wlosshead_fwd(const mtn_wlosshead_args* A, void* stream) {
-    int total = 0;
-    const int rc = wlosshead_check(__func__, A, false, 0, &total);
-    if (rc != MTN_OK) return rc;
-    hipLaunchKernelGGL(wlosshead_fwd_kernel, dim3((total + 3) / 4), dim3(256), 0, (hipStream_t)stream, *A, total);
-    MTN_CHECK_LAUNCH();
-    return MTN_OK;
-}
-
-extern "C" int mtn_wlosshead_bwd(int dtype, const mtn_wlosshead_args* A, void* stream) {
-    int total = 0;
-    const int rc = wlosshead_check(__func__, A, true, dtype, &total);
-    if (rc != MTN_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MTN_BF16) hipLaunchKernelGGL((wlosshead_bwd_kernel<bf16_t>), dim3((total + 3) / 4), dim3(256), 0, st, *A, total);
-    else hipLaunchKernelGGL((wlosshead_bwd_kernel<float>), dim3((total + 3) / 4), dim3(256), 0, st, *A, total);
-    MTN_CHECK_LAUNCH();
-    return MTN_OK;
-}
 
 // ------------------------------------------------------------------------------------------ rewards against a fixed corpus
 struct RowsArgs { EvalArgs e; const int* item; };

@@ -1688,11 +1688,11 @@ class GeneratorLossFn(torch.autograd.Function):
     vocab, pad, smoothing, lp_dtype.  Generator gradients are written to the flat gradient buffer (not returned).
     Knowledge distillation: ``spec["teacher"]`` = per stream a (rows_i, V) fp32 device tensor of teacher logits / log-probabilities or
     None, with ``spec["alpha"]`` and ``spec["temperature"]``.  With any teacher present the row kernels are mtn_distill_fwd / _bwd
-    (csrc/distill.hip; include/mtn_hip.h) in the place of the two loss-head calls, casts and GEMMs unchanged, and ``spec["kd_sum"]`` is
+    (csrc/losshead.hip; include/mtn_hip.h) in the place of the two loss-head calls, casts and GEMMs unchanged, and ``spec["kd_sum"]`` is
     left holding the device scalar sum_rows kd; with none the calls are exactly the loss head's.
     Signed row weights (self-critical sequence training): ``spec["row_weights"]`` = per stream a contiguous fp32 device tensor of one weight
     per row or None (all ones), ``spec["smoothing_seg"]`` = per stream a smoothing or None (the spec's).  With either present the row
-    kernels are mtn_wlosshead_fwd / _bwd (csrc/scst.hip); not together with a teacher."""
+    kernels are mtn_wlosshead_fwd / _bwd (csrc/losshead.hip); not together with a teacher."""
 
     @staticmethod
     def forward(ctx, spec, *xs):
@@ -1746,7 +1746,13 @@ class GeneratorLossFn(torch.autograd.Function):
         weighted = _row_weights(spec, rows, dev)
         if teachers is not None and weighted is not None:
             raise ValueError("GeneratorLossFn: row weights and teacher soft targets do not combine")
-        A = L.WLossHeadArgs() if weighted is not None else (L.LossHeadArgs() if teachers is None else L.DistillHeadArgs())
+        if weighted is not None:
+            args_cls, fwd, bwd = L.WLossHeadArgs, lib.mtn_wlosshead_fwd, lib.mtn_wlosshead_bwd
+        elif teachers is not None:
+            args_cls, fwd, bwd = L.DistillHeadArgs, lib.mtn_distill_fwd, lib.mtn_distill_bwd
+        else:
+            args_cls, fwd, bwd = L.LossHeadArgs, lib.mtn_losshead_fwd, lib.mtn_losshead_bwd
+        A = args_cls()
         A.n_seg = len(xs)
         norms = [n.float().reshape(1) if n.dtype != torch.float32 or n.dim() == 0 else n for n in spec["norms"]]
         targets = [t.contiguous().view(-1) for t in spec["targets"]]
@@ -1759,38 +1765,30 @@ class GeneratorLossFn(torch.autograd.Function):
         if weighted is not None:
             for i, (w, sm) in enumerate(zip(*weighted)):
                 A.roww[i], A.smoothing_seg[i] = L.ptr(w), sm
-            L.check(lib.mtn_wlosshead_fwd(C.byref(A), L.stream_ptr()))
-        elif teachers is None:
-            L.check(lib.mtn_losshead_fwd(C.byref(A), L.stream_ptr()))
-        else:
+        elif teachers is not None:
             rowkd = torch.empty(R, device=dev, dtype=torch.float32)
             for i, q in enumerate(teachers):
                 if q is not None:
                     A.teacher[i], A.ldq[i] = q.data_ptr(), q.stride(0)
             A.alpha, A.temperature, A.rowkd = float(spec.get("alpha", 0.5)), float(spec.get("temperature", 1.0)), rowkd.data_ptr()
-            L.check(lib.mtn_distill_fwd(C.byref(A), L.stream_ptr()))
+        L.check(fwd(C.byref(A), L.stream_ptr()))
+        if teachers is not None:
             spec["kd_sum"] = rowkd.sum()
-        ctx.args, ctx.keep = A, (x_lp, logits, lse, norms, targets, teachers if weighted is None else weighted)
+        ctx.args, ctx.bwd, ctx.keep = A, bwd, (x_lp, logits, lse, norms, targets, teachers if weighted is None else weighted)
         ctx.meta = (spec, segs, rows, offs, d, V, R, code, [x.shape for x in xs])
         return rowloss.sum()
 
     @staticmethod
     def backward(ctx, g):
-        lib = L.load()
         spec, segs, rows, offs, d, V, R, code, shapes = ctx.meta
-        x_lp, logits, lse, norms, targets, teachers = ctx.keep
+        x_lp, logits, lse = ctx.keep[:3]                      # (the rest is kept alive for the pointers in ctx.args)
         lp = spec["lp_dtype"]
         dev = x_lp.device
         A = ctx.args
         gl = g.contiguous().float().reshape(1)
         dlogits = torch.empty(R, V, device=dev, dtype=lp)
         A.gloss, A.dlogits, A.ldd = gl.data_ptr(), dlogits.data_ptr(), V
-        if isinstance(A, L.WLossHeadArgs):
-            L.check(lib.mtn_wlosshead_bwd(code, C.byref(A), L.stream_ptr()))
-        elif teachers is None:
-            L.check(lib.mtn_losshead_bwd(code, C.byref(A), L.stream_ptr()))
-        else:
-            L.check(lib.mtn_distill_bwd(code, C.byref(A), L.stream_ptr()))
+        L.check(ctx.bwd(code, C.byref(A), L.stream_ptr()))
         dx = torch.empty(R, d, device=dev, dtype=torch.float32)
         p_dx, p_dw = [], []
         for o, r, (w_lp, bias, gw, gb, *rest) in segs:

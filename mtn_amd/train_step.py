@@ -99,7 +99,7 @@ class TrainStep:
         with its vocabulary size.  Inside the step (and its captured graph) every active member runs an eval() forward on the step's
         batch under no_grad, the members' generator logits are combined by ops.ensemble_rows into one row of log-probabilities
         per target position, and the MAIN decoder stream's loss becomes (1 - distill_alpha) * label-smoothed KL + distill_alpha *
-        T^2 * KL(teacher_T || student_T) (csrc/distill.hip; the auto-encoder streams keep the plain loss).  The teacher pass runs
+        T^2 * KL(teacher_T || student_T) (csrc/losshead.hip; the auto-encoder streams keep the plain loss).  The teacher pass runs
         to completion before the student's forward starts and leaves nothing behind, so with distill_alpha == 0 the step is the
         undistilled step bit for bit.  ``last_kd``: device scalar, the step's summed row KL over its target-token normaliser.
         ``ema_decay``: > 0 = the optimiser built here keeps an exponential moving average of the weights (FusedAdam.enable_ema); a

@@ -1,4 +1,4 @@
-"""float64 reference and case list for the distillation loss head (csrc/distill.hip; include/mtn_hip.h mtn_distill_args), validated
+"""float64 reference and case list for the distillation loss head (csrc/losshead.hip; include/mtn_hip.h mtn_distill_args), validated
 without a GPU by tests/test_distill_refs.py and used on the device by tests/test_distill_kernel_gpu.py.  Plain helpers, no fixtures.
 
 composed         the hard part is row_refs.composed_loss (float64 log_softmax -> oracle label_smoothing_kl -> coef / norm, gradient by
@@ -132,7 +132,7 @@ def composed_distill(logits, targets, teachers, case, gloss=rr.GLOSS):
 
 
 def closed_form_f32(logits, targets, teachers, case, gloss=rr.GLOSS):
-    """The closed form of csrc/distill.hip in float32 with torch on the CPU: (lse, rowloss, rowkd, dlogits).  Not a reference."""
+    """The closed form of csrc/losshead.hip in float32 with torch on the CPU: (lse, rowloss, rowkd, dlogits).  Not a reference."""
     f = torch.float32
     lse, row_h, dz_h = rr.closed_form_f32(logits, targets, loss_case(case), gloss=gloss)
     dist, mask = seg_distilled(case), kd_rows_mask(case, targets)

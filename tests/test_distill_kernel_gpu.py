@@ -1,4 +1,4 @@
-"""mtn_distill_fwd / mtn_distill_bwd (csrc/distill.hip) through the C ABI against the float64 composed reference of
+"""mtn_distill_fwd / mtn_distill_bwd (csrc/losshead.hip) through the C ABI against the float64 composed reference of
 tests/distill_refs.py (validated without a GPU by tests/test_distill_refs.py), outputs and guard regions pre-filled with NaN.
 
 Where the bounds come from (none was obtained by running the kernel): the kernel is float32 with __expf / __logf.  The SAME closed form

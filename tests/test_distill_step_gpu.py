@@ -29,7 +29,7 @@ NAMES = ["small_shared", "cfg1_query"]
 def _config(name):
     """The golden configuration with its vocabulary rounded up to a multiple of 8 (60 -> 64, 100 -> 104): what the fused HIP loss head
     takes (tests/test_model_gpu.py::test_fused_loss_head_matches_composed_loss does the same) — below it the step composes the loss
-    from PyTorch ops and csrc/distill.hip would not run."""
+    from PyTorch ops and csrc/losshead.hip would not run."""
     c = fx.GOLDEN_CONFIGS[name]
     c = dict(c, vocab=-(-c["vocab"] // 8) * 8)
     assert c["vocab"] % 8 == 0

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """ms/step of the knowledge-distilled training step next to the plain one: cfg2 (run.sh's model), batch 32, bf16, dropout 0.1, captured
 graphs — no teacher, a same-size single teacher, a two-member ensemble teacher.  The expectation it confirms or refutes: a distilled
-step costs one eval() forward per teacher member plus a small head (csrc/distill.hip in the place of csrc/losshead.hip).
+step costs one eval() forward per teacher member plus a small head (the distillation form of csrc/losshead.hip in the place of the plain one).
 
     python tools/distill_bench.py [--steps 30] [--warmup 5] [--out profiles/distill_train_bench.json]
 """
