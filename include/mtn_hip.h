@@ -588,6 +588,48 @@ typedef struct {
 int mtn_wlosshead_fwd(const mtn_wlosshead_args* args, void* stream);
 int mtn_wlosshead_bwd(int dtype, const mtn_wlosshead_args* args, void* stream);
 
+/* Loss head with token-level unlikelihood (csrc/losshead.hip; detected by symbol, mtn_version() stays 125): the training-time repetition
+ * penalty of Welleck et al. 2019.  Every field of mtn_losshead_args keeps its meaning.  A segment with seq_len[s] = T > 0 holds rows[s] / T
+ * sequences of T positions, local row = b T + t (how trg_y.view(-1) lies); the earlier targets are read from target[s].  For a row whose
+ * target y_t is not <pad>, with z its logits, lse its log-sum-exp, p_j = exp(z_j - lse), and the negative candidates the SET
+ * C = { y_0 .. y_{t-1} } \ { y_t, <pad> } (each token once), scale = coef[s] / *norm[s], KL_ls, td, the zeroed rows and the lone-<pad> quirk
+ * the loss head's:
+ *   u_c     = 1 - p_c
+ *   ul      = sum_{c in C} -log(max(u_c, MTN_UL_CLAMP))     summed in an order the set fixes: two launches give the same bytes
+ *   rowloss = scale (KL_ls + ul_alpha ul)                   rowul (optional, [sum rows]) = ul, unscaled;  lse = as mtn_losshead_fwd writes it
+ *   bwd:      live(c) = c in C and u_c >= MTN_UL_CLAMP      (a clamped candidate has gradient 0, as torch.clamp gives)
+ *             r_c = p_c / u_c for live c, R = sum_{live c} r_c
+ *             dlogits_j = *gloss scale [(softmax_j sum(td) - td_j) + ul_alpha ([j live] r_j - p_j R)]; columns V..ldd-1 are +0.0
+ * ul = 0 and no extra gradient on every <pad>-target row (the quirk row included) and on every row with t = 0: those rows, every row of a
+ * segment with seq_len[s] == 0, and every segment when ul_alpha == 0 (the host drops seq_len) run the plain head's code: lse, rowloss and
+ * dlogits are those of mtn_losshead_fwd / _bwd on the same inputs bit for bit, rowul is +0.0.
+ * Candidates with u_c between 1e-9 and the clamp's far side (p_c between 0.9 and 1 - 1e-9) are outside what the tests hold: there 1 - p_c
+ * loses up to log2(1 / u_c) bits in float and which side of the clamp a candidate falls on is not stable.
+ * MTN_ERR_ARG, nothing launched: whatever mtn_losshead_fwd / _bwd refuse; ul_alpha negative or not finite; seq_len[s] < 0;
+ * rows[s] % seq_len[s] != 0; V > MTN_ULOSSHEAD_MAX_V (a bitmap of V bits per row lives in LDS).  Entries past n_seg are not looked at. */
+#define MTN_UL_CLAMP 1e-5f
+#define MTN_ULOSSHEAD_MAX_V 65536
+typedef struct {
+    int n_seg;
+    int rows[MTN_LOSSHEAD_MAX_SEG];
+    const long* target[MTN_LOSSHEAD_MAX_SEG];
+    const float* norm[MTN_LOSSHEAD_MAX_SEG];
+    float coef[MTN_LOSSHEAD_MAX_SEG];
+    int V, ldz, pad;
+    float smoothing;
+    const float* logits;
+    float* lse;
+    float* rowloss;
+    const float* gloss; /* backward: device scalar dL/dloss */
+    void* dlogits;
+    int ldd;
+    int seq_len[MTN_LOSSHEAD_MAX_SEG];
+    float ul_alpha;
+    float* rowul; /* optional */
+} mtn_ulosshead_args;
+int mtn_ulosshead_fwd(const mtn_ulosshead_args* args, void* stream);
+int mtn_ulosshead_bwd(int dtype, const mtn_ulosshead_args* args, void* stream);
+
 /* Transposed compute-dtype weight copies (operand of dX = dY W on the LDS-DMA GEMM path): for each descriptor the
  * [rows, cols] matrix at src+off is written as [cols, rows] at dst+dst_off (v111: the copies have a compact buffer of
  * their own — by default only the W_o^T matrices are kept).  `descs_device` is a DEVICE array (built once),

@@ -1,6 +1,6 @@
-// losshead.hip — generator log-softmax + label-smoothed KL divergence, fused per row, in its three forms: plain, with teacher soft
-// targets (word-level knowledge distillation, Hinton et al. 2015; Kim & Rush 2016) and with a signed weight per row (the policy-gradient
-// loss of self-critical sequence training).  include/mtn_hip.h states the contracts of the six entry points.
+// losshead.hip — generator log-softmax + label-smoothed KL divergence, fused per row, in its four forms: plain, with teacher soft
+// targets (word-level knowledge distillation, Hinton et al. 2015; Kim & Rush 2016), with a signed weight per row (the policy-gradient
+// loss of self-critical sequence training) and with token-level unlikelihood.  include/mtn_hip.h states the contracts of the eight entry points.
 //   Generator.forward      : log_softmax(proj(x))                          (mtn.py:62-69)
 //   LabelSmoothing.forward : KLDivLoss(sum)(logp, smoothed one-hot)        (label_smoothing.py:20-32)
 //   SimpleLossCompute      : sum_i coef_i * KL_i / norm_i                  (data_utils.py:133-144)
@@ -18,7 +18,12 @@
 // loses log2(|m_b - m_a|) bits to teacher logits with a common offset).  kd = 0 on rows whose target is <pad>; those rows never read q.
 // The reference's quirk is kept (label_smoothing.py:29): <pad> rows are zeroed only if the sum of their row indices is
 // positive, i.e. a lone <pad> target at flat row 0 keeps td = eps everywhere but the <pad> column.
-// The three forms are instantiations of the same code, so a segment without a teacher (or alpha == 0: the host drops the teacher
+//   unlikely  rowloss = scale (KL_ls + ul_alpha ul)                    dz_j = g scale [(softmax_j * sum(td) - td_j) + ul_alpha ([j live] r_j - p_j R)]
+// Unlikelihood (Welleck et al. 2019): the candidates C of a row are its sequence's earlier targets, as a set, without the row's own target
+// and <pad>; ul = sum_C -log(max(1 - p_c, 1e-5)), r_c = p_c / (1 - p_c) on unclamped candidates, R their sum.  The set is a bitmap of V bits
+// in the wave's LDS slice (lanes OR the earlier targets in); ul and R come from a walk over its words, the backward sweep tests its own
+// columns' bits, so every dlogits element is written once.  Rows without candidates (<pad>, t = 0, seq_len 0) take the plain path.
+// The forms are instantiations of the same code, so a segment without a teacher (or alpha == 0: the host drops the teacher
 // pointers; no (1 - alpha) factor is applied there) and a segment without weights at the loss head's smoothing (the weight is applied by
 // a multiplication of its own, which cannot be contracted into anything) give the plain head's lse, rowloss and dlogits bit for bit.
 // One 64-lane wave per row, float4 loads (z and q of a sweep issued together), wave-shuffle reductions in a fixed order, no atomics.
@@ -31,6 +36,7 @@
 
 template <typename Args> constexpr bool HEAD_DISTILL = std::is_same_v<Args, mtn_distill_args>;
 template <typename Args> constexpr bool HEAD_WEIGHTED = std::is_same_v<Args, mtn_wlosshead_args>;
+template <typename Args> constexpr bool HEAD_UL = std::is_same_v<Args, mtn_ulosshead_args>;
 
 struct HeadRow {
     int seg, local;      // segment (stream) and row inside it
@@ -42,6 +48,8 @@ struct HeadRow {
     float w = 1.0f;
     const float* q = nullptr;    // teacher row; nullptr: this row takes the plain path
     bool kd_seg = false;         // the segment is distilled: its hard part carries (1 - alpha)
+    int ul_t = 0;                // unlikelihood: position inside the sequence; 0: this row takes the plain path
+    const long* ul_prev = nullptr;   // the sequence's targets y_0 .. y_{t-1}
 };
 
 template <typename Args>
@@ -78,6 +86,13 @@ __device__ __forceinline__ HeadRow head_row(const Args& A, int row, int lane) {
     if constexpr (HEAD_DISTILL<Args>) {
         r.kd_seg = A.teacher[r.seg] != nullptr;
         r.q = (r.kd_seg && !r.t_is_pad) ? A.teacher[r.seg] + (size_t)r.local * A.ldq[r.seg] : nullptr;
+    }
+    if constexpr (HEAD_UL<Args>) {
+        const int T = A.seq_len[r.seg];
+        if (T > 0 && !r.t_is_pad) {                         // (<pad> rows, the quirk row included, and t = 0: no candidates)
+            r.ul_t = r.local % T;
+            r.ul_prev = A.target[r.seg] + (r.local - r.ul_t);
+        }
     }
     return r;
 }
@@ -158,6 +173,46 @@ __device__ __forceinline__ float head_wave_lse(float m, float s) {
     return m + __logf(s);
 }
 
+// Unlikelihood: the candidate set C = { y_0 .. y_{t-1} } \ { y_t, <pad> } of a row as a bitmap of V bits in the wave's own LDS slice.
+// LDS operations of one wave complete in issue order; the fence and the wave barrier keep the compiler from moving them.
+__device__ __forceinline__ void head_ul_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+__device__ __forceinline__ unsigned* head_ul_bitmap(const HeadRow& r, int V, int pad, int lane) {
+    extern __shared__ __attribute__((aligned(16))) unsigned head_ul_lds[];   // [4 waves][ceil(V / 32)]
+    const int words = (V + 31) >> 5;
+    unsigned* bits = head_ul_lds + (threadIdx.x >> 6) * words;
+    for (int w = lane; w < words; w += 64) bits[w] = 0u;
+    head_ul_sync();
+    for (int i = lane; i < r.ul_t; i += 64) {
+        const long y = r.ul_prev[i];
+        if (y >= 0 && y < V && y != r.t && y != pad) atomicOr(&bits[y >> 5], 1u << (y & 31));   // (a set: the order of the ORs is immaterial)
+    }
+    head_ul_sync();
+    return bits;
+}
+// sum over the candidates of -log(max(1 - p_c, clamp)) (forward) or of r_c = p_c / (1 - p_c) where unclamped (backward): a lane walks its
+// words' bits in ascending order, the lanes combine in wave_sum's order — fixed by V and the set alone
+template <bool BWD>
+__device__ __forceinline__ float head_ul_walk(const unsigned* bits, int V, const float* z, float lse, int lane) {
+    const int words = (V + 31) >> 5;
+    float acc = 0.f;
+    for (int w = lane; w < words; w += 64) {
+        unsigned m = bits[w];
+        while (m) {
+            const int c = (w << 5) + __ffs(m) - 1;
+            m &= m - 1;
+            const float p = __expf(z[c] - lse);
+            const float u = 1.0f - p;
+            if constexpr (BWD) {
+                if (u >= MTN_UL_CLAMP) acc += p / u;
+            } else acc -= __logf(fmaxf(u, MTN_UL_CLAMP));
+        }
+    }
+    return wave_sum(acc);
+}
+
 template <typename Args>
 __global__ __launch_bounds__(256) void losshead_fwd_kernel(const Args A, int total_rows) {
     const int lane = threadIdx.x & 63;
@@ -166,7 +221,7 @@ __global__ __launch_bounds__(256) void losshead_fwd_kernel(const Args A, int tot
     const HeadRow r = head_row(A, row, lane);
     const float* z = A.logits + (size_t)row * A.ldz;
     const int V = A.V;
-    float lse, S, kd = 0.f;
+    float lse, S, kd = 0.f, ul = 0.f;
     if (r.q == nullptr) lse = head_lse(z, V, lane, S);
     else if constexpr (HEAD_DISTILL<Args>) {
         const float* q = r.q;
@@ -213,17 +268,24 @@ __global__ __launch_bounds__(256) void losshead_fwd_kernel(const Args A, int tot
         const float lga = t1 ? lg : __logf(wave_sum(sa));
         kd = num / sb - __logf(sb) + lga;
     }
+    if constexpr (HEAD_UL<Args>) {
+        if (r.ul_t > 0) ul = head_ul_walk<false>(head_ul_bitmap(r, V, A.pad, lane), V, z, lse, lane);
+    }
     if (lane == 0) {
         A.lse[row] = lse;
         float loss = 0.f;
         if (!r.zero_row) {                                   // (the KL inside each branch: hoisted, the compiler contracts it otherwise)
-            if (!r.kd_seg) loss = head_hard_kl(r, z, V, A.pad, S, lse) * (r.weighted ? r.scale * r.w : r.scale);
+            if (!r.kd_seg && r.ul_t == 0) loss = head_hard_kl(r, z, V, A.pad, S, lse) * (r.weighted ? r.scale * r.w : r.scale);
+            else if constexpr (HEAD_UL<Args>) loss = r.scale * (head_hard_kl(r, z, V, A.pad, S, lse) + A.ul_alpha * ul);
             else if constexpr (HEAD_DISTILL<Args>)
                 loss = r.scale * ((1.0f - A.alpha) * head_hard_kl(r, z, V, A.pad, S, lse) + (A.alpha * A.temperature * A.temperature) * kd);
         }
         A.rowloss[row] = loss;
         if constexpr (HEAD_DISTILL<Args>) {
             if (A.rowkd) A.rowkd[row] = kd;
+        }
+        if constexpr (HEAD_UL<Args>) {
+            if (A.rowul) A.rowul[row] = ul;
         }
     }
 }
@@ -242,7 +304,34 @@ __global__ __launch_bounds__(256) void losshead_bwd_kernel(const Args A, int tot
     const float eps = r.eps, conf = r.conf;
     const float sum_td = r.zero_row ? 0.f : (r.t_is_pad ? (float)(V - 1) * eps : (float)(V - 2) * eps + conf);
     const float lse = A.lse[row];
-    if (!r.kd_seg) head_hard_bwd<T>(r, z, dz, V, A.ldd, A.pad, g, sum_td, lse, lane);
+    if (!r.kd_seg && r.ul_t == 0) head_hard_bwd<T>(r, z, dz, V, A.ldd, A.pad, g, sum_td, lse, lane);
+    else if constexpr (HEAD_UL<Args>) {                      // (a row with candidates is live: never a zeroed row)
+        const unsigned* bits = head_ul_bitmap(r, V, A.pad, lane);
+        const float R = head_ul_walk<true>(bits, V, z, lse, lane);
+        const float ua = A.ul_alpha;
+        for (int c = lane * 4; c < A.ldd; c += 256) {
+            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (c < V) {
+                const float4 v = *(const float4*)(z + c);
+                const unsigned m = bits[c >> 5] >> (c & 31);    // the sweep tests its own columns' bits: every element is written once
+                float* ov = &o.x;
+                const float* vv = &v.x;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int j = c + k;
+                    float td = eps;
+                    if (j == A.pad) td = 0.f;
+                    else if (j == r.t) td = conf;
+                    const float p = __expf(vv[k] - lse);
+                    const float u = 1.0f - p;
+                    float e = -(p * R);
+                    if (((m >> k) & 1u) && u >= MTN_UL_CLAMP) e += p / u;
+                    ov[k] = g * ((p * sum_td - td) + ua * e);
+                }
+            }
+            store_lp4<T>(dz + c, o);
+        }
+    }
     else if constexpr (HEAD_DISTILL<Args>) {
         const float* q = r.q;
         const float wh = 1.0f - A.alpha, ws = A.alpha * A.temperature;
@@ -301,6 +390,10 @@ static int head_check(const char* fn, const Args* A, bool bwd, int dtype, Args* 
         HEAD_CHECK(isfinite(A->alpha) && A->alpha >= 0.f && A->alpha <= 1.f, "alpha outside [0, 1]");
         HEAD_CHECK(isfinite(A->temperature) && A->temperature > 0.f, "temperature must be finite and > 0");
     }
+    if constexpr (HEAD_UL<Args>) {
+        HEAD_CHECK(isfinite(A->ul_alpha) && A->ul_alpha >= 0.f, "ul_alpha must be finite and >= 0");
+        HEAD_CHECK(A->V <= MTN_ULOSSHEAD_MAX_V, "V above MTN_ULOSSHEAD_MAX_V");
+    }
     *D = *A;
     *total = 0;
     for (int s = 0; s < A->n_seg; ++s) {
@@ -313,6 +406,10 @@ static int head_check(const char* fn, const Args* A, bool bwd, int dtype, Args* 
             HEAD_CHECK(((uintptr_t)A->roww[s] & 3) == 0, "row weights must be 4-byte aligned");
             HEAD_CHECK(!isnan(A->smoothing_seg[s]), "smoothing_seg is NaN");
         }
+        if constexpr (HEAD_UL<Args>) {
+            HEAD_CHECK(A->seq_len[s] >= 0, "seq_len < 0");
+            HEAD_CHECK(A->seq_len[s] == 0 || A->rows[s] % A->seq_len[s] == 0, "rows must be a multiple of seq_len");
+        }
         *total += A->rows[s];
     }
 #undef HEAD_CHECK
@@ -320,7 +417,21 @@ static int head_check(const char* fn, const Args* A, bool bwd, int dtype, Args* 
         for (int s = 0; s < MTN_LOSSHEAD_MAX_SEG; ++s)      // never read: the plain arithmetic, no (1 - alpha) factor
             if (s >= A->n_seg || A->alpha == 0.f) D->teacher[s] = nullptr;
     }
+    if constexpr (HEAD_UL<Args>) {
+        for (int s = 0; s < MTN_LOSSHEAD_MAX_SEG; ++s)      // seq_len 0: the plain arithmetic, no bitmap
+            if (s >= A->n_seg || A->ul_alpha == 0.f) D->seq_len[s] = 0;
+    }
     return MTN_OK;
+}
+
+// dynamic LDS of a launch: the unlikelihood bitmaps, one of V bits per wave, when any segment has candidates
+template <typename Args>
+static size_t head_lds(const Args& D) {
+    if constexpr (HEAD_UL<Args>) {
+        for (int s = 0; s < D.n_seg; ++s)
+            if (D.seq_len[s] > 0) return (size_t)4 * ((D.V + 31) / 32) * sizeof(unsigned);
+    }
+    return 0;
 }
 
 static int head_launched(const char* fn) {
@@ -336,7 +447,7 @@ static int head_fwd(const char* fn, const Args* A, void* stream) {
     int total = 0;
     const int rc = head_check(fn, A, false, 0, &D, &total);
     if (rc != MTN_OK) return rc;
-    hipLaunchKernelGGL(losshead_fwd_kernel<Args>, dim3((total + 3) / 4), dim3(256), 0, (hipStream_t)stream, D, total);
+    hipLaunchKernelGGL(losshead_fwd_kernel<Args>, dim3((total + 3) / 4), dim3(256), head_lds(D), (hipStream_t)stream, D, total);
     return head_launched(fn);
 }
 
@@ -347,8 +458,8 @@ static int head_bwd(const char* fn, int dtype, const Args* A, void* stream) {
     const int rc = head_check(fn, A, true, dtype, &D, &total);
     if (rc != MTN_OK) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    if (dtype == MTN_BF16) hipLaunchKernelGGL((losshead_bwd_kernel<bf16_t, Args>), dim3((total + 3) / 4), dim3(256), 0, st, D, total);
-    else hipLaunchKernelGGL((losshead_bwd_kernel<float, Args>), dim3((total + 3) / 4), dim3(256), 0, st, D, total);
+    if (dtype == MTN_BF16) hipLaunchKernelGGL((losshead_bwd_kernel<bf16_t, Args>), dim3((total + 3) / 4), dim3(256), head_lds(D), st, D, total);
+    else hipLaunchKernelGGL((losshead_bwd_kernel<float, Args>), dim3((total + 3) / 4), dim3(256), head_lds(D), st, D, total);
     return head_launched(fn);
 }
 
@@ -358,3 +469,5 @@ extern "C" int mtn_distill_fwd(const mtn_distill_args* A, void* stream) { return
 extern "C" int mtn_distill_bwd(int dtype, const mtn_distill_args* A, void* stream) { return head_bwd(__func__, dtype, A, stream); }
 extern "C" int mtn_wlosshead_fwd(const mtn_wlosshead_args* A, void* stream) { return head_fwd(__func__, A, stream); }
 extern "C" int mtn_wlosshead_bwd(int dtype, const mtn_wlosshead_args* A, void* stream) { return head_bwd(__func__, dtype, A, stream); }
+extern "C" int mtn_ulosshead_fwd(const mtn_ulosshead_args* A, void* stream) { return head_fwd(__func__, A, stream); }
+extern "C" int mtn_ulosshead_bwd(int dtype, const mtn_ulosshead_args* A, void* stream) { return head_bwd(__func__, dtype, A, stream); }

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import contextlib
 import logging
+import math
 import os
 
 from typing import List, Optional
@@ -368,6 +369,23 @@ class NoamOpt:
         return self.factor * (self.model_size ** (-0.5) * min(step ** (-0.5), step * self.warmup ** (-1.5)))
 
 
+UL_CLAMP = 9.999999747378752e-06            # MTN_UL_CLAMP (include/mtn_hip.h): the float 1e-5f, fairseq's clamp
+
+
+def unlikelihood_rows(logp, y, pad):
+    """Token-level unlikelihood (Welleck et al. 2019) composed from PyTorch ops, the definition include/mtn_hip.h states for
+    mtn_ulosshead_args: ``logp`` (B, T, V) log-probabilities, ``y`` (B, T) targets -> (B, T) ul = sum over the set of the sequence's
+    earlier targets, without the row's own target and <pad>, of -log(clamp(1 - p_c, min=MTN_UL_CLAMP)); 0 on <pad>-target rows."""
+    B, T, V = logp.shape
+    onehot = torch.zeros(B, T, V, dtype=torch.bool, device=logp.device).scatter_(2, y.unsqueeze(2), True)
+    cand = (onehot.cumsum(1) - onehot.long()) > 0                      # seen at an earlier position
+    cand &= ~onehot                                                     # not the row's own target
+    cand[:, :, pad] = False
+    cand &= (y != pad).unsqueeze(2)
+    u = torch.clamp(1.0 - logp.exp(), min=UL_CLAMP)
+    return -(torch.where(cand, u, torch.ones_like(u)).log()).sum(2)
+
+
 class SimpleLossCompute:
     """generator -> label-smoothed KL (+ lambda * auto-encoder losses) -> backward -> optimiser step
     (data_utils.py:123-156).  ``sync=False`` returns the device tensor instead of ``loss.item()*norm`` so that the
@@ -378,8 +396,10 @@ class SimpleLossCompute:
         self.generator, self.ae_generator, self.criterion = generator, ae_generator, criterion
         self.opt, self.l, self.sync, self.grad_sync, self.fused = opt, l, sync, grad_sync, fused
         self.last_kd_sum = None
+        self.last_ul_sum = None
 
-    def _fused_loss(self, x, y, norm, ae_x, ae_y, ae_norm, teacher_logp=None, alpha=0.0, temperature=1.0, row_weights=None, smoothing=None):
+    def _fused_loss(self, x, y, norm, ae_x, ae_y, ae_norm, teacher_logp=None, alpha=0.0, temperature=1.0, row_weights=None, smoothing=None,
+                    unlikelihood=0.0):
         """Generator + log-softmax + label-smoothed KL + weighted sum as the fused HIP loss head (ops.GeneratorLossFn).
         Returns None when the fused path does not apply (CPU tensors, un-flattened model, vocab not a multiple of 8,
         foreign criterion): the caller then composes the same value from PyTorch ops."""
@@ -413,8 +433,11 @@ class SimpleLossCompute:
             w = None if row_weights is None else row_weights.detach().reshape(-1)
             spec["row_weights"] = [w] + [None] * (len(xs) - 1)
             spec["smoothing_seg"] = [smoothing] + [None] * (len(xs) - 1)
+        if unlikelihood > 0.0:                  # the main stream only, as the teacher
+            spec["unlikelihood"] = (unlikelihood, [y.size(1)] + [None] * (len(xs) - 1))
         out = ops.GeneratorLossFn.apply(spec, *xs)
         self.last_kd_sum = spec.get("kd_sum")
+        self.last_ul_sum = spec.get("ul_sum")
         return out
 
     def _weighted_rows(self, logp, y, row_weights, smoothing):
@@ -432,7 +455,7 @@ class SimpleLossCompute:
         return kl.sum() if row_weights is None else (row_weights.detach().reshape(-1).to(kl.dtype) * kl).sum()
 
     def loss(self, x, y, norm, ae_x=None, ae_y=None, ae_norm=None, teacher_logp=None, alpha=0.0, temperature=1.0, row_weights=None,
-             smoothing=None):
+             smoothing=None, unlikelihood=0.0):
         """``teacher_logp``: (rows, V) fp32 teacher log-probabilities (or logits: they are normalised) for the main stream — word-level
         knowledge distillation, loss = (1 - alpha) KL_ls + alpha T^2 KL(softmax(q / T) || softmax(z / T)) over the rows whose target is
         not <pad>, both over ``norm`` (include/mtn_hip.h mtn_distill_args).  alpha == 0 is the plain loss.  ``last_kd_sum`` is left
@@ -440,7 +463,21 @@ class SimpleLossCompute:
         ``row_weights``: one fp32 weight per main-stream row (signed; no gradient flows into it), loss = sum_rows w KL_ls / norm — the
         policy-gradient loss of self-critical sequence training when w = -(reward - baseline); ``smoothing``: the main stream's label
         smoothing in the place of the criterion's (0: KL_ls = -log p(target)).  The auto-encoder streams keep the plain loss.  Not
-        together with a teacher (include/mtn_hip.h mtn_wlosshead_args)."""
+        together with a teacher (include/mtn_hip.h mtn_wlosshead_args).
+        ``unlikelihood``: alpha >= 0 of token-level unlikelihood training on the main stream, ``y`` (B, T): loss = (KL_ls + alpha
+        sum_rows ul) / norm with ul the row's sum over its sequence's earlier targets (a set, without the row's own target and <pad>) of
+        -log(clamp(1 - p_c, 1e-5)) (include/mtn_hip.h mtn_ulosshead_args).  0 is the plain loss.  ``last_ul_sum`` is left holding
+        sum_rows ul (None at 0).  Not together with a teacher or row weights."""
+        unlikelihood = float(unlikelihood)
+        if not (unlikelihood >= 0.0 and math.isfinite(unlikelihood)):
+            raise ValueError("unlikelihood: alpha is finite and >= 0")
+        if unlikelihood > 0.0:
+            if teacher_logp is not None:
+                raise ValueError("unlikelihood and teacher soft targets do not combine")
+            if row_weights is not None or smoothing is not None:
+                raise ValueError("unlikelihood and row weights do not combine")
+            if y.dim() != 2:
+                raise ValueError("unlikelihood: y is (B, T)")
         if teacher_logp is not None and not (0.0 <= float(alpha) <= 1.0 and 0.0 < float(temperature) < float("inf")):
             raise ValueError("distillation: alpha in [0, 1] and a finite temperature > 0")
         weighted = row_weights is not None or smoothing is not None
@@ -451,8 +488,9 @@ class SimpleLossCompute:
         if row_weights is not None and row_weights.numel() != y.numel():
             raise ValueError("row_weights: one weight per target row")
         self.last_kd_sum = None
+        self.last_ul_sum = None
         fused = self._fused_loss(x, y, norm, ae_x, ae_y, ae_norm, teacher_logp, alpha, temperature, row_weights,
-                                 None if smoothing is None else float(smoothing)) if self.fused else None
+                                 None if smoothing is None else float(smoothing), unlikelihood) if self.fused else None
         if fused is not None:
             return fused
         if teacher_logp is not None and float(alpha) == 0.0:
@@ -473,6 +511,10 @@ class SimpleLossCompute:
             kd = torch.where(live, kd, torch.zeros_like(kd)).sum()
             self.last_kd_sum = kd.detach()
             loss = (1.0 - float(alpha)) * loss + float(alpha) * T * T * kd / norm.float()
+        if unlikelihood > 0.0:
+            ul = unlikelihood_rows(out.reshape(y.size(0), y.size(1), out.size(-1)), y, self.criterion.padding_idx).sum()
+            self.last_ul_sum = ul.detach()
+            loss = loss + unlikelihood * ul / norm.float()
         if ae_x is not None:
             xs = ae_x if isinstance(ae_x, (list, tuple)) else [ae_x]
             for i, ae_in in enumerate(xs):
@@ -484,8 +526,8 @@ class SimpleLossCompute:
                 loss = loss + self.l * self.criterion(ae_out.reshape(-1, ae_out.size(-1)), ae_y.reshape(-1)) / ae_norm.float()
         return loss
 
-    def __call__(self, x, y, norm, ae_x=None, ae_y=None, ae_norm=None, teacher_logp=None, alpha=0.0, temperature=1.0):
-        loss = self.loss(x, y, norm, ae_x, ae_y, ae_norm, teacher_logp, alpha, temperature)
+    def __call__(self, x, y, norm, ae_x=None, ae_y=None, ae_norm=None, teacher_logp=None, alpha=0.0, temperature=1.0, unlikelihood=0.0):
+        loss = self.loss(x, y, norm, ae_x, ae_y, ae_norm, teacher_logp, alpha, temperature, unlikelihood=unlikelihood)
         if self.opt is not None:
             loss.backward()
             if self.grad_sync is not None:

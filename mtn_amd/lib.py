@@ -104,6 +104,10 @@ class WLossHeadArgs(C.Structure):
     _fields_ = LossHeadArgs._fields_ + [("roww", C.c_void_p * 4), ("smoothing_seg", C.c_float * 4)]
 
 
+class ULossHeadArgs(C.Structure):
+    _fields_ = LossHeadArgs._fields_ + [("seq_len", C.c_int * 4), ("ul_alpha", C.c_float), ("rowul", C.c_void_p)]
+
+
 class TransposeDesc(C.Structure):
     _fields_ = [("off", C.c_long), ("rows", C.c_int), ("cols", C.c_int), ("tile_start", C.c_int), ("reserved", C.c_int), ("dst_off", C.c_long)]
 
@@ -316,6 +320,8 @@ SYMBOLS = {
     "mtn_distill_bwd": (C.c_int, [C.c_int, C.POINTER(DistillHeadArgs), _P]),
     "mtn_wlosshead_fwd": (C.c_int, [C.POINTER(WLossHeadArgs), _P]),
     "mtn_wlosshead_bwd": (C.c_int, [C.c_int, C.POINTER(WLossHeadArgs), _P]),
+    "mtn_ulosshead_fwd": (C.c_int, [C.POINTER(ULossHeadArgs), _P]),
+    "mtn_ulosshead_bwd": (C.c_int, [C.c_int, C.POINTER(ULossHeadArgs), _P]),
     "mtn_eval_table_build": (C.c_int, [C.POINTER(EvalRowsArgs), _P]),
     "mtn_eval_score_rows": (C.c_int, [C.POINTER(EvalRowsArgs), _P]),
     "mtn_scst_assemble": (C.c_int, [C.POINTER(ScstAssembleArgs), _P]),

@@ -1680,6 +1680,27 @@ def _row_weights(spec, rows, dev):
     return weights, sms
 
 
+def _unlikelihood(spec, rows):
+    """spec["unlikelihood"] = (alpha, seq_lens per stream: an int or None) checked against the streams: None when it is absent, alpha is 0
+    or no stream has a sequence length (the plain loss head runs), else (alpha, [T per stream, 0 = none])."""
+    ul = spec.get("unlikelihood")
+    if ul is None:
+        return None
+    alpha, lens = ul
+    alpha = float(alpha)
+    if not (alpha >= 0.0 and math.isfinite(alpha)):
+        raise ValueError("GeneratorLossFn: the unlikelihood alpha is finite and >= 0")
+    if len(lens) != len(rows):
+        raise ValueError("GeneratorLossFn: spec['unlikelihood'] holds one sequence length (an int or None) per stream")
+    lens = [0 if T is None else int(T) for T in lens]
+    for T, r in zip(lens, rows):
+        if T < 0 or (T > 0 and r % T != 0):
+            raise ValueError("GeneratorLossFn: a stream's rows are a multiple of its sequence length")
+    if alpha == 0.0 or not any(lens):
+        return None
+    return alpha, lens
+
+
 class GeneratorLossFn(torch.autograd.Function):
     """sum_i coef_i * KLDiv(log_softmax(x_i W_i^T + b_i), smooth(y_i)) / norm_i  — Generator (mtn.py:62-69) +
     LabelSmoothing (label_smoothing.py) + SimpleLossCompute's weighted sum (data_utils.py:133-144) as: one grouped cast,
@@ -1692,7 +1713,10 @@ class GeneratorLossFn(torch.autograd.Function):
     left holding the device scalar sum_rows kd; with none the calls are exactly the loss head's.
     Signed row weights (self-critical sequence training): ``spec["row_weights"]`` = per stream a contiguous fp32 device tensor of one weight
     per row or None (all ones), ``spec["smoothing_seg"]`` = per stream a smoothing or None (the spec's).  With either present the row
-    kernels are mtn_wlosshead_fwd / _bwd (csrc/losshead.hip); not together with a teacher."""
+    kernels are mtn_wlosshead_fwd / _bwd (csrc/losshead.hip); not together with a teacher.
+    Unlikelihood training (Welleck et al. 2019): ``spec["unlikelihood"]`` = (alpha, per stream the sequence length T of its (B, T) targets
+    or None).  With it present and alpha > 0 the row kernels are mtn_ulosshead_fwd / _bwd (csrc/losshead.hip; include/mtn_hip.h), casts and
+    GEMMs unchanged, and ``spec["ul_sum"]`` is left holding the device scalar sum_rows ul; not together with a teacher or row weights."""
 
     @staticmethod
     def forward(ctx, spec, *xs):
@@ -1746,7 +1770,13 @@ class GeneratorLossFn(torch.autograd.Function):
         weighted = _row_weights(spec, rows, dev)
         if teachers is not None and weighted is not None:
             raise ValueError("GeneratorLossFn: row weights and teacher soft targets do not combine")
-        if weighted is not None:
+        unlikely = _unlikelihood(spec, rows)
+        if unlikely is not None and (teachers is not None or weighted is not None):
+            raise ValueError("GeneratorLossFn: unlikelihood does not combine with %s" % ("teacher soft targets" if teachers is not None
+                                                                                         else "row weights"))
+        if unlikely is not None:
+            args_cls, fwd, bwd = L.ULossHeadArgs, lib.mtn_ulosshead_fwd, lib.mtn_ulosshead_bwd
+        elif weighted is not None:
             args_cls, fwd, bwd = L.WLossHeadArgs, lib.mtn_wlosshead_fwd, lib.mtn_wlosshead_bwd
         elif teachers is not None:
             args_cls, fwd, bwd = L.DistillHeadArgs, lib.mtn_distill_fwd, lib.mtn_distill_bwd
@@ -1771,9 +1801,16 @@ class GeneratorLossFn(torch.autograd.Function):
                 if q is not None:
                     A.teacher[i], A.ldq[i] = q.data_ptr(), q.stride(0)
             A.alpha, A.temperature, A.rowkd = float(spec.get("alpha", 0.5)), float(spec.get("temperature", 1.0)), rowkd.data_ptr()
+        elif unlikely is not None:
+            rowul = torch.empty(R, device=dev, dtype=torch.float32)
+            for i, T in enumerate(unlikely[1]):
+                A.seq_len[i] = T
+            A.ul_alpha, A.rowul = unlikely[0], rowul.data_ptr()
         L.check(fwd(C.byref(A), L.stream_ptr()))
         if teachers is not None:
             spec["kd_sum"] = rowkd.sum()
+        if unlikely is not None:
+            spec["ul_sum"] = rowul.sum()
         ctx.args, ctx.bwd, ctx.keep = A, bwd, (x_lp, logits, lse, norms, targets, teachers if weighted is None else weighted)
         ctx.meta = (spec, segs, rows, offs, d, V, R, code, [x.shape for x in xs])
         return rowloss.sum()

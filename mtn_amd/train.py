@@ -109,8 +109,12 @@ def parse(argv=None):
     p.add_argument("--scst-top-p", default=1.0, type=float)
     p.add_argument("--scst-xe-weight", default=0.0, type=float, metavar="W",
                    help="> 0: the gold answer is one more row per dialogue with the constant weight W (smoothing 0)")
+    # unlikelihood training: the training-time repetition penalty (generate.py's --no-repeat-ngram / --repetition-penalty act at decode time)
+    p.add_argument("--unlikelihood-alpha", default=0.0, type=float, metavar="A",
+                   help="> 0: the response stream's loss gains A * sum over each target position of -log(1 - p(c)) over the response's "
+                        "earlier tokens c (Welleck et al. 2019); validation stays the plain loss (0: off)")
     args = p.parse_args(argv)
-    err = distill_flag_error(args) or ema_flag_error(args) or scst_flag_error(args)
+    err = distill_flag_error(args) or ema_flag_error(args) or scst_flag_error(args) or unlikelihood_flag_error(args)
     if err:
         p.error(err)
     return args
@@ -177,6 +181,19 @@ def scst_flag_error(args, world=None):
     if not args.train_set and args.corpus_videos <= 0:
         return ("--scst-samples does not combine with the fixed synthetic batch: rewards need a corpus of answers "
                 "(--train-set or --corpus-videos)")
+    return None
+
+
+def unlikelihood_flag_error(args):
+    """What is wrong with --unlikelihood-alpha, or what it conflicts with, as one line (None: nothing).  0 = off."""
+    import math
+    a = args.unlikelihood_alpha
+    if not (a >= 0.0 and math.isfinite(a)):        # (nan fails the comparison)
+        return "--unlikelihood-alpha must be finite and >= 0 (got %r)" % a
+    if a > 0.0 and args.distill_model:
+        return "--unlikelihood-alpha does not combine with --distill-model: unlikelihood under distillation is out of scope"
+    if a > 0.0 and args.scst_samples:
+        return "--unlikelihood-alpha does not combine with --scst-samples: unlikelihood under self-critical training is out of scope"
     return None
 
 
@@ -285,7 +302,8 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
     """The same epoch on captured graphs (train_step.BucketedTrainer): lengths rounded up to the bucket, one graph per padded
     shape, batches assembled in place on the device; the host only syncs at the report interval.  ``cut``: the --cut-a
     RandomState (None = no truncation).  Returns (mean loss per token, target tokens of the epoch over all ranks).  ``stats``: a dict
-    that receives "kd", the epoch's mean distillation KL per token, when the trainer has a teacher, and "reward" / "baseline", the
+    that receives "kd", the epoch's mean distillation KL per token, when the trainer has a teacher, "ul", the epoch's mean unlikelihood per
+    token, when it trains with unlikelihood, and "reward" / "baseline", the
     mean over the epoch's steps of the steps' mean reward and mean baseline, when it trains self-critically."""
     order = list(range(len(indices)))
     rng.shuffle(order)
@@ -294,6 +312,7 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
     scst = getattr(trainer, "scst", None) is not None
     rl_sum = torch.zeros(2, device=dev, dtype=torch.float64)
     kd_sum = torch.zeros((), device=dev) if trainer.teacher is not None else None
+    ul_sum = torch.zeros((), device=dev) if getattr(trainer, "unlikelihood", 0.0) > 0.0 else None
     tok_sum = torch.zeros((), device=dev, dtype=torch.int64)
     t0, tok0 = time.time(), 0
     for j, k in enumerate(order):
@@ -305,6 +324,8 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
         tok_sum += n_glob
         if kd_sum is not None:
             kd_sum += trainer.last_kd * n_glob
+        if ul_sum is not None:
+            ul_sum += trainer.last_ul * n_glob
         if scst:
             rl_sum += torch.stack([trainer.last_reward, trainer.last_baseline])
         if (j + 1) % report_interval == 0 and rank == 0:
@@ -316,7 +337,11 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
         torch.distributed.all_reduce(loss_sum)
         if kd_sum is not None:
             torch.distributed.all_reduce(kd_sum)
+        if ul_sum is not None:
+            torch.distributed.all_reduce(ul_sum)
     ntok = int(tok_sum)
+    if ul_sum is not None and stats is not None:
+        stats["ul"] = float(ul_sum) / max(1, ntok)
     if kd_sum is not None and stats is not None:
         stats["kd"] = float(kd_sum) / max(1, ntok)
     if scst and stats is not None:
@@ -354,31 +379,37 @@ def global_norms(b, ae_y, sync):
     return norms, local_ntok
 
 
-def run_epoch(corpus, indices, model, loss_compute, ae_ft, epoch, report_interval, rank, rng, cut=None, distill=None, stats=None):
+def run_epoch(corpus, indices, model, loss_compute, ae_ft, epoch, report_interval, rank, rng, cut=None, distill=None, stats=None,
+              unlikelihood=0.0):
     """train.py:23-50: shuffle the planned batches, assemble each on the device, forward, loss + backward + optimiser.
     Data parallel: the loss normalisers are the GLOBAL token counts of the step (all ranks' batches), so that the summed
     gradients are those of one rank on the concatenated batch (dp.py) — as the captured schedule does (TrainStep._norms).
     ``cut``: the --cut-a RandomState (None = no truncation).  Returns (mean loss per token, target tokens over all ranks).
     ``distill``: (teacher, alpha, temperature) — the teacher's rows are computed before the student's forward (train_step.teacher_rows);
-    ``stats`` then receives "kd", this rank's mean distillation KL per token."""
+    ``stats`` then receives "kd", this rank's mean distillation KL per token.  ``unlikelihood``: alpha of SimpleLossCompute.loss;
+    ``stats`` then receives "ul", this rank's mean unlikelihood per token."""
     from .data_handler import make_batch
     from .train_step import teacher_rows
     order = list(range(len(indices)))
     rng.shuffle(order)
     t0, tokens, total_loss, total_tokens, global_tokens = time.time(), 0, 0.0, 0, 0
     sync = loss_compute.grad_sync
-    kd_total = 0.0
+    kd_total = ul_total = 0.0
     for j, k in enumerate(order):
         b = make_batch(corpus, indices[k], 1, separate_caption=True, cut_a=cut is not None, rng=cut)
         kw = {}
         if distill is not None:
             kw = dict(teacher_logp=teacher_rows(distill[0], b), alpha=distill[1], temperature=distill[2])
+        if unlikelihood > 0.0:
+            kw = dict(unlikelihood=unlikelihood)
         out, ae_out = model.forward(b)
         ae_y = b.cap if ae_ft in ("caption", "summary") else b.query
         norms, local_ntok = global_norms(b, ae_y, sync)
         loss = loss_compute(out, b.trg_y, norms[0], ae_out, ae_y, norms[1], **kw)     # = normalised loss x global target tokens
         if distill is not None and loss_compute.last_kd_sum is not None:
             kd_total += float(loss_compute.last_kd_sum)
+        if loss_compute.last_ul_sum is not None:
+            ul_total += float(loss_compute.last_ul_sum)
         n_glob = float(norms[0])
         loss = loss * local_ntok / n_glob                                       # this rank's share, for the epoch mean below
         total_loss += loss
@@ -391,6 +422,8 @@ def run_epoch(corpus, indices, model, loss_compute, ae_ft, epoch, report_interva
             t0, tokens = time.time(), 0
     if distill is not None and stats is not None:
         stats["kd"] = kd_total / max(1, total_tokens)
+    if unlikelihood > 0.0 and stats is not None:
+        stats["ul"] = ul_total / max(1, total_tokens)
     return total_loss / max(1, total_tokens), global_tokens
 
 
@@ -490,7 +523,7 @@ def main(argv=None):
             from .train_step import BucketedTrainer
             trainer = BucketedTrainer(model, corpus, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l,
                                       bucket=args.bucket, grad_sync=sync, ema_decay=args.ema_decay, scst=scst,
-                                      use_graph=not (args.eager and scst is not None), **distill)
+                                      use_graph=not (args.eager and scst is not None), unlikelihood=args.unlikelihood_alpha, **distill)
         valid = None
         if args.valid_videos > 0 or valid_data is not None:
             vdata = valid_data if valid_data is not None else synthetic_corpus(args.valid_videos, args.vocab_size, args.ft_sizes, args.rand_seed + 1000)
@@ -511,7 +544,8 @@ def main(argv=None):
             stats = {}
             if not graphed:
                 mean, ntok = run_epoch(corpus, indices, model, lc, args.auto_encoder_ft, epoch, args.report_interval, rank, rng, cut,
-                                       distill=(teacher, args.distill_alpha, args.distill_temperature) if teacher is not None else None, stats=stats)
+                                       distill=(teacher, args.distill_alpha, args.distill_temperature) if teacher is not None else None, stats=stats,
+                                       unlikelihood=args.unlikelihood_alpha)
             else:
                 mean, ntok = run_epoch_graphed(trainer, indices, epoch, args.report_interval, rank, rng, cut, stats=stats)
             means.append(mean)
@@ -521,6 +555,8 @@ def main(argv=None):
                 print("epoch %d mean train loss per token: %f" % (epoch + 1, mean))
                 if "kd" in stats:
                     print("epoch %d mean distillation KL per token: %f" % (epoch + 1, stats["kd"]))
+                if "ul" in stats:
+                    print("epoch %d mean unlikelihood per token: %f" % (epoch + 1, stats["ul"]))
                 if "reward" in stats:
                     print("epoch %d mean reward: %f mean baseline: %f" % (epoch + 1, stats["reward"], stats["baseline"]))
             if args.model:
@@ -571,14 +607,17 @@ def main(argv=None):
     Q, H, C, T, V = args.lens
     batch = synthetic_batch(args.vocab_size, args.batch_size, Q, H, C, T, [V] * len(args.ft_sizes), args.ft_sizes, device=dev, seed=1 + rank)
     step = TrainStep(model, batch, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l, grad_sync=sync, ema_decay=args.ema_decay,
-                     **distill)
+                     unlikelihood=args.unlikelihood_alpha, **distill)
     ntok = int(batch.ntokens) * world
     for epoch in range(args.num_epochs):
         t0, tokens = time.time(), 0
         kd_sum = torch.zeros((), device=dev) if teacher is not None else None
+        ul_sum = torch.zeros((), device=dev) if args.unlikelihood_alpha > 0.0 else None
         for j in range(args.steps_per_epoch):
             loss = step()
             tokens += ntok
+            if ul_sum is not None:
+                ul_sum += step.last_ul
             if kd_sum is not None:
                 kd_sum += step.last_kd
             if (j + 1) % args.report_interval == 0 and rank == 0:
@@ -591,6 +630,11 @@ def main(argv=None):
                 torch.distributed.all_reduce(kd_sum)
             if rank == 0:
                 print("epoch %d mean distillation KL per token: %f" % (epoch + 1, float(kd_sum) / max(1, args.steps_per_epoch)))
+        if ul_sum is not None:
+            if world > 1:
+                torch.distributed.all_reduce(ul_sum)
+            if rank == 0:
+                print("epoch %d mean unlikelihood per token: %f" % (epoch + 1, float(ul_sum) / max(1, args.steps_per_epoch)))
         if args.model:
             model_state = model.state_dict()      # every rank: under the sharded optimiser's compute-dtype gather this gathers the fp32
             if rank == 0:                         # masters of the other ranks' shards (a collective) — rank 0 alone writes

@@ -11,6 +11,7 @@ the simpler schedule: one graph for forward+backward, the whole-buffer all-reduc
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Callable, Optional
 
@@ -88,7 +89,7 @@ class TrainStep:
     def __init__(self, model, batch, vocab: int, pad: int = 1, warmup: int = 4000, factor: float = 1.0, lam: float = 1.0,
                  smoothing: float = 0.1, grad_sync=None, use_graph: bool = True, overlap: Optional[bool] = None, opt=None,
                  dynamic_norms: bool = False, fuse_optimizer: Optional[bool] = None, teacher=None, distill_alpha: float = 0.5,
-                 distill_temperature: float = 1.0, ema_decay: float = 0.0, scst: Optional[ScstConfig] = None):
+                 distill_temperature: float = 1.0, ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, unlikelihood: float = 0.0):
         """``opt``: share an existing NoamOpt (several TrainSteps over one model, e.g. one per batch shape).
         ``dynamic_norms``: the batch tensors are refilled in place between steps, so the loss normalisers (token counts,
         train.py:35-39) are recomputed from them inside the step instead of once at construction.
@@ -118,8 +119,19 @@ class TrainStep:
         learning-rate scale is cross-entropy's; the auto-encoder streams keep the plain loss, at ``smoothing``, which the main stream
         does not use under scst (its rows are -log p(target): smoothing 0).  ``last_reward`` / ``last_baseline``:
         device scalars (float64), the step's mean reward and mean baseline.  ``load_rows(trg, trg_y, weights)``: the test entry that
-        puts fixed rows in the place of the samples."""
+        puts fixed rows in the place of the samples.
+        ``unlikelihood``: alpha of token-level unlikelihood training (Welleck et al. 2019) on the MAIN decoder stream: its loss becomes
+        label-smoothed KL + alpha * sum over each target row of -log(clamp(1 - p_c, 1e-5)) over the set of its sequence's earlier targets
+        (mtn_ulosshead_fwd / _bwd in the place of the two loss-head launches, inside the captured graph; the head is local to the rank, so
+        data parallelism needs nothing new).  0 = the plain step, launch for launch and bit for bit.  Not together with a teacher or
+        scst.  ``last_ul``: device scalar, the step's summed ul over its target-token normaliser."""
         self.model, self.batch = model, batch
+        self.unlikelihood, self.last_ul = float(unlikelihood), None
+        if not (self.unlikelihood >= 0.0 and math.isfinite(self.unlikelihood)):
+            raise ValueError("TrainStep: unlikelihood is finite and >= 0")
+        if self.unlikelihood > 0.0 and (teacher is not None or scst is not None):
+            raise ValueError("TrainStep: unlikelihood does not combine with %s" % ("a teacher (distillation)" if teacher is not None
+                                                                                   else "scst"))
         self._init_teacher(teacher, distill_alpha, distill_temperature, vocab)
         self.scst = scst
         if scst is not None:
@@ -391,6 +403,10 @@ class TrainStep:
         if self.scst is not None:
             return self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], row_weights=self._roww,
                                 smoothing=0.0)
+        if self.unlikelihood > 0.0:
+            loss = self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], unlikelihood=self.unlikelihood)
+            self.last_ul = self.lc.last_ul_sum / self._norms[0]
+            return loss
         if teacher_rows is None:
             return self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1])
         loss = self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], teacher_logp=teacher_rows,
@@ -676,12 +692,19 @@ class BucketedTrainer:
 
     def __init__(self, model, corpus, vocab_size: int, pad: int = 1, warmup: int = 4000, lam: float = 1.0, bucket: int = 8,
                  grad_sync=None, max_shapes: int = 64, teacher=None, distill_alpha: float = 0.5, distill_temperature: float = 1.0,
-                 ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, use_graph: bool = True):
+                 ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, use_graph: bool = True, unlikelihood: float = 0.0):
         """``scst``: self-critical sequence training — every padded shape keeps, next to its static source Batch, a TrainStep(scst=...)
         whose own static batch holds the drawn rows; a step refills the source in place and calls rl_step with the batch's QA ids as
         corpus items and sampling keys and the seed ``scst.seed + rl_steps`` (``rl_steps``: steps taken; set it after a resume).  With
         xe_weight the rows have max(scst.max_length, the shape's padded answer length) positions.  ``last_reward`` / ``last_baseline``:
-        the last step's device scalars.  ``use_graph`` = False: the same steps run eagerly."""
+        the last step's device scalars.  ``use_graph`` = False: the same steps run eagerly.
+        ``unlikelihood``: TrainStep's alpha for every shape; ``last_ul``: the last step's device scalar (None at 0)."""
+        self.unlikelihood, self.last_ul = float(unlikelihood), None
+        if not (self.unlikelihood >= 0.0 and math.isfinite(self.unlikelihood)):
+            raise ValueError("BucketedTrainer: unlikelihood is finite and >= 0")
+        if self.unlikelihood > 0.0 and (teacher is not None or scst is not None):
+            raise ValueError("BucketedTrainer: unlikelihood does not combine with %s" % ("a teacher (distillation)" if teacher is not None
+                                                                                         else "scst"))
         if scst is not None and (teacher is not None or grad_sync is not None):
             raise ValueError("BucketedTrainer: scst does not combine with a teacher (distillation) or with data parallelism")
         self.scst, self.use_graph, self.rl_steps = scst, use_graph, 0
@@ -725,7 +748,8 @@ class BucketedTrainer:
                 cfg = cfg.with_max_length(batch.trg.size(1))
             ts = TrainStep(self.model, batch, self.vocab, pad=self.pad, lam=self.lam, grad_sync=self.grad_sync, opt=self.opt,
                            dynamic_norms=True, teacher=self.teacher, distill_alpha=self.distill_alpha,
-                           distill_temperature=self.distill_temperature, scst=cfg, use_graph=self.use_graph)
+                           distill_temperature=self.distill_temperature, scst=cfg, use_graph=self.use_graph,
+                           unlikelihood=self.unlikelihood)
             self.steps[key] = hit = (batch, ts)
         else:
             make_batch(self.corpus, pidx, self.pad, separate_caption=True, out=hit[0], cut_a=cut_a, rng=rng)
@@ -738,6 +762,7 @@ class BucketedTrainer:
             return loss, hit[1].batch
         loss = hit[1]()
         self.last_kd = hit[1].last_kd               # (device scalar; None without a teacher)
+        self.last_ul = hit[1].last_ul               # (device scalar; None without unlikelihood)
         hit[0]._norms_global = hit[1]._norms        # [target tokens, auto-encoder tokens] the step's loss is divided by (all ranks)
         return loss, hit[0]
 
