@@ -47,7 +47,9 @@ const char* mtn_last_error(void);
  * 115: new entry point mtn_sample_rows.  116: new entry point mtn_score_rows.  117: new entry point mtn_constrain_rows.
  * 121: new entry point mtn_mbr_select.  122: new entry points mtn_eval_metrics and mtn_eval_workspace_bytes.
  * 123: new entry points mtn_distill_fwd / _bwd.  124: new entry points mtn_lerp_f32, mtn_ema_step and mtn_swap_f32.
- * 125: new entry points mtn_wlosshead_fwd / _bwd, mtn_eval_table_build, mtn_eval_score_rows, mtn_scst_assemble and mtn_scst_advantage. */
+ * 125: new entry points mtn_wlosshead_fwd / _bwd, mtn_eval_table_build, mtn_eval_score_rows, mtn_scst_assemble and mtn_scst_advantage.
+ * Entry points added since (mtn_ulosshead_fwd / _bwd; mtn_grad_sumsq_partials, mtn_grad_sumsq, mtn_clip_scale) are detected by symbol:
+ * additions only, the version stays 125. */
 int mtn_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -676,6 +678,35 @@ int mtn_adam_step_chunks(int dtype, int n_chunks, const long* off, const int* le
 int mtn_lerp_f32(long n, float* acc, const float* x, float coef, void* stream);
 int mtn_ema_step(long n, float* ema, const float* p, const float* state, float decay, float* coef_out, void* stream);
 int mtn_swap_f32(long n, float* a, float* b, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Gradient clipping by global norm (csrc/gradnorm.hip; detected by symbol, version 125): torch.nn.utils.clip_grad_norm_'s arithmetic over ONE flat fp32
+ * gradient buffer, left in device memory where mtn_adam_step reads it as grad_scale.  Stream-ordered, capturable into a hipGraph;
+ * nothing is allocated, no atomics, no host read.  Every sum is taken in an order that is a pure function of n (never of the device),
+ * so two launches over the same bytes give the same bytes.
+ *   mtn_grad_sumsq_partials(n): how many doubles mtn_grad_sumsq writes for a buffer of n floats: min(2048, ceil((n / 4) / 256)), at
+ *     least 1; 0 for n <= 0.  Host, a pure function of n.
+ *   mtn_grad_sumsq: partial[b] = the sum over workgroup b's elements of (double)g[i] * (double)g[i], accumulated in double (the product
+ *     of two floats is exact there, so magnitudes whose square leaves fp32's range, 1e-25 or 1e25, keep their norm).  Workgroup b of G =
+ *     mtn_grad_sumsq_partials(n), thread t of 256, takes the 16-byte vectors j = b * 256 + t, j + 256 G, ... below n / 4, each thread
+ *     one chain in that order (x, y, z, w inside a vector); workgroup 0's threads t < n % 4 then add tail element (n / 4) * 4 + t.  The
+ *     workgroup's total: xor butterfly over the 64 lanes (offsets 32, 16, ..., 1), then the four waves' totals in wave order.  g is
+ *     read only.
+ *   mtn_clip_scale (one workgroup): thread t sums partial[t], partial[t + 256], ... in that order, the same tree adds the threads;
+ *     norm = sqrt(sum) * |base| with base = *base_scale (1 when NULL); coef = min(1, max_norm / (norm + 1e-6)) in double
+ *     (clip_grad_norm_'s definition, its 1e-6 included); *scale_out = (float)((double)base * coef), rounded once — and the base's own
+ *     bits (1.0f without one) when coef == 1, so an unclipped step multiplies by exactly one.  max_norm = +inf measures and never
+ *     clips.  A norm that is not finite: coef and *scale_out are NaN (Adam propagates it; error_if_nonfinite=False).  *norm_out
+ *     (optional) = norm.  stats (optional device double[5]), updated by one thread with plain loads and stores (stream order keeps
+ *     calls apart): [0] += norm and [1] = max([1], norm) when the norm is finite, [2] += 1, [3] += 1 when coef < 1, [4] += 1 when the
+ *     norm is not finite.  scale_out may be base_scale itself (it is read first).
+ * MTN_ERR_ARG, nothing launched: n <= 0; a null or misaligned pointer (g at 16 bytes, doubles at 8, floats at 4; base_scale, norm_out
+ * and stats may be NULL); n_partial < 1 or above 2048; max_norm NaN or <= 0.
+ * ------------------------------------------------------------------------------------------ */
+int mtn_grad_sumsq_partials(long n);
+int mtn_grad_sumsq(long n, const float* g, double* partial, void* stream);
+int mtn_clip_scale(int n_partial, const double* partial, float max_norm, const float* base_scale, float* scale_out, double* norm_out,
+                   double* stats, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Device-side batch assembly (replaces the host padding of data_handler.py:206-274 `make_batch` and the mask passes of

@@ -105,6 +105,7 @@ class FusedAdam:
         self._aux_cache = {}                      # host-side chunk lists of the table launch's front tiles (ops.ParamGradQueue._table_aux)
         self.ema: Optional[torch.Tensor] = None   # exponential moving average of the fp32 masters (enable_ema); None = off: nothing is launched
         self.ema_decay = 0.0
+        self.clip_max_norm: Optional[float] = None   # gradient clipping by global norm (enable_clip); None = off: nothing is launched
 
     def tick(self, factor: float, model_size: int, warmup: int):
         L.check(L.load().mtn_noam_tick(self.state.data_ptr(), factor, model_size, warmup, self.betas[0], self.betas[1], L.stream_ptr()))
@@ -135,11 +136,61 @@ class FusedAdam:
             L.check(L.load().mtn_ema_step(n, self.ema.data_ptr() + 4 * off, flat.data_ptr() + 4 * off, self.state.data_ptr(), self.ema_decay,
                                           None, L.stream_ptr()))
 
+    # ---- gradient clipping by global norm: two launches ahead of the update, the coefficient stays on the device
+    def enable_clip(self, max_norm: float):
+        """Clip the gradient's global L2 norm at ``max_norm`` (> 0; inf measures the norm and never clips) as
+        torch.nn.utils.clip_grad_norm_ does: from now on step() reduces the whole flat gradient buffer to its norm (mtn_grad_sumsq),
+        turns it into scale = min(1, max_norm / (norm + 1e-6)) in device memory (mtn_clip_scale; times ``grad_scale`` if one is set,
+        and the norm is then that of the scaled gradient) and hands that scalar to mtn_adam_step as its grad_scale: no host read, so the
+        launches are captured with the step.  The reduction runs over the padding between parameters too: it is allocated as zeros and
+        nothing on the separate-optimiser path writes there (tests/test_clip_step_gpu.py).  Adam is not linear in g, so the update
+        cannot start before the whole gradient exists: can_fuse() is False while clipping is on and step_range() (the sharded
+        data-parallel update) raises.  ``clip_norm``: device double, the norm of the step just run.  No optimiser state: nothing to
+        checkpoint."""
+        max_norm = float(max_norm)
+        if not max_norm > 0.0:                     # (nan fails the comparison)
+            raise ValueError("FusedAdam.enable_clip: max_norm > 0 (inf allowed), got %r" % (max_norm,))
+        flat, _, grad = self.model.flat_buffers()
+        if self.m.numel() != flat.numel() or self.m.device != flat.device:
+            raise L.MtnHipError("model was re-flattened after the optimiser was built")
+        if getattr(self, "_sharded", None) is not None:
+            raise L.MtnHipError("gradient clipping does not combine with the sharded data-parallel optimiser")
+        self._clip_np = int(L.load().mtn_grad_sumsq_partials(grad.numel()))
+        self._clip_partial = torch.zeros(self._clip_np, device=flat.device, dtype=torch.float64)
+        self._clip_f64 = torch.zeros(6, device=flat.device, dtype=torch.float64)      # [0] the norm, [1:6] the stats block
+        self.clip_norm, self._clip_stats = self._clip_f64[0], self._clip_f64[1:]
+        self.clip_scale = torch.ones(1, device=flat.device, dtype=torch.float32)
+        self.clip_max_norm = max_norm
+        return self
+
+    def _clip(self, grad):
+        """The two clipping launches; returns the device scalar the update multiplies every gradient by."""
+        if self.clip_max_norm is None:
+            return self.grad_scale
+        if grad.numel() != self.model._flat_grad.numel() or int(L.load().mtn_grad_sumsq_partials(grad.numel())) != self._clip_np:
+            raise L.MtnHipError("model was re-flattened after clipping was enabled")
+        h, st = L.load(), L.stream_ptr()
+        L.check(h.mtn_grad_sumsq(grad.numel(), grad.data_ptr(), self._clip_partial.data_ptr(), st))
+        L.check(h.mtn_clip_scale(self._clip_np, self._clip_partial.data_ptr(), self.clip_max_norm, L.ptr(self.grad_scale),
+                                 self.clip_scale.data_ptr(), self.clip_norm.data_ptr(), self._clip_stats.data_ptr(), st))
+        return self.clip_scale
+
+    def clip_stats(self, reset: bool = False):
+        """Since the last reset: dict(mean, max: of the finite gradient norms; steps; clipped: steps whose coefficient was < 1;
+        nonfinite: steps whose norm was inf or NaN — their update wrote NaN).  One small D2H copy (it synchronises)."""
+        if self.clip_max_norm is None:
+            raise L.MtnHipError("clip_stats(): clipping is off (enable_clip)")
+        s = [float(x) for x in self._clip_stats.cpu()]
+        if reset:
+            self._clip_stats.zero_()
+        fin = s[2] - s[4]
+        return {"mean": s[0] / fin if fin > 0 else 0.0, "max": s[1], "steps": int(s[2]), "clipped": int(s[3]), "nonfinite": int(s[4])}
+
     def step(self):
         flat, flat_lp, grad, lp_ptr = self._buffers()
         L.check(L.load().mtn_adam_step(L.dtype_code(self.model.compute_dtype), flat.numel(), flat.data_ptr(), grad.data_ptr(),
                                        self.m.data_ptr(), self.v.data_ptr(), lp_ptr, self.state.data_ptr(),
-                                       L.ptr(self.grad_scale), self.betas[0], self.betas[1], self.eps, L.stream_ptr()))
+                                       L.ptr(self._clip(grad)), self.betas[0], self.betas[1], self.eps, L.stream_ptr()))
         self._ema_update(flat, 0, flat.numel())
         self.model.refresh_transposed()
 
@@ -148,6 +199,9 @@ class FusedAdam:
         dp.ShardedOptimizerSync).  write_lp = False: the compute-dtype copies are NOT written — the caller refreshes them once all
         shards of all ranks have arrived (refresh_copies); True: the shard's compute-dtype copy is written by the same pass (the
         compute-dtype gather: the other ranks receive THAT, not the fp32 master)."""
+        if self.clip_max_norm is not None:
+            raise L.MtnHipError("FusedAdam.step_range: gradient clipping needs the whole reduced gradient before any element is updated; "
+                                "the sharded data-parallel optimiser updates shard by shard (use the all-reduce scheme)")
         flat, flat_lp, grad, lp_ptr = self._buffers()
         assert off % 4 == 0 and n > 0
         lp = None
@@ -176,6 +230,8 @@ class FusedAdam:
     # ---- optimiser epilogue: the update of the sublayer weight matrices rides on their parameter-gradient GEMMs
     def can_fuse(self) -> bool:
         m = self.model
+        if self.clip_max_norm is not None:        # the epilogue updates a weight before the rest of the gradient exists
+            return False
         m.prepare()
         ok = bool(getattr(m, "_fusable", None)) and m._flat.is_cuda and os.environ.get("MTN_NO_FUSED_ADAM") is None
         if ok:      # build the two expected "rest" tables now: they are device tensors and the step may be under graph capture later
@@ -190,6 +246,8 @@ class FusedAdam:
         mtn_adam_fuse) — no gradient round trip through HBM, no separate transpose pass.  The schedule must already have
         been advanced (tick) and ``step_rest()`` must follow the backward pass.  Single-rank only: with data parallelism
         the gradients are exchanged between backward and the update."""
+        if self.clip_max_norm is not None:
+            raise L.MtnHipError("FusedAdam.fuse_into_backward: gradient clipping needs the separate optimiser pass (can_fuse() is False)")
         flat, flat_lp, grad, lp_ptr = self._buffers()
         m = self.model
         esz = flat_lp.element_size()

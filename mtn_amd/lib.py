@@ -333,6 +333,9 @@ SYMBOLS = {
     "mtn_lerp_f32": (C.c_int, [C.c_long, _P, _P, C.c_float, _P]),
     "mtn_ema_step": (C.c_int, [C.c_long, _P, _P, _P, C.c_float, _P, _P]),
     "mtn_swap_f32": (C.c_int, [C.c_long, _P, _P, _P]),
+    "mtn_grad_sumsq_partials": (C.c_int, [C.c_long]),
+    "mtn_grad_sumsq": (C.c_int, [C.c_long, _P, _P, _P]),
+    "mtn_clip_scale": (C.c_int, [C.c_int, _P, C.c_float, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -113,8 +113,13 @@ def parse(argv=None):
     p.add_argument("--unlikelihood-alpha", default=0.0, type=float, metavar="A",
                    help="> 0: the response stream's loss gains A * sum over each target position of -log(1 - p(c)) over the response's "
                         "earlier tokens c (Welleck et al. 2019); validation stays the plain loss (0: off)")
+    # gradient clipping by global norm, as torch.nn.utils.clip_grad_norm_: the cap every Transformer recipe carries next to Adam
+    p.add_argument("--clip-grad-norm", default=0.0, type=float, metavar="C",
+                   help="C > 0: every step's gradient is multiplied by min(1, C / (its global L2 norm + 1e-6)) on the device before Adam "
+                        "reads it (inf: measure the norm, never clip); the step then takes the separate optimiser pass; every epoch logs "
+                        "the mean and largest norm and how many steps were clipped (0: off)")
     args = p.parse_args(argv)
-    err = distill_flag_error(args) or ema_flag_error(args) or scst_flag_error(args) or unlikelihood_flag_error(args)
+    err = distill_flag_error(args) or ema_flag_error(args) or scst_flag_error(args) or unlikelihood_flag_error(args) or clip_flag_error(args)
     if err:
         p.error(err)
     return args
@@ -195,6 +200,34 @@ def unlikelihood_flag_error(args):
     if a > 0.0 and args.scst_samples:
         return "--unlikelihood-alpha does not combine with --scst-samples: unlikelihood under self-critical training is out of scope"
     return None
+
+
+def clip_flag_error(args, world=None):
+    """What is wrong with --clip-grad-norm, or what it conflicts with, as one line (None: nothing).  0 = off; inf is allowed.  ``world``:
+    the number of ranks (None: what the launcher's WORLD_SIZE says)."""
+    import os
+    c = args.clip_grad_norm
+    if not c >= 0.0:                               # (nan fails the comparison)
+        return "--clip-grad-norm must be 0 (off) or > 0, inf allowed (got %r)" % c
+    if c == 0.0:
+        return None
+    if world is None:
+        world = int(os.environ.get("WORLD_SIZE", "1") or 1)
+    if world > 1 and os.environ.get("MTN_DP_SHARDED", "0") != "0":
+        return ("--clip-grad-norm does not combine with the sharded data-parallel optimiser (MTN_DP_SHARDED=%s): clipping under it is out "
+                "of scope; leave MTN_DP_SHARDED unset or 0" % os.environ["MTN_DP_SHARDED"])
+    return None
+
+
+def clip_epoch_report(adam, epoch, rank):
+    """The epoch's gradient-norm line from the optimiser's stats block (one small D2H copy; the block is reset).  A step whose norm
+    was not finite wrote NaN into the weights: the run ends here, before anything of this epoch is saved."""
+    st = adam.clip_stats(reset=True)
+    if rank == 0:
+        print("epoch %d gradient norm: mean %f max %f clipped %d of %d steps" % (epoch + 1, st["mean"], st["max"], st["clipped"], st["steps"]))
+    if st["nonfinite"] > 0:
+        raise SystemExit("mtn_amd.train: epoch %d: the gradient norm was not finite in %d of %d steps; the weights are NaN, no checkpoint "
+                         "of this epoch is written" % (epoch + 1, st["nonfinite"], st["steps"]))
 
 
 def ema_flag_error(args):
@@ -432,7 +465,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(asctime)s %(levelname)s: %(message)s")
     cut_a = cut_a_applies(args)
     rank, world, local = dp.init_distributed()
-    err = scst_flag_error(args, world)
+    err = scst_flag_error(args, world) or clip_flag_error(args, world)
     if err:
         raise SystemExit("mtn_amd.train: " + err)
     local = local % torch.cuda.device_count()      # (several ranks may share a GPU in a gloo dry run)
@@ -517,13 +550,16 @@ def main(argv=None):
             opt = NoamOpt(args.d_model, 1, args.warmup_steps, FusedAdam(model))
             if args.ema_decay:
                 opt.optimizer.enable_ema(args.ema_decay)
+            if args.clip_grad_norm:
+                opt.optimizer.enable_clip(args.clip_grad_norm)
             lc = SimpleLossCompute(model.generator, model.auto_encoder_generator, LabelSmoothing(args.vocab_size, 1, 0.1), opt=opt,
                                    l=args.loss_l, grad_sync=sync)
         else:
             from .train_step import BucketedTrainer
             trainer = BucketedTrainer(model, corpus, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l,
                                       bucket=args.bucket, grad_sync=sync, ema_decay=args.ema_decay, scst=scst,
-                                      use_graph=not (args.eager and scst is not None), unlikelihood=args.unlikelihood_alpha, **distill)
+                                      use_graph=not (args.eager and scst is not None), unlikelihood=args.unlikelihood_alpha,
+                                      clip_grad_norm=args.clip_grad_norm, **distill)
         valid = None
         if args.valid_videos > 0 or valid_data is not None:
             vdata = valid_data if valid_data is not None else synthetic_corpus(args.valid_videos, args.vocab_size, args.ft_sizes, args.rand_seed + 1000)
@@ -559,6 +595,8 @@ def main(argv=None):
                     print("epoch %d mean unlikelihood per token: %f" % (epoch + 1, stats["ul"]))
                 if "reward" in stats:
                     print("epoch %d mean reward: %f mean baseline: %f" % (epoch + 1, stats["reward"], stats["baseline"]))
+            if args.clip_grad_norm:
+                clip_epoch_report(the_opt.optimizer, epoch, rank)
             if args.model:
                 # EVERY rank builds the optimiser state: with the sharded optimiser (dp.ShardedOptimizerSync) a rank holds the
                 # Adam moments of its shards only (and, with the compute-dtype gather, the current fp32 masters of its shards
@@ -607,7 +645,7 @@ def main(argv=None):
     Q, H, C, T, V = args.lens
     batch = synthetic_batch(args.vocab_size, args.batch_size, Q, H, C, T, [V] * len(args.ft_sizes), args.ft_sizes, device=dev, seed=1 + rank)
     step = TrainStep(model, batch, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l, grad_sync=sync, ema_decay=args.ema_decay,
-                     unlikelihood=args.unlikelihood_alpha, **distill)
+                     unlikelihood=args.unlikelihood_alpha, clip_grad_norm=args.clip_grad_norm, **distill)
     ntok = int(batch.ntokens) * world
     for epoch in range(args.num_epochs):
         t0, tokens = time.time(), 0
@@ -635,6 +673,8 @@ def main(argv=None):
                 torch.distributed.all_reduce(ul_sum)
             if rank == 0:
                 print("epoch %d mean unlikelihood per token: %f" % (epoch + 1, float(ul_sum) / max(1, args.steps_per_epoch)))
+        if args.clip_grad_norm:
+            clip_epoch_report(step.opt.optimizer, epoch, rank)
         if args.model:
             model_state = model.state_dict()      # every rank: under the sharded optimiser's compute-dtype gather this gathers the fp32
             if rank == 0:                         # masters of the other ranks' shards (a collective) — rank 0 alone writes

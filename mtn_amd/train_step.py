@@ -89,7 +89,8 @@ class TrainStep:
     def __init__(self, model, batch, vocab: int, pad: int = 1, warmup: int = 4000, factor: float = 1.0, lam: float = 1.0,
                  smoothing: float = 0.1, grad_sync=None, use_graph: bool = True, overlap: Optional[bool] = None, opt=None,
                  dynamic_norms: bool = False, fuse_optimizer: Optional[bool] = None, teacher=None, distill_alpha: float = 0.5,
-                 distill_temperature: float = 1.0, ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, unlikelihood: float = 0.0):
+                 distill_temperature: float = 1.0, ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, unlikelihood: float = 0.0,
+                 clip_grad_norm: float = 0.0):
         """``opt``: share an existing NoamOpt (several TrainSteps over one model, e.g. one per batch shape).
         ``dynamic_norms``: the batch tensors are refilled in place between steps, so the loss normalisers (token counts,
         train.py:35-39) are recomputed from them inside the step instead of once at construction.
@@ -124,8 +125,21 @@ class TrainStep:
         label-smoothed KL + alpha * sum over each target row of -log(clamp(1 - p_c, 1e-5)) over the set of its sequence's earlier targets
         (mtn_ulosshead_fwd / _bwd in the place of the two loss-head launches, inside the captured graph; the head is local to the rank, so
         data parallelism needs nothing new).  0 = the plain step, launch for launch and bit for bit.  Not together with a teacher or
-        scst.  ``last_ul``: device scalar, the step's summed ul over its target-token normaliser."""
+        scst.  ``last_ul``: device scalar, the step's summed ul over its target-token normaliser.
+        ``clip_grad_norm``: C > 0 (inf allowed: measure, never clip) = the optimiser built here clips the gradient's global L2 norm at C
+        as torch.nn.utils.clip_grad_norm_ does (FusedAdam.enable_clip: mtn_grad_sumsq + mtn_clip_scale ahead of mtn_adam_step, the
+        coefficient never leaves the device); a shared ``opt`` keeps whatever its owner enabled.  0 = off: the step is what it is
+        without the keyword, launch for launch.  Adam is not linear in g, so a clipped step takes the separate-optimiser path
+        (``fuse_optimizer`` = False) in every schedule — eager, the one-graph capture, rl_step under scst — and pays for the gradient's
+        HBM round trip.  Data parallelism uses the all-reduce scheme with clipping on (the layer-segmented overlap stays): after the
+        exchange every rank holds the whole reduced gradient and computes the same norm bits with no further collective.  Clipping
+        under the SHARDED optimiser is out of scope (every slice would have to be reduced before any shard is updated, which undoes
+        that schedule's point): asking for it explicitly (MTN_DP_SHARDED=1) raises.  ``last_grad_norm``: device double, the norm of
+        the step just run (None when clipping is off)."""
         self.model, self.batch = model, batch
+        clip_grad_norm = float(clip_grad_norm)
+        if not clip_grad_norm >= 0.0:              # (nan fails the comparison)
+            raise ValueError("TrainStep: clip_grad_norm is 0 (off) or > 0 (inf allowed)")
         self.unlikelihood, self.last_ul = float(unlikelihood), None
         if not (self.unlikelihood >= 0.0 and math.isfinite(self.unlikelihood)):
             raise ValueError("TrainStep: unlikelihood is finite and >= 0")
@@ -143,7 +157,10 @@ class TrainStep:
             opt = NoamOpt(model.decoder.layers[0].size, factor, warmup, FusedAdam(model))
             if ema_decay:
                 opt.optimizer.enable_ema(ema_decay)
+            if clip_grad_norm:
+                opt.optimizer.enable_clip(clip_grad_norm)
         self.opt = opt
+        self.clipping = getattr(opt.optimizer, "clip_max_norm", None) is not None
         self.dynamic_norms = dynamic_norms
         self.crit = LabelSmoothing(vocab, pad, smoothing)
         self.lc = SimpleLossCompute(model.generator, model.auto_encoder_generator, self.crit, opt=None, l=lam, sync=False)
@@ -158,7 +175,11 @@ class TrainStep:
         # data parallel: reduce-scatter + optimiser on this rank's shard + all-gather of the master weights
         # (dp.ShardedOptimizerSync) instead of all-reduce + the full optimiser pass on every rank; MTN_DP_SHARDED=0 = the latter
         self.sharded = None
-        if grad_sync is not None and os.environ.get("MTN_DP_SHARDED", "1") != "0" and hasattr(self.opt.optimizer, "step_range"):
+        if self.clipping and grad_sync is not None and os.environ.get("MTN_DP_SHARDED", "0") != "0":
+            raise ValueError("TrainStep: gradient clipping does not combine with the sharded data-parallel optimiser (MTN_DP_SHARDED): "
+                             "the norm needs every slice reduced before any shard is updated; leave MTN_DP_SHARDED unset or 0")
+        if (grad_sync is not None and not self.clipping and os.environ.get("MTN_DP_SHARDED", "1") != "0"
+                and hasattr(self.opt.optimizer, "step_range")):
             from .dp import ShardedOptimizerSync
             if getattr(grad_sync, "compress", False):
                 raise ValueError("bf16 gradient compression applies to the all-reduce scheme only (MTN_DP_SHARDED=0): the sharded "
@@ -185,6 +206,10 @@ class TrainStep:
         self._norms = torch.stack([batch.ntokens, (ae_y != pad).sum()]).float()
         if grad_sync is not None:
             grad_sync.all_reduce_scalars(self._norms)
+
+    @property
+    def last_grad_norm(self):
+        return self.opt.optimizer.clip_norm if self.clipping else None
 
     # ---- pieces
     def local_norms(self):
@@ -692,13 +717,15 @@ class BucketedTrainer:
 
     def __init__(self, model, corpus, vocab_size: int, pad: int = 1, warmup: int = 4000, lam: float = 1.0, bucket: int = 8,
                  grad_sync=None, max_shapes: int = 64, teacher=None, distill_alpha: float = 0.5, distill_temperature: float = 1.0,
-                 ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, use_graph: bool = True, unlikelihood: float = 0.0):
+                 ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, use_graph: bool = True, unlikelihood: float = 0.0,
+                 clip_grad_norm: float = 0.0):
         """``scst``: self-critical sequence training — every padded shape keeps, next to its static source Batch, a TrainStep(scst=...)
         whose own static batch holds the drawn rows; a step refills the source in place and calls rl_step with the batch's QA ids as
         corpus items and sampling keys and the seed ``scst.seed + rl_steps`` (``rl_steps``: steps taken; set it after a resume).  With
         xe_weight the rows have max(scst.max_length, the shape's padded answer length) positions.  ``last_reward`` / ``last_baseline``:
         the last step's device scalars.  ``use_graph`` = False: the same steps run eagerly.
-        ``unlikelihood``: TrainStep's alpha for every shape; ``last_ul``: the last step's device scalar (None at 0)."""
+        ``unlikelihood``: TrainStep's alpha for every shape; ``last_ul``: the last step's device scalar (None at 0).
+        ``clip_grad_norm``: > 0 = the one optimiser all shapes share clips the gradient's global norm (FusedAdam.enable_clip)."""
         self.unlikelihood, self.last_ul = float(unlikelihood), None
         if not (self.unlikelihood >= 0.0 and math.isfinite(self.unlikelihood)):
             raise ValueError("BucketedTrainer: unlikelihood is finite and >= 0")
@@ -715,6 +742,8 @@ class BucketedTrainer:
         self.opt = NoamOpt(model.decoder.layers[0].size, 1.0, warmup, FusedAdam(model))
         if ema_decay:
             self.opt.optimizer.enable_ema(ema_decay)
+        if clip_grad_norm:
+            self.opt.optimizer.enable_clip(clip_grad_norm)
         self.steps = {}
         self.last_kd = None
 
