@@ -48,8 +48,8 @@ const char* mtn_last_error(void);
  * 121: new entry point mtn_mbr_select.  122: new entry points mtn_eval_metrics and mtn_eval_workspace_bytes.
  * 123: new entry points mtn_distill_fwd / _bwd.  124: new entry points mtn_lerp_f32, mtn_ema_step and mtn_swap_f32.
  * 125: new entry points mtn_wlosshead_fwd / _bwd, mtn_eval_table_build, mtn_eval_score_rows, mtn_scst_assemble and mtn_scst_advantage.
- * Entry points added since (mtn_ulosshead_fwd / _bwd; mtn_grad_sumsq_partials, mtn_grad_sumsq, mtn_clip_scale) are detected by symbol:
- * additions only, the version stays 125. */
+ * Entry points added since (mtn_ulosshead_fwd / _bwd; mtn_grad_sumsq_partials, mtn_grad_sumsq, mtn_clip_scale; mtn_grad_accum) are
+ * detected by symbol: additions only, the version stays 125. */
 int mtn_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -707,6 +707,36 @@ int mtn_grad_sumsq_partials(long n);
 int mtn_grad_sumsq(long n, const float* g, double* partial, void* stream);
 int mtn_clip_scale(int n_partial, const double* partial, float max_norm, const float* base_scale, float* scale_out, double* norm_out,
                    double* stats, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Gradient accumulation over a window of K micro-batches (csrc/gradaccum.hip; detected by symbol, version 125).  Micro-step k leaves
+ * its gradient g_k in the flat fp32 gradient buffer, normalised by its own token counts, and w_k is its target-token count over all
+ * ranks (a device float).  The window's gradient is
+ *     G = (sum_k w_k g_k) / (sum_k w_k),
+ * the gradient of the token-weighted mean of the micro-steps' losses.  For the main decoder stream that is the gradient of the step on
+ * the concatenated batch; for the auto-encoder streams it is that gradient when the micro-batches share their query-to-target token
+ * ratio — otherwise a micro-batch's auto-encoder term carries the weight w_k / sum w and not its share of the query tokens.
+ * One pass over n floats per micro-step: 16-byte accesses, mtn_grad_sumsq's grid (mtn_grad_sumsq_partials(n) workgroups of 256, a pure
+ * function of n), workgroup 0's threads t < n % 4 take the tail.  Stream-ordered, capturable, nothing allocated, no atomics, no host
+ * read.  Every operation below is ONE separately rounded fp32 operation, never an fma: numpy float32 reproduces the bytes.  w = *w.
+ *   MTN_ACCUM_FIRST: acc[i] = w * g[i];                       *total_out = w;              total_in is ignored.
+ *   MTN_ACCUM_ADD:   acc[i] = acc[i] + w * g[i];              *total_out = *total_in + w.  (a multiply, then an add)
+ *   MTN_ACCUM_LAST:  t = *total_in + w;  inv = (float)(1.0 / (double)t), computed by every thread;
+ *                    g[i] = (acc[i] + w * g[i]) * inv;        *total_out = t.               acc is read only.
+ *     With partial non-NULL the launch also writes, from the g it has just written, the mtn_grad_sumsq_partials(n) doubles
+ *     mtn_grad_sumsq would: each thread's chain in that kernel's order, the same workgroup tree, the same bytes.
+ * g is written in LAST only.  One thread of workgroup 0 stores *total_out with a plain store while every thread reads *total_in: they
+ * are different floats (the caller alternates two slots).  The caller guarantees t > 0: a zero total gives inf / NaN as the arithmetic
+ * says; nothing is checked on the device.
+ * MTN_ERR_ARG, nothing launched: another mode; n < 0; acc or g null or not 16-byte aligned; acc == g; w or total_out null; w, total_in
+ * or total_out not 4-byte aligned; total_in null outside FIRST; total_out == total_in or == w; partial not 8-byte aligned, or non-NULL
+ * outside LAST.  n == 0 returns MTN_OK with nothing launched.
+ * ------------------------------------------------------------------------------------------ */
+#define MTN_ACCUM_FIRST 0
+#define MTN_ACCUM_ADD 1
+#define MTN_ACCUM_LAST 2
+int mtn_grad_accum(int mode, long n, float* acc, float* g, const float* w, const float* total_in, float* total_out, double* partial,
+                   void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Device-side batch assembly (replaces the host padding of data_handler.py:206-274 `make_batch` and the mask passes of

@@ -5,38 +5,7 @@
 // launches over the same bytes give the same bytes, on any device.
 #include <math.h>
 
-#include "common.h"
-
-#define GN_THREADS 256
-#define GN_MAX_PARTIALS 2048  // 256 CUs x 8 blocks, as average.hip's avg_grid_for
-
-static inline int gn_grid_for(long n) {
-    long b = ((n >> 2) + GN_THREADS - 1) / GN_THREADS;
-    if (b > GN_MAX_PARTIALS) b = GN_MAX_PARTIALS;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-__device__ __forceinline__ double gn_sq(double acc, float x) {
-    const double d = (double)x;  // the product of two floats is exact in double: acc + d * d is rounded once, fused or not
-    return acc + d * d;
-}
-
-// The workgroup's total in thread 0, in a fixed order: xor butterfly inside each wave (every lane adds the same pairs), then the
-// waves' totals from LDS, wave 0 first.
-__device__ __forceinline__ double gn_block_sum(double v, double* lds) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0) {
-        t = lds[0];
-#pragma unroll
-        for (int w = 1; w < GN_THREADS / 64; ++w) t += lds[w];
-    }
-    return t;
-}
+#include "gradnorm_common.h"  // the grid, the chain step and the reduction tree, shared with gradaccum.hip
 
 __global__ __launch_bounds__(GN_THREADS) void grad_sumsq_kernel(long n, const float* __restrict__ g, double* __restrict__ partial) {
     __shared__ double lds[GN_THREADS / 64];
@@ -75,8 +44,6 @@ __global__ __launch_bounds__(GN_THREADS) void clip_scale_kernel(int n_partial, c
         if (!finite) stats[4] += 1.0;
     }
 }
-
-static inline bool gn_aligned(const void* p, uintptr_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
 
 extern "C" int mtn_grad_sumsq_partials(long n) { return n <= 0 ? 0 : gn_grid_for(n); }
 

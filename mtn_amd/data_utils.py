@@ -106,6 +106,7 @@ class FusedAdam:
         self.ema: Optional[torch.Tensor] = None   # exponential moving average of the fp32 masters (enable_ema); None = off: nothing is launched
         self.ema_decay = 0.0
         self.clip_max_norm: Optional[float] = None   # gradient clipping by global norm (enable_clip); None = off: nothing is launched
+        self.accum: Optional[torch.Tensor] = None    # gradient accumulation over a window of micro-batches (enable_accumulation); None = off
 
     def tick(self, factor: float, model_size: int, warmup: int):
         L.check(L.load().mtn_noam_tick(self.state.data_ptr(), factor, model_size, warmup, self.betas[0], self.betas[1], L.stream_ptr()))
@@ -170,7 +171,10 @@ class FusedAdam:
         if grad.numel() != self.model._flat_grad.numel() or int(L.load().mtn_grad_sumsq_partials(grad.numel())) != self._clip_np:
             raise L.MtnHipError("model was re-flattened after clipping was enabled")
         h, st = L.load(), L.stream_ptr()
-        L.check(h.mtn_grad_sumsq(grad.numel(), grad.data_ptr(), self._clip_partial.data_ptr(), st))
+        if getattr(self, "_accum_sumsq", False):   # the launch that closed the accumulation window wrote these partials (accumulate)
+            self._accum_sumsq = False
+        else:
+            L.check(h.mtn_grad_sumsq(grad.numel(), grad.data_ptr(), self._clip_partial.data_ptr(), st))
         L.check(h.mtn_clip_scale(self._clip_np, self._clip_partial.data_ptr(), self.clip_max_norm, L.ptr(self.grad_scale),
                                  self.clip_scale.data_ptr(), self.clip_norm.data_ptr(), self._clip_stats.data_ptr(), st))
         return self.clip_scale
@@ -186,6 +190,61 @@ class FusedAdam:
         fin = s[2] - s[4]
         return {"mean": s[0] / fin if fin > 0 else 0.0, "max": s[1], "steps": int(s[2]), "clipped": int(s[3]), "nonfinite": int(s[4])}
 
+    # ---- gradient accumulation: one launch per micro-step over a second flat fp32 buffer, the window's gradient lands in the gradient buffer
+    def enable_accumulation(self):
+        """Accumulate the gradient over a window of micro-batches before every update: ``accum`` (zeros like the flat gradient buffer)
+        collects w_k * g_k and the launch that closes the window writes G = (sum_k w_k g_k) / (sum_k w_k) over the gradient buffer in
+        place (include/mtn_hip.h mtn_grad_accum states the arithmetic), where the exchange, clipping and the update already read it.
+        ``accumulate(w, last)`` is one micro-step's launch; the caller runs tick / step once per window, so the step count counts
+        windows.  The sublayer gradients are overwritten by every backward pass, so the optimiser epilogue of the dW GEMMs would update
+        a weight before the window's gradient exists: can_fuse() is False while accumulation is on, fuse_into_backward() and
+        step_range() (the sharded data-parallel update) raise.  Windows never span an epoch: no optimiser state, nothing to checkpoint."""
+        flat, _, grad = self.model.flat_buffers()
+        if self.m.numel() != flat.numel() or self.m.device != flat.device:
+            raise L.MtnHipError("model was re-flattened after the optimiser was built")
+        if getattr(self, "_sharded", None) is not None:
+            raise L.MtnHipError("gradient accumulation does not combine with the sharded data-parallel optimiser")
+        self.accum = torch.zeros_like(grad)
+        self._accum_total = torch.zeros(2, device=grad.device, dtype=torch.float32)    # the two slots the launches alternate between
+        self._accum_k = 0                          # micro-steps of the open window already accumulated (host side)
+        self._accum_sumsq = False                  # the closing launch wrote clipping's partials: _clip skips its mtn_grad_sumsq once
+        self.accum_windows = self.accum_micro = 0  # windows closed / micro-steps seen so far (host side)
+        return self
+
+    def accumulate(self, w, last: bool, sumsq: bool = True) -> bool:
+        """One micro-step of the open window: its gradient is in the flat gradient buffer, ``w`` is its weight (a device float: the
+        micro-step's target-token count over all ranks).  The window's first micro-step is MTN_ACCUM_FIRST, the one that closes it
+        (``last``) MTN_ACCUM_LAST, the others MTN_ACCUM_ADD; a window of one launches nothing.  With clipping on and ``sumsq``, the
+        closing launch writes the partials of the window gradient's sum of squares, and the update that follows skips its
+        mtn_grad_sumsq launch; pass ``sumsq`` = False when a gradient exchange comes between (the norm is the reduced gradient's).
+        Stream-ordered, no host read.  Returns ``last``."""
+        if self.accum is None:
+            raise L.MtnHipError("accumulate(): accumulation is off (enable_accumulation)")
+        grad = self.model.flat_buffers()[2]
+        if grad.numel() != self.accum.numel() or grad.device != self.accum.device:
+            raise L.MtnHipError("model was re-flattened after accumulation was enabled")
+        if not (torch.is_tensor(w) and w.dtype == torch.float32 and w.device == grad.device and w.numel() == 1):
+            raise ValueError("accumulate(): w is one float32 on the gradient's device")
+        k, last = self._accum_k, bool(last)
+        self._accum_sumsq = False
+        self.accum_micro += 1
+        self._accum_k = 0 if last else k + 1
+        self.accum_windows += int(last)
+        if last and k == 0:                        # a window of one: the gradient buffer is the window's gradient already
+            return last
+        h = L.load()
+        partial = None
+        if last and sumsq and self.clip_max_norm is not None:
+            if int(h.mtn_grad_sumsq_partials(grad.numel())) != self._clip_np:
+                raise L.MtnHipError("model was re-flattened after clipping was enabled")
+            partial, self._accum_sumsq = self._clip_partial, True
+        mode = L.MTN_ACCUM_FIRST if k == 0 else (L.MTN_ACCUM_LAST if last else L.MTN_ACCUM_ADD)
+        tot = self._accum_total
+        L.check(h.mtn_grad_accum(mode, grad.numel(), self.accum.data_ptr(), grad.data_ptr(), w.data_ptr(),
+                                 None if k == 0 else tot.data_ptr() + 4 * ((k - 1) & 1), tot.data_ptr() + 4 * (k & 1), L.ptr(partial),
+                                 L.stream_ptr()))
+        return last
+
     def step(self):
         flat, flat_lp, grad, lp_ptr = self._buffers()
         L.check(L.load().mtn_adam_step(L.dtype_code(self.model.compute_dtype), flat.numel(), flat.data_ptr(), grad.data_ptr(),
@@ -199,6 +258,9 @@ class FusedAdam:
         dp.ShardedOptimizerSync).  write_lp = False: the compute-dtype copies are NOT written — the caller refreshes them once all
         shards of all ranks have arrived (refresh_copies); True: the shard's compute-dtype copy is written by the same pass (the
         compute-dtype gather: the other ranks receive THAT, not the fp32 master)."""
+        if self.accum is not None:
+            raise L.MtnHipError("FusedAdam.step_range: gradient accumulation updates once per window, from the whole window gradient; "
+                                "the sharded data-parallel optimiser updates shard by shard (use the all-reduce scheme)")
         if self.clip_max_norm is not None:
             raise L.MtnHipError("FusedAdam.step_range: gradient clipping needs the whole reduced gradient before any element is updated; "
                                 "the sharded data-parallel optimiser updates shard by shard (use the all-reduce scheme)")
@@ -232,6 +294,8 @@ class FusedAdam:
         m = self.model
         if self.clip_max_norm is not None:        # the epilogue updates a weight before the rest of the gradient exists
             return False
+        if self.accum is not None:                # ... or, under accumulation, before the window's gradient exists
+            return False
         m.prepare()
         ok = bool(getattr(m, "_fusable", None)) and m._flat.is_cuda and os.environ.get("MTN_NO_FUSED_ADAM") is None
         if ok:      # build the two expected "rest" tables now: they are device tensors and the step may be under graph capture later
@@ -246,6 +310,8 @@ class FusedAdam:
         mtn_adam_fuse) — no gradient round trip through HBM, no separate transpose pass.  The schedule must already have
         been advanced (tick) and ``step_rest()`` must follow the backward pass.  Single-rank only: with data parallelism
         the gradients are exchanged between backward and the update."""
+        if self.accum is not None:
+            raise L.MtnHipError("FusedAdam.fuse_into_backward: gradient accumulation needs the separate optimiser pass (can_fuse() is False)")
         if self.clip_max_norm is not None:
             raise L.MtnHipError("FusedAdam.fuse_into_backward: gradient clipping needs the separate optimiser pass (can_fuse() is False)")
         flat, flat_lp, grad, lp_ptr = self._buffers()

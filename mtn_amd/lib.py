@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmtn_hip.so")
 
 MTN_F32, MTN_BF16 = 0, 1
+MTN_ACCUM_FIRST, MTN_ACCUM_ADD, MTN_ACCUM_LAST = 0, 1, 2      # mtn_grad_accum's modes (include/mtn_hip.h)
 
 
 class Dropout(C.Structure):
@@ -336,6 +337,7 @@ SYMBOLS = {
     "mtn_grad_sumsq_partials": (C.c_int, [C.c_long]),
     "mtn_grad_sumsq": (C.c_int, [C.c_long, _P, _P, _P]),
     "mtn_clip_scale": (C.c_int, [C.c_int, _P, C.c_float, _P, _P, _P, _P, _P]),
+    "mtn_grad_accum": (C.c_int, [C.c_int, C.c_long, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

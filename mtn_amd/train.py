@@ -118,8 +118,14 @@ def parse(argv=None):
                    help="C > 0: every step's gradient is multiplied by min(1, C / (its global L2 norm + 1e-6)) on the device before Adam "
                         "reads it (inf: measure the norm, never clip); the step then takes the separate optimiser pass; every epoch logs "
                         "the mean and largest norm and how many steps were clipped (0: off)")
+    # gradient accumulation: an effective batch of K assembled batches per optimiser update, without holding one padded batch of that size
+    p.add_argument("--accum-steps", default=1, type=int, metavar="K",
+                   help="K > 1: the optimiser updates once per window of K consecutive batches, from the token-weighted mean of their "
+                        "gradients, accumulated on the device (an epoch's last window may be shorter); under several ranks the gradient "
+                        "exchange runs once per window; every epoch logs its updates (1: off)")
     args = p.parse_args(argv)
-    err = distill_flag_error(args) or ema_flag_error(args) or scst_flag_error(args) or unlikelihood_flag_error(args) or clip_flag_error(args)
+    err = (distill_flag_error(args) or ema_flag_error(args) or scst_flag_error(args) or unlikelihood_flag_error(args) or clip_flag_error(args)
+           or accum_flag_error(args))
     if err:
         p.error(err)
     return args
@@ -215,6 +221,26 @@ def clip_flag_error(args, world=None):
         world = int(os.environ.get("WORLD_SIZE", "1") or 1)
     if world > 1 and os.environ.get("MTN_DP_SHARDED", "0") != "0":
         return ("--clip-grad-norm does not combine with the sharded data-parallel optimiser (MTN_DP_SHARDED=%s): clipping under it is out "
+                "of scope; leave MTN_DP_SHARDED unset or 0" % os.environ["MTN_DP_SHARDED"])
+    return None
+
+
+def accum_flag_error(args, world=None):
+    """What is wrong with --accum-steps, or what it conflicts with, as one line (None: nothing).  1 = off.  ``world``: the number of ranks
+    (None: what the launcher's WORLD_SIZE says)."""
+    import os
+    k = args.accum_steps
+    if k < 1:
+        return "--accum-steps must be an integer >= 1 (got %r)" % k
+    if k == 1:
+        return None
+    if args.scst_samples:
+        return ("--accum-steps does not combine with --scst-samples: accumulation under self-critical training is out of scope "
+                "(a self-critical step is one update per call)")
+    if world is None:
+        world = int(os.environ.get("WORLD_SIZE", "1") or 1)
+    if world > 1 and os.environ.get("MTN_DP_SHARDED", "0") != "0":
+        return ("--accum-steps does not combine with the sharded data-parallel optimiser (MTN_DP_SHARDED=%s): accumulation under it is out "
                 "of scope; leave MTN_DP_SHARDED unset or 0" % os.environ["MTN_DP_SHARDED"])
     return None
 
@@ -348,8 +374,12 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
     ul_sum = torch.zeros((), device=dev) if getattr(trainer, "unlikelihood", 0.0) > 0.0 else None
     tok_sum = torch.zeros((), device=dev, dtype=torch.int64)
     t0, tok0 = time.time(), 0
+    accum = getattr(trainer, "accum_steps", 1) > 1
     for j, k in enumerate(order):
-        loss, b = trainer.step(indices[k], cut_a=cut is not None, rng=cut)
+        if accum:           # the trainer closes a window at every accum_steps-th batch; the epoch's last batch closes a short one
+            loss, b = trainer.step(indices[k], cut_a=cut is not None, rng=cut, last=True if j == len(order) - 1 else None)
+        else:
+            loss, b = trainer.step(indices[k], cut_a=cut is not None, rng=cut)
         # the step's loss is already divided by the token count of the step over ALL ranks (train.py:36; dp.py): weight it
         # with that same count; the ranks' sums add up to the epoch mean of the global batches
         n_glob = b._norms_global[0].to(torch.int64)
@@ -465,7 +495,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(asctime)s %(levelname)s: %(message)s")
     cut_a = cut_a_applies(args)
     rank, world, local = dp.init_distributed()
-    err = scst_flag_error(args, world) or clip_flag_error(args, world)
+    err = scst_flag_error(args, world) or clip_flag_error(args, world) or accum_flag_error(args, world)
     if err:
         raise SystemExit("mtn_amd.train: " + err)
     local = local % torch.cuda.device_count()      # (several ranks may share a GPU in a gloo dry run)
@@ -546,7 +576,8 @@ def main(argv=None):
                 raise SystemExit("mtn_amd.train: --scst-xe-weight needs answers of at most 128 tokens (the metric kernels' longest sentence)")
             logging.info("self-critical training: %d samples per dialogue, reward %s, baseline %s, %d reference answers on the device",
                          scst.samples, scst.reward, scst.baseline, corpus.n_dialogs)
-        if args.eager and scst is None:
+        accum = args.accum_steps > 1                          # (--eager then runs the trainer's steps eagerly, as under scst)
+        if args.eager and scst is None and not accum:
             opt = NoamOpt(args.d_model, 1, args.warmup_steps, FusedAdam(model))
             if args.ema_decay:
                 opt.optimizer.enable_ema(args.ema_decay)
@@ -558,8 +589,8 @@ def main(argv=None):
             from .train_step import BucketedTrainer
             trainer = BucketedTrainer(model, corpus, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l,
                                       bucket=args.bucket, grad_sync=sync, ema_decay=args.ema_decay, scst=scst,
-                                      use_graph=not (args.eager and scst is not None), unlikelihood=args.unlikelihood_alpha,
-                                      clip_grad_norm=args.clip_grad_norm, **distill)
+                                      use_graph=not (args.eager and (scst is not None or accum)), unlikelihood=args.unlikelihood_alpha,
+                                      clip_grad_norm=args.clip_grad_norm, accum_steps=args.accum_steps, **distill)
         valid = None
         if args.valid_videos > 0 or valid_data is not None:
             vdata = valid_data if valid_data is not None else synthetic_corpus(args.valid_videos, args.vocab_size, args.ft_sizes, args.rand_seed + 1000)
@@ -567,7 +598,7 @@ def main(argv=None):
             valid = (DeviceCorpus(vdata, dev), vidx)
             logging.info("#validation sample = %d  #validation batch = %d", vn, len(vidx))
         min_valid = min_valid_ema = 1.0e10
-        graphed = not args.eager or scst is not None           # (self-critical --eager: the trainer's steps, run eagerly)
+        graphed = not args.eager or scst is not None or accum  # (self-critical / accumulating --eager: the trainer's steps, run eagerly)
         the_opt = trainer.opt if graphed else opt
         if args.resume:
             model.load_state_dict(torch.load(args.resume + ".pth.tar", map_location=dev), strict=False)
@@ -583,7 +614,10 @@ def main(argv=None):
                                        distill=(teacher, args.distill_alpha, args.distill_temperature) if teacher is not None else None, stats=stats,
                                        unlikelihood=args.unlikelihood_alpha)
             else:
+                seen = (trainer.updates, trainer.micro_steps)
                 mean, ntok = run_epoch_graphed(trainer, indices, epoch, args.report_interval, rank, rng, cut, stats=stats)
+                if accum and rank == 0:
+                    print("epoch %d optimiser updates: %d over %d batches" % (epoch + 1, trainer.updates - seen[0], trainer.micro_steps - seen[1]))
             means.append(mean)
             if rank == 0:
                 logging.info("epoch %d: %d target tokens trained%s", epoch + 1, ntok, " (answers cut at random)" if cut_a else "")
@@ -645,14 +679,16 @@ def main(argv=None):
     Q, H, C, T, V = args.lens
     batch = synthetic_batch(args.vocab_size, args.batch_size, Q, H, C, T, [V] * len(args.ft_sizes), args.ft_sizes, device=dev, seed=1 + rank)
     step = TrainStep(model, batch, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l, grad_sync=sync, ema_decay=args.ema_decay,
-                     unlikelihood=args.unlikelihood_alpha, clip_grad_norm=args.clip_grad_norm, **distill)
+                     unlikelihood=args.unlikelihood_alpha, clip_grad_norm=args.clip_grad_norm, accumulate=args.accum_steps > 1, **distill)
     ntok = int(batch.ntokens) * world
+    K = args.accum_steps
     for epoch in range(args.num_epochs):
         t0, tokens = time.time(), 0
         kd_sum = torch.zeros((), device=dev) if teacher is not None else None
         ul_sum = torch.zeros((), device=dev) if args.unlikelihood_alpha > 0.0 else None
         for j in range(args.steps_per_epoch):
-            loss = step()
+            # --accum-steps K: a call is one micro-step on the batch; every K-th one, and the epoch's last, closes the window and updates
+            loss = step() if K == 1 else step((j + 1) % K == 0 or j == args.steps_per_epoch - 1)
             tokens += ntok
             if ul_sum is not None:
                 ul_sum += step.last_ul
@@ -673,6 +709,8 @@ def main(argv=None):
                 torch.distributed.all_reduce(ul_sum)
             if rank == 0:
                 print("epoch %d mean unlikelihood per token: %f" % (epoch + 1, float(ul_sum) / max(1, args.steps_per_epoch)))
+        if K > 1 and rank == 0:
+            print("epoch %d optimiser updates: %d over %d batches" % (epoch + 1, -(-args.steps_per_epoch // K), args.steps_per_epoch))
         if args.clip_grad_norm:
             clip_epoch_report(step.opt.optimizer, epoch, rank)
         if args.model:

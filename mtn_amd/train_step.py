@@ -90,7 +90,7 @@ class TrainStep:
                  smoothing: float = 0.1, grad_sync=None, use_graph: bool = True, overlap: Optional[bool] = None, opt=None,
                  dynamic_norms: bool = False, fuse_optimizer: Optional[bool] = None, teacher=None, distill_alpha: float = 0.5,
                  distill_temperature: float = 1.0, ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, unlikelihood: float = 0.0,
-                 clip_grad_norm: float = 0.0):
+                 clip_grad_norm: float = 0.0, accumulate: bool = False):
         """``opt``: share an existing NoamOpt (several TrainSteps over one model, e.g. one per batch shape).
         ``dynamic_norms``: the batch tensors are refilled in place between steps, so the loss normalisers (token counts,
         train.py:35-39) are recomputed from them inside the step instead of once at construction.
@@ -135,7 +135,21 @@ class TrainStep:
         exchange every rank holds the whole reduced gradient and computes the same norm bits with no further collective.  Clipping
         under the SHARDED optimiser is out of scope (every slice would have to be reduced before any shard is updated, which undoes
         that schedule's point): asking for it explicitly (MTN_DP_SHARDED=1) raises.  ``last_grad_norm``: device double, the norm of
-        the step just run (None when clipping is off)."""
+        the step just run (None when clipping is off).
+        ``accumulate``: gradient accumulation over a window of micro-batches — the optimiser built here keeps a second flat fp32 buffer
+        (FusedAdam.enable_accumulation; a shared ``opt`` keeps whatever its owner enabled) and ``__call__(last)`` is one MICRO-step:
+        today's forward, loss and backward, normalised by its own token counts, then one mtn_grad_accum launch weighted by the
+        micro-step's target-token count over all ranks (``_norms[0]``, a device float).  Weights do not move inside a window; the call
+        with ``last`` true closes it: the window's gradient G = (sum_k w_k g_k) / (sum_k w_k) is then in the gradient buffer and the
+        exchange, Noam tick, clipping, Adam and EMA run once, on G (the step count counts windows).  G is the gradient of the
+        token-weighted mean of the micro-steps' losses: the concatenated batch's gradient for the main stream, and for the
+        auto-encoder streams too when the micro-batches share their query-to-target token ratio (otherwise a micro-batch's
+        auto-encoder term carries w_k / sum w, not its share of the query tokens).  A window of one launches nothing new: it is the
+        ``fuse_optimizer`` = False step bit for bit.  The captured form is a forward/backward graph and an optimiser graph with the
+        accumulate launch (and the exchange) between the replays; nothing in a window synchronises with the host.  The returned
+        loss is the micro-step's own.  Data parallelism: the whole-buffer, non-overlapped all-reduce, once per window, after the
+        closing launch; MTN_DP_SHARDED=1 raises.  With clipping on one rank the closing launch also writes the partials of G's sum
+        of squares and the update skips its mtn_grad_sumsq launch.  Not together with scst."""
         self.model, self.batch = model, batch
         clip_grad_norm = float(clip_grad_norm)
         if not clip_grad_norm >= 0.0:              # (nan fails the comparison)
@@ -148,6 +162,8 @@ class TrainStep:
                                                                                    else "scst"))
         self._init_teacher(teacher, distill_alpha, distill_temperature, vocab)
         self.scst = scst
+        if scst is not None and (accumulate or (opt is not None and getattr(opt.optimizer, "accum", None) is not None)):
+            raise ValueError("TrainStep: scst does not combine with gradient accumulation (accumulate=True): rl_step is one update per call")
         if scst is not None:
             if teacher is not None or grad_sync is not None:
                 raise ValueError("TrainStep: scst does not combine with a teacher (distillation) or with data parallelism")
@@ -159,8 +175,11 @@ class TrainStep:
                 opt.optimizer.enable_ema(ema_decay)
             if clip_grad_norm:
                 opt.optimizer.enable_clip(clip_grad_norm)
+            if accumulate:
+                opt.optimizer.enable_accumulation()
         self.opt = opt
         self.clipping = getattr(opt.optimizer, "clip_max_norm", None) is not None
+        self.accumulating = getattr(opt.optimizer, "accum", None) is not None
         self.dynamic_norms = dynamic_norms
         self.crit = LabelSmoothing(vocab, pad, smoothing)
         self.lc = SimpleLossCompute(model.generator, model.auto_encoder_generator, self.crit, opt=None, l=lam, sync=False)
@@ -171,14 +190,17 @@ class TrainStep:
         self._loss = None
         if overlap is None:
             overlap = os.environ.get("MTN_DP_OVERLAP", "1") != "0"
-        self.overlap = bool(overlap) and grad_sync is not None
+        self.overlap = bool(overlap) and grad_sync is not None and not self.accumulating     # (accumulation: the whole-buffer exchange)
         # data parallel: reduce-scatter + optimiser on this rank's shard + all-gather of the master weights
         # (dp.ShardedOptimizerSync) instead of all-reduce + the full optimiser pass on every rank; MTN_DP_SHARDED=0 = the latter
         self.sharded = None
         if self.clipping and grad_sync is not None and os.environ.get("MTN_DP_SHARDED", "0") != "0":
             raise ValueError("TrainStep: gradient clipping does not combine with the sharded data-parallel optimiser (MTN_DP_SHARDED): "
                              "the norm needs every slice reduced before any shard is updated; leave MTN_DP_SHARDED unset or 0")
-        if (grad_sync is not None and not self.clipping and os.environ.get("MTN_DP_SHARDED", "1") != "0"
+        if self.accumulating and grad_sync is not None and os.environ.get("MTN_DP_SHARDED", "0") != "0":
+            raise ValueError("TrainStep: gradient accumulation does not combine with the sharded data-parallel optimiser (MTN_DP_SHARDED): "
+                             "the update runs once per window, from the whole window gradient; leave MTN_DP_SHARDED unset or 0")
+        if (grad_sync is not None and not self.clipping and not self.accumulating and os.environ.get("MTN_DP_SHARDED", "1") != "0"
                 and hasattr(self.opt.optimizer, "step_range")):
             from .dp import ShardedOptimizerSync
             if getattr(grad_sync, "compress", False):
@@ -198,7 +220,8 @@ class TrainStep:
             self.sharded = sh
         self._g_seg = None
         self._st = None
-        self._fuse_opt = False if fuse_optimizer is False else None
+        self._g_opt_sumsq = None                 # accumulation with clipping: the optimiser graph that reads the closing launch's partials
+        self._fuse_opt = False if fuse_optimizer is False or self.accumulating else None
         ae_y = batch.cap if model.auto_encoder_ft in ("caption", "summary") else batch.query
         self._ae_y = ae_y
         # loss normalisers (train.py:35-39).  Under DP they are all-reduced ONCE here for a static batch so that
@@ -631,7 +654,11 @@ class TrainStep:
 
     def _capture_simple(self):
         self._g_fb = torch.cuda.CUDAGraph()
-        if self.grad_sync is None:
+        if self.accumulating:                     # the accumulate launch (and the exchange) sit between the two replays
+            with torch.cuda.graph(self._g_fb, capture_error_mode=CAPTURE_MODE):
+                self._loss = self._fwd_bwd()
+            self._g_opt = self._capture_optim(False)
+        elif self.grad_sync is None:
             with torch.cuda.graph(self._g_fb, capture_error_mode=CAPTURE_MODE):
                 if self._fused():
                     self._loss = self._step_fused()
@@ -649,10 +676,48 @@ class TrainStep:
                     self._optim()
         # the warm-up/capture passes did not run the optimiser outside capture: parameters are untouched
 
-    def __call__(self) -> torch.Tensor:
+    def _capture_optim(self, have_sumsq: bool):
+        """The optimiser graph of the accumulating step.  ``have_sumsq``: clipping reads the partials the closing mtn_grad_accum launch
+        wrote (no mtn_grad_sumsq in this graph); False: the norm launch is part of it (a window of one, a gradient exchange, no clipping)."""
+        self.opt.optimizer._accum_sumsq = bool(have_sumsq)       # (consumed by FusedAdam._clip inside the capture)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self._g_fb.pool(), capture_error_mode=CAPTURE_MODE):
+            self._optim()
+        return g
+
+    def _micro_step(self, last: bool) -> torch.Tensor:
+        """__call__ under accumulation: forward + backward, the accumulate launch, and on the window's last micro-step the exchange and
+        the optimiser.  Nothing synchronises with the host."""
+        adam = self.opt.optimizer
+        if self.use_graph:
+            if self._g_fb is None:
+                self._capture()
+            self._g_fb.replay()
+            loss = self._loss
+        else:
+            loss = self._fwd_bwd()
+        adam.accumulate(self._norms[0], last, sumsq=self.grad_sync is None)
+        if not last:
+            return loss
+        if self.grad_sync is not None:
+            self.grad_sync()
+        if not self.use_graph:
+            self._optim()
+        elif adam._accum_sumsq:
+            if self._g_opt_sumsq is None:
+                self._g_opt_sumsq = self._capture_optim(True)
+            self._g_opt_sumsq.replay()
+        else:
+            self._g_opt.replay()
+        return loss
+
+    def __call__(self, last: bool = True) -> torch.Tensor:
         """Runs one step; returns the device tensor of the NORMALISED loss (main KL / global target tokens + lambda * sum of the
         auto-encoder KLs / global query tokens: the `loss` of data_utils.py:135-144, before the `* norm` of :156), without
-        synchronising."""
+        synchronising.  ``last`` matters under accumulation only (``accumulate``): the call is one micro-step, and ``last`` closes the
+        window."""
+        if self.accumulating:
+            return self._micro_step(bool(last))
         if not self.use_graph:
             if self.overlap:
                 self._run_segmented(self._segments())
@@ -718,14 +783,23 @@ class BucketedTrainer:
     def __init__(self, model, corpus, vocab_size: int, pad: int = 1, warmup: int = 4000, lam: float = 1.0, bucket: int = 8,
                  grad_sync=None, max_shapes: int = 64, teacher=None, distill_alpha: float = 0.5, distill_temperature: float = 1.0,
                  ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, use_graph: bool = True, unlikelihood: float = 0.0,
-                 clip_grad_norm: float = 0.0):
+                 clip_grad_norm: float = 0.0, accum_steps: int = 1):
         """``scst``: self-critical sequence training — every padded shape keeps, next to its static source Batch, a TrainStep(scst=...)
         whose own static batch holds the drawn rows; a step refills the source in place and calls rl_step with the batch's QA ids as
         corpus items and sampling keys and the seed ``scst.seed + rl_steps`` (``rl_steps``: steps taken; set it after a resume).  With
         xe_weight the rows have max(scst.max_length, the shape's padded answer length) positions.  ``last_reward`` / ``last_baseline``:
         the last step's device scalars.  ``use_graph`` = False: the same steps run eagerly.
         ``unlikelihood``: TrainStep's alpha for every shape; ``last_ul``: the last step's device scalar (None at 0).
-        ``clip_grad_norm``: > 0 = the one optimiser all shapes share clips the gradient's global norm (FusedAdam.enable_clip)."""
+        ``clip_grad_norm``: > 0 = the one optimiser all shapes share clips the gradient's global norm (FusedAdam.enable_clip).
+        ``accum_steps``: K > 1 = gradient accumulation (TrainStep's ``accumulate``): step() is one micro-step and every K-th one, or
+        one called with ``last=True``, closes the window and updates.  The accumulator belongs to the shared optimiser, so the
+        micro-steps of one window may fall into different padded shapes.  ``micro_steps`` / ``updates``: counted on the host.
+        1 = off: today's step, launch for launch.  Not together with scst."""
+        if int(accum_steps) != accum_steps or int(accum_steps) < 1:
+            raise ValueError("BucketedTrainer: accum_steps is an integer >= 1")
+        self.accum_steps, self.micro_steps, self.updates, self._in_window = int(accum_steps), 0, 0, 0
+        if self.accum_steps > 1 and scst is not None:
+            raise ValueError("BucketedTrainer: scst does not combine with gradient accumulation (accum_steps > 1): rl_step is one update per call")
         self.unlikelihood, self.last_ul = float(unlikelihood), None
         if not (self.unlikelihood >= 0.0 and math.isfinite(self.unlikelihood)):
             raise ValueError("BucketedTrainer: unlikelihood is finite and >= 0")
@@ -744,6 +818,11 @@ class BucketedTrainer:
             self.opt.optimizer.enable_ema(ema_decay)
         if clip_grad_norm:
             self.opt.optimizer.enable_clip(clip_grad_norm)
+        if self.accum_steps > 1:
+            if grad_sync is not None and os.environ.get("MTN_DP_SHARDED", "0") != "0":
+                raise ValueError("BucketedTrainer: gradient accumulation does not combine with the sharded data-parallel optimiser "
+                                 "(MTN_DP_SHARDED): leave MTN_DP_SHARDED unset or 0")
+            self.opt.optimizer.enable_accumulation()
         self.steps = {}
         self.last_kd = None
 
@@ -757,10 +836,12 @@ class BucketedTrainer:
         pidx = self._padded(index)
         return (tuple(pidx[2]),) + tuple(pidx[3:])
 
-    def step(self, index, cut_a: bool = False, rng=None):
+    def step(self, index, cut_a: bool = False, rng=None, last: Optional[bool] = None):
         """One optimiser step on the batch described by ``index`` (an entry of data_handler.make_batch_indices with
         separate_caption=True).  Returns (device loss tensor, the static Batch that now holds this batch).  ``cut_a``: the
-        reference's random answer truncation, drawn once per step from ``rng`` (data_handler.draw_cuts; None = np.random)."""
+        reference's random answer truncation, drawn once per step from ``rng`` (data_handler.draw_cuts; None = np.random).
+        ``last`` (accum_steps > 1: the call is one micro-step): None = the trainer counts and closes the window at accum_steps;
+        True closes it now (an epoch's tail); False keeps it open, whatever the count."""
         from .data_handler import make_batch
         pidx = self._padded(index)
         key = (tuple(pidx[2]),) + tuple(pidx[3:])                    # (== self._key(index))
@@ -789,7 +870,16 @@ class BucketedTrainer:
             self.last_reward, self.last_baseline = hit[1].last_reward, hit[1].last_baseline
             hit[1].batch._norms_global = hit[1]._norms
             return loss, hit[1].batch
-        loss = hit[1]()
+        if self.accum_steps > 1:
+            self._in_window += 1
+            last = self._in_window >= self.accum_steps if last is None else bool(last)
+            loss = hit[1](last)
+            self.micro_steps += 1
+            if last:
+                self._in_window = 0
+                self.updates += 1
+        else:
+            loss = hit[1]()
         self.last_kd = hit[1].last_kd               # (device scalar; None without a teacher)
         self.last_ul = hit[1].last_ul               # (device scalar; None without unlikelihood)
         hit[0]._norms_global = hit[1]._norms        # [target tokens, auto-encoder tokens] the step's loss is divided by (all ranks)
