@@ -331,23 +331,33 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_mfma_kernel(const AttnGro
     attn_fwd_mfma_body<T, DK, NW>(A, blockIdx.x / A.h, blockIdx.x % A.h, blockIdx.y * MQ, wave, fsm);
 }
 
-template <typename T, int DK, int NW> static int launch_fwd_mfma_nw(const AttnGroup& G, dim3 grid, hipStream_t s) {
+static constexpr size_t LDS_MAX = 160 * 1024;   // LDS of one CU: the most a workgroup can ask for
+
+// LDS request of the NW-wave forward kernel: one V^T image per wave; with NW > 1 the combine area aliases the images
+template <typename T, int DK, int NW> static constexpr size_t fwd_mfma_lds() {
     const size_t vt = (size_t)DK * (MK * sizeof(T) + tpad<T>());
-    if constexpr (NW == 1) {
-        hipLaunchKernelGGL((attn_fwd_mfma_kernel<T, DK, 1>), grid, dim3(64), vt, s, G);
-    } else {
-        const size_t comb = sizeof(float) * (NW * DK * 33 + 2 * NW * 32);
-        const size_t lds = NW * vt > comb ? NW * vt : comb;        // the combine area aliases the V^T images
-        if (int rc = set_lds(attn_fwd_mfma_kernel<T, DK, NW>, lds)) return rc;
-        hipLaunchKernelGGL((attn_fwd_mfma_kernel<T, DK, NW>), grid, dim3(64 * NW), lds, s, G);
-    }
-    return MTN_OK;
+    if (NW == 1) return vt;
+    const size_t comb = sizeof(float) * (NW * DK * 33 + 2 * NW * 32);
+    return NW * vt > comb ? NW * vt : comb;
 }
-// nw = waves per workgroup = key tiles of the longest memory, capped at 4 (1, 2 or 4)
+template <typename T, int DK, int NW> static int launch_fwd_mfma_nw(const AttnGroup& G, dim3 grid, hipStream_t s) {
+    constexpr size_t lds = fwd_mfma_lds<T, DK, NW>();
+    if constexpr (lds > LDS_MAX) {
+        return -1;                                                 // (launch_fwd_mfma never asks for it)
+    } else {
+        if constexpr (NW > 1) {
+            if (int rc = set_lds(attn_fwd_mfma_kernel<T, DK, NW>, lds)) return rc;
+        }
+        hipLaunchKernelGGL((attn_fwd_mfma_kernel<T, DK, NW>), grid, dim3(64 * NW), lds, s, G);
+        return MTN_OK;
+    }
+}
+// nw = waves per workgroup wanted (1, 2, 4 or 8: the key tiles of the longest memory, rounded up); taken is the largest wave count
+// <= nw whose LDS request fits the CU (fp32 with d_k = 128: 4, the 8-wave image is 272 KB).  Every wave count walks all key tiles.
 template <typename T, int DK> static int launch_fwd_mfma(const AttnGroup& G, dim3 grid, int nw, hipStream_t s) {
     if (nw <= 1) return launch_fwd_mfma_nw<T, DK, 1>(G, grid, s);
     if (nw == 2) return launch_fwd_mfma_nw<T, DK, 2>(G, grid, s);
-    if (nw <= 4) return launch_fwd_mfma_nw<T, DK, 4>(G, grid, s);
+    if (nw <= 4 || fwd_mfma_lds<T, DK, 8>() > LDS_MAX) return launch_fwd_mfma_nw<T, DK, 4>(G, grid, s);
     return launch_fwd_mfma_nw<T, DK, 8>(G, grid, s);
 }
 template <typename T> static int dispatch_fwd_mfma(int dk, const AttnGroup& G, dim3 grid, int nw, hipStream_t s) {
@@ -646,23 +656,32 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_mfma_kernel(const AttnGro
     }
 }
 
-template <typename T, int DK, int NW> static int launch_bwd_mfma_nw(const AttnGroup& G, dim3 grid, hipStream_t s) {
+// LDS request of the NW-wave backward kernel: the shared dO^T / Q^T images and D, then K^T + dS per wave; with NW > 1 the dQ combine
+// area aliases the per-wave images
+template <typename T, int DK, int NW> static constexpr size_t bwd_mfma_lds() {
     const size_t rowb = 32 * sizeof(T) + tpad<T>();
     const size_t shared = 2 * (size_t)DK * rowb + 32 * sizeof(float), per_wave = ((size_t)DK + 32) * rowb;
-    if constexpr (NW == 1) {
-        hipLaunchKernelGGL((attn_bwd_mfma_kernel<T, DK, 1>), grid, dim3(64), shared + per_wave, s, G);
-    } else {
-        const size_t comb = sizeof(float) * NW * DK * 33;
-        const size_t lds = shared + (NW * per_wave > comb ? NW * per_wave : comb);   // the dQ combine area aliases the per-wave images
-        if (int rc = set_lds(attn_bwd_mfma_kernel<T, DK, NW>, lds)) return rc;
-        hipLaunchKernelGGL((attn_bwd_mfma_kernel<T, DK, NW>), grid, dim3(64 * NW), lds, s, G);
-    }
-    return MTN_OK;
+    if (NW == 1) return shared + per_wave;
+    const size_t comb = sizeof(float) * NW * DK * 33;
+    return shared + (NW * per_wave > comb ? NW * per_wave : comb);
 }
+template <typename T, int DK, int NW> static int launch_bwd_mfma_nw(const AttnGroup& G, dim3 grid, hipStream_t s) {
+    constexpr size_t lds = bwd_mfma_lds<T, DK, NW>();
+    if constexpr (lds > LDS_MAX) {
+        return -1;                                                 // (launch_bwd_mfma never asks for it)
+    } else {
+        if constexpr (NW > 1) {
+            if (int rc = set_lds(attn_bwd_mfma_kernel<T, DK, NW>, lds)) return rc;
+        }
+        hipLaunchKernelGGL((attn_bwd_mfma_kernel<T, DK, NW>), grid, dim3(64 * NW), lds, s, G);
+        return MTN_OK;
+    }
+}
+// as launch_fwd_mfma: the largest wave count <= nw that fits (fp32 with d_k = 128: 4, the 8-wave image is 216 KB; bf16 fits at 150 KB)
 template <typename T, int DK> static int launch_bwd_mfma(const AttnGroup& G, dim3 grid, int nw, hipStream_t s) {
     if (nw <= 1) return launch_bwd_mfma_nw<T, DK, 1>(G, grid, s);
     if (nw == 2) return launch_bwd_mfma_nw<T, DK, 2>(G, grid, s);
-    if (nw <= 4) return launch_bwd_mfma_nw<T, DK, 4>(G, grid, s);
+    if (nw <= 4 || bwd_mfma_lds<T, DK, 8>() > LDS_MAX) return launch_bwd_mfma_nw<T, DK, 4>(G, grid, s);
     return launch_bwd_mfma_nw<T, DK, 8>(G, grid, s);
 }
 template <typename T> static int dispatch_bwd_mfma(int dk, const AttnGroup& G, dim3 grid, int nw, hipStream_t s) {
@@ -697,7 +716,11 @@ static int check_attn(const mtn_attn_args* A, bool bwd) {
 template <typename K> static int set_lds(K kernel, size_t bytes) {
     if (bytes > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) { mtn_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return MTN_ERR_LAUNCH; }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();   // a caller may fall back to another kernel: its launch check must not read this refusal
+            mtn_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
+            return MTN_ERR_LAUNCH;
+        }
     }
     return MTN_OK;
 }
