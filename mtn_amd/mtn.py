@@ -145,52 +145,47 @@ class SublayerConnection(nn.Module):
             return torch.bfloat16, None, None
         return o.compute_dtype, (o._seed if self.training else None), o._queue
 
-    def attend(self, x, attn: MultiHeadedAttention, mem, mask):
+    def _common(self, module, grouped):
+        """-> (module.fused(), the config fields both kinds share).  Gradient destinations (and with them the queue) are set when
+        the model is flattened; a group member (`grouped`) requires them."""
         lp, seed, queue = self._ctx()
-        f = attn.fused()
+        f = module.fused()
         g = None
-        if f["grads"] is not None and self.norm._grads is not None:
+        if grouped or (f["grads"] is not None and self.norm._grads is not None):
             g = dict(f["grads"], ln_a=self.norm._grads[0], ln_b=self.norm._grads[1])
-        cfg = ops.MhaConfig(heads=attn.h, eps=self.norm.eps,
-                            p_attn=attn.p if self.training else 0.0, p_out=self.p if self.training else 0.0,
-                            salt=self.salt, seed=seed, lp_dtype=lp, w_qkv_lp=f["w_qkv_lp"], w_o_lp=f["w_o_lp"],
-                            w_qkv_lpT=f.get("w_qkv_lpT"), w_o_lpT=f.get("w_o_lpT"), grads=g,
-                            queue=queue if g is not None else None, ln_fold=self._fold_for(attn))
+        return f, dict(eps=self.norm.eps, p_out=self.p if self.training else 0.0, salt=self.salt, seed=seed, lp_dtype=lp, grads=g,
+                       queue=queue if g is not None else None, ln_fold=self._fold_for(module))
+
+    def _mha_config(self, attn: MultiHeadedAttention, mem, grouped=False):
+        """-> (fused parameters, ops.MhaConfig, the memory's compute-dtype copy if it has one in this sublayer's dtype)"""
+        f, kw = self._common(attn, grouped)
+        cfg = ops.MhaConfig(heads=attn.h, p_attn=attn.p if self.training else 0.0, w_qkv_lp=f["w_qkv_lp"], w_o_lp=f["w_o_lp"],
+                            w_qkv_lpT=f.get("w_qkv_lpT"), w_o_lpT=f.get("w_o_lpT"), **kw)
         mem_lp = getattr(mem, "_mtn_lp", None) if mem is not None else None
-        if mem_lp is not None and mem_lp.dtype != lp:
+        if mem_lp is not None and mem_lp.dtype != cfg.lp_dtype:
             mem_lp = None
+        return f, cfg, mem_lp
+
+    def _ffn_config(self, ff: PositionwiseFeedForward, grouped=False):
+        f, kw = self._common(ff, grouped)
+        return f, ops.FfnConfig(p_hidden=ff.p if self.training else 0.0, w1_lp=f["w1_lp"], w2_lp=f["w2_lp"], w1_lpT=f.get("w1_lpT"),
+                                w2_lpT=f.get("w2_lpT"), **kw)
+
+    def attend(self, x, attn: MultiHeadedAttention, mem, mask):
+        f, cfg, mem_lp = self._mha_config(attn, mem)
         return ops.MHASublayerFn.apply(x, mem, mem_lp, mask, self.norm.a_2, self.norm.b_2,
                                        f["w_qkv"], f["b_qkv"], f["w_o"], f["b_o"], cfg)
 
     def member(self, sublayer, mem=None, mask=None):
         """This sublayer as a member of a lockstep group (ops.SublayerGroupFn); needs the flattened model."""
-        lp, seed, queue = self._ctx()
-        f = sublayer.fused()
-        g = dict(f["grads"], ln_a=self.norm._grads[0], ln_b=self.norm._grads[1])
         if isinstance(sublayer, MultiHeadedAttention):
-            cfg = ops.MhaConfig(heads=sublayer.h, eps=self.norm.eps, p_attn=sublayer.p if self.training else 0.0,
-                                p_out=self.p if self.training else 0.0, salt=self.salt, seed=seed, lp_dtype=lp,
-                                w_qkv_lp=f["w_qkv_lp"], w_o_lp=f["w_o_lp"], w_qkv_lpT=f.get("w_qkv_lpT"), w_o_lpT=f.get("w_o_lpT"),
-                                grads=g, queue=queue, ln_fold=self._fold_for(sublayer))
-            mem_lp = getattr(mem, "_mtn_lp", None) if mem is not None else None
-            if mem_lp is not None and mem_lp.dtype != lp:
-                mem_lp = None
+            f, cfg, mem_lp = self._mha_config(sublayer, mem, grouped=True)
             return ops.GroupMember("mha", cfg, (self.norm.a_2, self.norm.b_2, f["b_qkv"], f["b_o"]), mask, mem_lp)
-        cfg = ops.FfnConfig(eps=self.norm.eps, p_hidden=sublayer.p if self.training else 0.0, p_out=self.p if self.training else 0.0,
-                            salt=self.salt, seed=seed, lp_dtype=lp, w1_lp=f["w1_lp"], w2_lp=f["w2_lp"], w1_lpT=f.get("w1_lpT"),
-                            w2_lpT=f.get("w2_lpT"), grads=g, queue=queue, ln_fold=self._fold_for(sublayer))
+        f, cfg = self._ffn_config(sublayer, grouped=True)
         return ops.GroupMember("ffn", cfg, (self.norm.a_2, self.norm.b_2, f["b1"], f["b2"]))
 
     def feed(self, x, ff: PositionwiseFeedForward):
-        lp, seed, queue = self._ctx()
-        f = ff.fused()
-        g = None
-        if f["grads"] is not None and self.norm._grads is not None:
-            g = dict(f["grads"], ln_a=self.norm._grads[0], ln_b=self.norm._grads[1])
-        cfg = ops.FfnConfig(eps=self.norm.eps, p_hidden=ff.p if self.training else 0.0,
-                            p_out=self.p if self.training else 0.0, salt=self.salt, seed=seed, lp_dtype=lp,
-                            w1_lp=f["w1_lp"], w2_lp=f["w2_lp"], w1_lpT=f.get("w1_lpT"), w2_lpT=f.get("w2_lpT"), grads=g,
-                            queue=queue if g is not None else None, ln_fold=self._fold_for(ff))
+        f, cfg = self._ffn_config(ff)
         return ops.FFNSublayerFn.apply(x, self.norm.a_2, self.norm.b_2, f["w1"], f["b1"], f["w2"], f["b2"], cfg)
 
     def forward(self, x, sublayer, mem=None, mask=None, self_attention=False):
@@ -238,9 +233,9 @@ class DecoderLayer(nn.Module):
             kv = getattr(sc, "_kv_ready", None)        # K|V of a constant memory projected ahead of the layer loop
             if kv is not None and mb.kind == "mha" and mem is not None and kv.size(0) == mem.size(0) * mem.size(1):
                 mb.kv_ready = kv
-            if torch.is_grad_enabled() and _HANDOFF:   # gradient hand-off along the chain (ops.GroupMember.holder / .feeds)
+            if torch.is_grad_enabled() and _HANDOFF:   # gradient hand-off along the chain (ops.HandOff: GroupMember.holder / .feeds)
                 mb.feeds = getattr(inp, "_mtn_next", None)
-                mb.holder = dict(p=mb.cfg.p_out, salt=mb.cfg.salt * 4 + 1, seed=mb.cfg.seed, lp=mb.cfg.lp_dtype, dyl=None, dx_ptr=None, ver=None, shape=None)
+                mb.holder = ops.HandOff.of(mb.cfg)
             members.append(mb)
             tensors += [inp, mem if isinstance(mod, MultiHeadedAttention) else None]
         # attention members first, then FFN members (the C side takes two arrays)

@@ -284,6 +284,108 @@ class ParamGradQueue:
         self.gemm, self.ln, self.keep = [], [], []
 
 
+# ------------------------------------------------------------------------------------------ gradient protocols
+class GradMeet:
+    """Where the gradients of a tensor with several consumers meet: one fp32 buffer instead of autograd adds.  It rides on the
+    tensor as `_mtn_gacc`.  Every consumer joins in forward; in backward each settles once, in autograd's order: as an INPUT
+    (`settle`: its dx becomes the buffer, or is added to it after the launch) or as an attention MEMORY (`buffer`: the dmem GEMM
+    writes or accumulates in place).  The last to settle returns the sum to autograd; everyone before returns nothing."""
+    __slots__ = ("buf", "remaining")
+
+    def __init__(self):
+        self.buf, self.remaining = None, 0
+
+    @staticmethod
+    def join(t, create=False):
+        """forward: one more consumer of `t` -> its meeting point (None when nobody opened one and `create` is off)."""
+        g = getattr(t, "_mtn_gacc", None)
+        if g is None and create:
+            g = t._mtn_gacc = GradMeet()
+        if g is not None:
+            g.remaining += 1
+        return g
+
+    def settle(self, dx, later):
+        """backward, input role.  -> what this consumer returns to autograd.  An addition into the buffer has to wait until dx is
+        written: it is appended to `later` as (buffer, dx), for the caller to run after its launch, in order."""
+        self.remaining -= 1
+        if self.buf is None:
+            if self.remaining > 0:
+                self.buf = dx                  # first writer: the others accumulate into our dx
+                return None
+            return dx                          # nobody else came
+        buf = self.buf
+        later.append((buf, dx))
+        if self.remaining > 0:
+            return None
+        self.buf = None
+        return buf
+
+    def buffer(self, shape, device):
+        """backward, memory role.  -> (buffer, accumulate, last): write the gradient to `buffer` (accumulate = 0) or add it there
+        (1); `last`: the sum is complete with this write, return it to autograd."""
+        accumulate = int(self.buf is not None)
+        if self.buf is None:
+            self.buf = torch.empty(shape, device=device, dtype=torch.float32)
+        buf = self.buf
+        self.remaining -= 1
+        if self.remaining == 0:
+            self.buf = None
+        return buf, accumulate, self.remaining == 0
+
+    def seed(self, grad, shape):
+        """A gradient that arrives from outside the graph (a leaf's .grad across a layer cut) takes the first writer's place.
+        -> whether it was taken (then it must not go to autograd as well)."""
+        if self.remaining > 0 and self.buf is None and grad.is_contiguous() and grad.dtype == torch.float32 and grad.shape == shape:
+            self.buf = grad
+            return True
+        return False
+
+
+def _out_site(cfg):
+    """(p, salt, seed) of the dropout on a sublayer's output (mtn.py:127): the site of its own kernels and of its HandOff."""
+    return cfg.p_out, cfg.salt * 4 + 1, cfg.seed
+
+
+class HandOff:
+    """A sublayer's dy, delivered by whoever computes it: the consumer of the sublayer's output writes its dx once more, through
+    the PRODUCER's output dropout (p, salt, seed) and in the producer's compute dtype (lp), so the producer's backward starts
+    without a cast launch (include/mtn_hip.h: dyl_ready / next_dyl).  It rides on the output tensor as `_mtn_next`."""
+    __slots__ = ("p", "salt", "seed", "lp", "dyl", "dx_ptr", "ver", "shape")
+
+    def __init__(self, p, salt, seed, lp):
+        self.p, self.salt, self.seed, self.lp = p, salt, seed, lp
+        self.dyl = self.dx_ptr = self.ver = self.shape = None
+
+    @classmethod
+    def of(cls, cfg):
+        return cls(*_out_site(cfg), cfg.lp_dtype)
+
+    def drop(self) -> L.Dropout:
+        return _drop(self.p, self.salt, self.seed)
+
+    def offer(self, dx, dtype):
+        """consumer: -> the tensor its kernels fill with dropout-masked dx in `dtype`; remembers which dx that copy stands for."""
+        self.dyl = torch.empty(dx.shape, device=dx.device, dtype=dtype)
+        self.dx_ptr, self.ver, self.shape = dx.data_ptr(), dx._version, dx.shape
+        return self.dyl
+
+    def claim(self, dy):
+        """producer: -> the offered copy if `dy` IS the dx it was made from, untouched, else None; the offer ends either way.
+        Valid only with the same storage address, the same shape and the version counter dx had: autograd sums gradients in
+        place with add_, which bumps it; any tensor derived from dx — a sum, a clone — is allocated while dx is still alive, so
+        it cannot sit at dx's address.  The dx tensor itself is not held: a leaf's .grad may then take it over without a copy
+        (layer-segmented backward)."""
+        ok = self.dyl is not None and self.dx_ptr == dy.data_ptr() and self.ver == dy._version and tuple(self.shape) == tuple(dy.shape)
+        ready, self.dyl, self.dx_ptr = (self.dyl if ok else None), None, None
+        return ready
+
+    def withdraw(self, ptr):
+        """The tensor at `ptr` is about to be accumulated into outside autograd's sight: an offer made for it ends."""
+        if self.dx_ptr == ptr:
+            self.dyl = self.dx_ptr = None
+
+
 # ------------------------------------------------------------------------------------------ LayerNorm
 class LayerNormFn(torch.autograd.Function):
     """mtn.py:111-114.  Returns (y_f32, y_lp); y_lp (compute dtype copy for GEMM operands) is non-differentiable."""
@@ -367,17 +469,12 @@ class LayerNormGroupFn(torch.autograd.Function):
         L.check(lib.mtn_layernorm_fwd_group(code, n, descs, L.stream_ptr()))
         spec["_lp_rows"] = y_lp
         ctx.spec, ctx.saved, ctx.rows, ctx.d = spec, saved, rows, d
-        # gradient hand-off (GroupMember.holder): the sublayer that produced an input wants dx once more, through ITS output dropout,
-        # in the compute dtype
+        # gradient hand-off (HandOff): the sublayer that produced an input wants dx once more, through ITS output dropout, in the
+        # compute dtype
         ctx.feeds = [getattr(t, "_mtn_next", None) for t in tensors[:n]]
         # an input that a sublayer attends as memory too (the last layer's auto-encoder outputs): the two gradients meet in one
-        # buffer (protocol of SublayerGroupFn: `_mtn_gacc`) instead of an autograd add
-        ctx.xaccs = []
-        for t in tensors[:n]:
-            xg = getattr(t, "_mtn_gacc", None) if (_XACC and t.requires_grad) else None
-            if xg is not None:
-                xg["remaining"] += 1
-            ctx.xaccs.append(xg)
+        # buffer (GradMeet) instead of an autograd add
+        ctx.xaccs = [GradMeet.join(t) if (_XACC and t.requires_grad) else None for t in tensors[:n]]
         return tuple(ys)
 
     @staticmethod
@@ -396,10 +493,9 @@ class LayerNormGroupFn(torch.autograd.Function):
             B_.rows, B_.d, B_.eps, B_.x, B_.a2, B_.mean, B_.rstd = rows[i], d, eps, x.data_ptr(), a2.data_ptr(), mean.data_ptr(), rstd.data_ptr()
             B_.g, B_.dx, B_.partial = g.data_ptr(), dx.data_ptr(), partial.data_ptr()
             f = ctx.feeds[i]
-            if f is not None and f.get("lp") is not None and f["lp"] != torch.float32 and ctx.xaccs[i] is None:   # (a shared gradient buffer is not final here)
-                nxt = torch.empty(x.shape, device=x.device, dtype=f["lp"])
-                f["dyl"], f["dx_ptr"], f["ver"], f["shape"] = nxt, dx.data_ptr(), dx._version, dx.shape
-                B_.dx_lp, B_.dx_lp_dtype, B_.dx_lp_drop = nxt.data_ptr(), L.dtype_code(f["lp"]), _drop(f["p"], f["salt"], f["seed"])
+            if f is not None and f.lp is not None and f.lp != torch.float32 and ctx.xaccs[i] is None:   # (a shared gradient buffer is not final here)
+                nxt = f.offer(dx, f.lp)
+                B_.dx_lp, B_.dx_lp_dtype, B_.dx_lp_drop = nxt.data_ptr(), L.dtype_code(f.lp), f.drop()
                 keep.append(nxt)
             da = ga if ga is not None else torch.empty_like(a2)
             db = gb if gb is not None else torch.empty_like(a2)
@@ -408,18 +504,12 @@ class LayerNormGroupFn(torch.autograd.Function):
             dxs.append(dx)
             keep += [g, partial]
         L.check(lib.mtn_layernorm_bwd_group(n, descs, L.stream_ptr()))
+        post = []
         for i, xg in enumerate(ctx.xaccs):
-            if xg is None:
-                continue
-            xg["remaining"] -= 1
-            if xg["buf"] is None and xg["remaining"] > 0:
-                xg["buf"], dxs[i] = dxs[i], None                  # first writer: the memory-role users accumulate into our dx
-            elif xg["buf"] is not None:
-                buf = xg["buf"]
-                buf.add_(dxs[i])
-                dxs[i] = None
-                if xg["remaining"] == 0:
-                    dxs[i], xg["buf"] = buf, None
+            if xg is not None:
+                dxs[i] = xg.settle(dxs[i], post)
+        for buf, dxp in post:
+            buf.add_(dxp)
         now = []
         for desc, partial, has_dest in finals:
             if queue is not None and has_dest:
@@ -475,101 +565,6 @@ class MhaConfig:
     ln_fold: Optional[torch.Tensor] = None       # fold vectors of w_qkv behind the sublayer's LayerNorm (mtn_ln_fold), float [2K]
 
 
-class MHASublayerFn(torch.autograd.Function):
-    """y = x + dropout(MHA(LN(x), mem, mem, mask)).  mem=None -> self-attention (key=value=LN(x), mtn.py:183,209)."""
-
-    @staticmethod
-    def forward(ctx, x, mem, mem_lp, mask, ln_a, ln_b, w_qkv, b_qkv, w_o, b_o, cfg: MhaConfig):
-        _require_cuda(x, mem, ln_a, w_qkv)
-        lib = L.load()
-        x = x.contiguous()
-        B, a, d = x.shape
-        self_attn = mem is None
-        m = a if self_attn else mem.size(1)
-        lp = cfg.lp_dtype
-        code = L.dtype_code(lp)
-        dev = x.device
-        if not self_attn and mem_lp is None:
-            mem_lp = cast_to_lp(mem, lp)
-        w_qkv_lp = cfg.w_qkv_lp if cfg.w_qkv_lp is not None else cast_to_lp(w_qkv, lp)
-        w_o_lp = cfg.w_o_lp if cfg.w_o_lp is not None else cast_to_lp(w_o, lp)
-        mask_u8, sb, sq = _mask_u8(mask, B, a, m)
-        y = torch.empty_like(x)
-        xn = torch.empty(B * a, d, device=dev, dtype=lp)
-        mean = torch.empty(B * a, device=dev, dtype=torch.float32)
-        rstd = torch.empty_like(mean)
-        qkv = torch.empty(B * a, 3 * d if self_attn else d, device=dev, dtype=lp)
-        kv = None if self_attn else torch.empty(B * m, 2 * d, device=dev, dtype=lp)
-        o = torch.empty(B * a, d, device=dev, dtype=lp)
-        lse = torch.empty(2 * B * cfg.heads * a, device=dev, dtype=torch.float32)
-        args = L.MhaArgs()
-        args.B, args.a, args.m, args.d, args.h = B, a, m, d, cfg.heads
-        args.self_attn, args.ln_eps = int(self_attn), cfg.eps
-        args.drop_attn = _drop(cfg.p_attn, cfg.salt * 4 + 0, cfg.seed)
-        args.drop_out = _drop(cfg.p_out, cfg.salt * 4 + 1, cfg.seed)
-        args.x, args.mem = x.data_ptr(), L.ptr(mem_lp)
-        args.mask, args.mask_sb, args.mask_sq = L.ptr(mask_u8), sb, sq
-        args.ln_a, args.ln_b = ln_a.data_ptr(), ln_b.data_ptr()
-        args.w_qkv, args.b_qkv, args.w_o, args.b_o = w_qkv_lp.data_ptr(), b_qkv.data_ptr(), w_o_lp.data_ptr(), b_o.data_ptr()
-        args.y, args.xn, args.mean, args.rstd = y.data_ptr(), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr()
-        args.qkv, args.kv, args.o, args.lse = qkv.data_ptr(), L.ptr(kv), o.data_ptr(), lse.data_ptr()
-        L.check(lib.mtn_mha_sublayer_fwd(code, C.byref(args), L.stream_ptr()))
-        ctx.save_for_backward(x, mem_lp, mask_u8, ln_a, ln_b, w_qkv_lp, b_qkv, w_o_lp, b_o, xn, mean, rstd, qkv, kv, o, lse)
-        ctx.cfg, ctx.dims, ctx.mask_strides = cfg, (B, a, m, d, self_attn), (sb, sq)
-        ctx.need_dmem = (not self_attn) and mem.requires_grad
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, mem_lp, mask_u8, ln_a, ln_b, w_qkv_lp, b_qkv, w_o_lp, b_o, xn, mean, rstd, qkv, kv, o, lse = ctx.saved_tensors
-        cfg: MhaConfig = ctx.cfg
-        B, a, m, d, self_attn = ctx.dims
-        lib = L.load()
-        code = L.dtype_code(cfg.lp_dtype)
-        dev = x.device
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        dmem = torch.empty(B, m, d, device=dev, dtype=torch.float32) if ctx.need_dmem else None
-        g = cfg.grads
-
-        def dst(name, like):
-            return g[name] if g is not None else torch.empty(like.shape, device=dev, dtype=torch.float32)
-
-        d_ln_a, d_ln_b = dst("ln_a", ln_a), dst("ln_b", ln_b)
-        d_w_qkv, d_b_qkv = dst("w_qkv", w_qkv_lp), dst("b_qkv", b_qkv)
-        d_w_o, d_b_o = dst("w_o", w_o_lp), dst("b_o", b_o)
-        ws_lp = torch.empty(lib.mtn_mha_bwd_ws_lp_elems(B, a, m, d, int(self_attn)), device=dev, dtype=cfg.lp_dtype)
-        ws_f32 = torch.empty(lib.mtn_mha_bwd_ws_f32_floats(B, a, m, d), device=dev, dtype=torch.float32)
-        args = L.MhaArgs()
-        args.B, args.a, args.m, args.d, args.h = B, a, m, d, cfg.heads
-        args.self_attn, args.ln_eps = int(self_attn), cfg.eps
-        args.drop_attn = _drop(cfg.p_attn, cfg.salt * 4 + 0, cfg.seed)
-        args.drop_out = _drop(cfg.p_out, cfg.salt * 4 + 1, cfg.seed)
-        args.x, args.mem = x.data_ptr(), L.ptr(mem_lp)
-        args.mask, args.mask_sb, args.mask_sq = L.ptr(mask_u8), ctx.mask_strides[0], ctx.mask_strides[1]
-        args.ln_a, args.ln_b = ln_a.data_ptr(), ln_b.data_ptr()
-        args.w_qkv, args.b_qkv, args.w_o, args.b_o = w_qkv_lp.data_ptr(), b_qkv.data_ptr(), w_o_lp.data_ptr(), b_o.data_ptr()
-        args.w_qkv_t, args.w_o_t = L.ptr(cfg.w_qkv_lpT), L.ptr(cfg.w_o_lpT)
-        args.xn, args.mean, args.rstd = xn.data_ptr(), mean.data_ptr(), rstd.data_ptr()
-        args.qkv, args.kv, args.o, args.lse = qkv.data_ptr(), L.ptr(kv), o.data_ptr(), lse.data_ptr()
-        args.dy, args.dx, args.dmem, args.dmem_accumulate = dy.data_ptr(), dx.data_ptr(), L.ptr(dmem), 0
-        args.d_ln_a, args.d_ln_b = d_ln_a.data_ptr(), d_ln_b.data_ptr()
-        args.d_w_qkv, args.d_b_qkv, args.d_w_o, args.d_b_o = d_w_qkv.data_ptr(), d_b_qkv.data_ptr(), d_w_o.data_ptr(), d_b_o.data_ptr()
-        args.ws_lp, args.ws_f32 = ws_lp.data_ptr(), ws_f32.data_ptr()
-        args.ln_fold = L.ptr(cfg.ln_fold)
-        defer = g is not None and cfg.queue is not None
-        args.defer_param_grads = int(defer)
-        L.check(lib.mtn_mha_sublayer_bwd(code, C.byref(args), L.stream_ptr()))
-        if defer:
-            probs = (L.GemmProblem * 3)()
-            ln = L.LnFinalizeDesc()
-            n = lib.mtn_mha_param_grad_work(code, C.byref(args), probs, C.byref(ln))
-            cfg.queue.add(code, [probs[i] for i in range(n)], ln, [ws_lp, ws_f32, o, xn, mem_lp] if mem_lp is not None else [ws_lp, ws_f32, o, xn])
-        if g is not None:
-            return dx, dmem, None, None, None, None, None, None, None, None, None
-        return dx, dmem, None, None, d_ln_a, d_ln_b, d_w_qkv, d_b_qkv, d_w_o, d_b_o, None
-
-
 @dataclass
 class FfnConfig:
     eps: float = 1e-6
@@ -587,84 +582,182 @@ class FfnConfig:
     ln_fold: Optional[torch.Tensor] = None        # fold vectors of w1 (mtn_ln_fold), float [2 d_ff]
 
 
-class FFNSublayerFn(torch.autograd.Function):
-    """y = x + dropout(w_2(dropout(relu(w_1 LN(x)))))."""
+# The argument structs (L.MhaArgs / L.FfnArgs) are filled HERE and nowhere else: the fields both kinds share by `_pack_fwd` /
+# `_pack_bwd`, the rest by one packer per struct and direction.  A forward packer allocates what the sublayer saves and returns
+# (y, sv): the output and everything backward needs, kept alive beside the struct; a backward packer completes the SAME struct.
+# The single-sublayer Functions and SublayerGroupFn are both callers (one member / several), so a new field is threaded once.
+def _pack_fwd(A, cfg, x, ln_a, ln_b):
+    d = x.size(-1)
+    rows = x.numel() // d
+    y = torch.empty_like(x)
+    xn = torch.empty(rows, d, device=x.device, dtype=cfg.lp_dtype)
+    mean = torch.empty(rows, device=x.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    A.ln_eps, A.drop_out = cfg.eps, _drop(*_out_site(cfg))
+    A.x, A.ln_a, A.ln_b = x.data_ptr(), ln_a.data_ptr(), ln_b.data_ptr()
+    A.y, A.xn, A.mean, A.rstd = y.data_ptr(), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr()
+    A.ln_fold = L.ptr(cfg.ln_fold)              # (read by backward only, like the transposed weights: csrc/sublayer.hip)
+    return y, dict(x=x, xn=xn, mean=mean, rstd=rstd)
+
+
+def _pack_mha_fwd(A, cfg: MhaConfig, x, mem, mem_lp, mask, params, w_qkv=None, w_o=None, kv_ready=None):
+    """params = (ln_a, ln_b, b_qkv, b_o); w_qkv / w_o (fp32) are cast where cfg carries no compute-dtype copies; kv_ready: K|V of
+    the memory, projected ahead (project_memories)."""
+    ln_a, ln_b, b_qkv, b_o = params
+    B, a, d = x.shape
+    self_attn = mem is None
+    m = a if self_attn else mem.size(1)
+    lp, dev = cfg.lp_dtype, x.device
+    if not self_attn and mem_lp is None:
+        mem_lp = cast_to_lp(mem, lp)
+    w_qkv_lp = cfg.w_qkv_lp if cfg.w_qkv_lp is not None else cast_to_lp(w_qkv, lp)
+    w_o_lp = cfg.w_o_lp if cfg.w_o_lp is not None else cast_to_lp(w_o, lp)
+    mask_u8, sb, sq = _mask_u8(mask, B, a, m)
+    y, sv = _pack_fwd(A, cfg, x, ln_a, ln_b)
+    qkv = torch.empty(B * a, 3 * d if self_attn else d, device=dev, dtype=lp)
+    kv = None if self_attn else (kv_ready if kv_ready is not None else torch.empty(B * m, 2 * d, device=dev, dtype=lp))
+    o = torch.empty(B * a, d, device=dev, dtype=lp)
+    lse = torch.empty(2 * B * cfg.heads * a, device=dev, dtype=torch.float32)
+    A.B, A.a, A.m, A.d, A.h, A.self_attn = B, a, m, d, cfg.heads, int(self_attn)
+    A.drop_attn = _drop(cfg.p_attn, cfg.salt * 4 + 0, cfg.seed)
+    A.mem, A.mask, A.mask_sb, A.mask_sq = L.ptr(mem_lp), L.ptr(mask_u8), sb, sq
+    A.w_qkv, A.b_qkv, A.w_o, A.b_o = w_qkv_lp.data_ptr(), b_qkv.data_ptr(), w_o_lp.data_ptr(), b_o.data_ptr()
+    A.w_qkv_t, A.w_o_t = L.ptr(cfg.w_qkv_lpT), L.ptr(cfg.w_o_lpT)
+    A.qkv, A.kv, A.o, A.lse = qkv.data_ptr(), L.ptr(kv), o.data_ptr(), lse.data_ptr()
+    A.kv_ready = int((not self_attn) and kv_ready is not None)
+    sv.update(mem_lp=mem_lp, mask=mask_u8, qkv=qkv, kv=kv, o=o, lse=lse, need_dmem=(not self_attn) and mem.requires_grad,
+              like=dict(ln_a=ln_a, ln_b=ln_b, w_qkv=w_qkv_lp, b_qkv=b_qkv, w_o=w_o_lp, b_o=b_o))
+    return y, sv
+
+
+def _pack_ffn_fwd(A, cfg: FfnConfig, x, params, w1=None, w2=None, want_lp=False):
+    """params = (ln_a, ln_b, b1, b2); want_lp: the output also leaves in the compute dtype (sv['y_lp'])."""
+    ln_a, ln_b, b1, b2 = params
+    lp = cfg.lp_dtype
+    w1_lp = cfg.w1_lp if cfg.w1_lp is not None else cast_to_lp(w1, lp)
+    w2_lp = cfg.w2_lp if cfg.w2_lp is not None else cast_to_lp(w2, lp)
+    y, sv = _pack_fwd(A, cfg, x, ln_a, ln_b)
+    A.rows, A.d, A.d_ff = sv["xn"].size(0), x.size(-1), w1_lp.size(0)
+    hid = torch.empty(A.rows, A.d_ff, device=x.device, dtype=lp)
+    y_lp = torch.empty(y.shape, device=x.device, dtype=lp) if want_lp and lp != torch.float32 else None
+    A.drop_hidden = _drop(cfg.p_hidden, cfg.salt * 4 + 2, cfg.seed)
+    A.w1, A.b1, A.w2, A.b2 = w1_lp.data_ptr(), b1.data_ptr(), w2_lp.data_ptr(), b2.data_ptr()
+    A.w1_t, A.w2_t = L.ptr(cfg.w1_lpT), L.ptr(cfg.w2_lpT)
+    A.hid, A.y_lp = hid.data_ptr(), L.ptr(y_lp)
+    sv.update(hid=hid, y_lp=y_lp, like=dict(ln_a=ln_a, ln_b=ln_b, w1=w1_lp, b1=b1, w2=w2_lp, b2=b2))
+    return y, sv
+
+
+def _dests(cfg, sv):
+    """fp32 destinations of the parameter gradients: the caller's (cfg.grads), else fresh ones to return through autograd."""
+    if cfg.grads is not None:
+        return cfg.grads
+    return {k: torch.empty(t.shape, device=t.device, dtype=torch.float32) for k, t in sv["like"].items()}
+
+
+def _ffn_bwd_ws_lp_elems(rows, d, ff):
+    return rows * d + rows * ff               # dyl [rows,d] | dh [rows,d_ff] (csrc/sublayer.hip ffn_ws)
+
+
+def _pack_bwd(A, cfg, dy, dx, g, ws_lp_elems, ws_f32_floats, defer, ready, nxt):
+    """ready: this sublayer's dy, already through its output dropout in the compute dtype (HandOff.claim); nxt: the HandOff of the
+    sublayer that produced our input, on which our dx has just been offered.  -> tensors the deferred work reads."""
+    ws_lp = torch.empty(ws_lp_elems, device=dx.device, dtype=cfg.lp_dtype)
+    ws_f32 = torch.empty(ws_f32_floats, device=dx.device, dtype=torch.float32)
+    A.dy, A.dx, A.d_ln_a, A.d_ln_b = dy.data_ptr(), dx.data_ptr(), g["ln_a"].data_ptr(), g["ln_b"].data_ptr()
+    A.ws_lp, A.ws_f32, A.defer_param_grads = ws_lp.data_ptr(), ws_f32.data_ptr(), int(defer)
+    A.dyl_ready, A.next_dyl = L.ptr(ready), L.ptr(nxt.dyl if nxt is not None else None)
+    if nxt is not None:
+        A.next_drop = nxt.drop()
+    return [dy, ws_lp, ws_f32] + ([ready] if ready is not None else [])
+
+
+def _pack_mha_bwd(A, cfg, sv, dy, dx, g, defer, dmem=None, accumulate=0, mem_nxt=None, ready=None, nxt=None):
+    """dmem: fp32 destination of the memory's gradient (added to when `accumulate`); mem_nxt: the HandOff of the memory's producer,
+    on which dmem has just been offered."""
+    lib = L.load()
+    B, a, m, d = A.B, A.a, A.m, A.d
+    keep = _pack_bwd(A, cfg, dy, dx, g, lib.mtn_mha_bwd_ws_lp_elems(B, a, m, d, A.self_attn), lib.mtn_mha_bwd_ws_f32_floats(B, a, m, d),
+                     defer, ready, nxt)
+    A.dmem, A.dmem_accumulate = L.ptr(dmem), accumulate
+    A.dmem_lp = L.ptr(mem_nxt.dyl if mem_nxt is not None else None)
+    if mem_nxt is not None:
+        A.dmem_lp_drop = mem_nxt.drop()
+    A.d_w_qkv, A.d_b_qkv, A.d_w_o, A.d_b_o = g["w_qkv"].data_ptr(), g["b_qkv"].data_ptr(), g["w_o"].data_ptr(), g["b_o"].data_ptr()
+    return keep + [sv["o"], sv["xn"]] + ([sv["mem_lp"]] if sv["mem_lp"] is not None else [])
+
+
+def _pack_ffn_bwd(A, cfg, sv, dy, dx, g, defer, ready=None, nxt=None):
+    rows, d, ff = A.rows, A.d, A.d_ff
+    keep = _pack_bwd(A, cfg, dy, dx, g, _ffn_bwd_ws_lp_elems(rows, d, ff), L.load().mtn_ffn_bwd_ws_f32_floats(rows, d, ff), defer, ready, nxt)
+    A.d_w1, A.d_b1, A.d_w2, A.d_b2 = g["w1"].data_ptr(), g["b1"].data_ptr(), g["w2"].data_ptr(), g["b2"].data_ptr()
+    return keep + [sv["hid"], sv["xn"]]
+
+
+def _queue_param_grads(queue, code, A, keep):
+    """The dW/db GEMM problems and the LayerNorm finalize of one backward-packed struct -> the queue (nothing launched)."""
+    lib = L.load()
+    work = lib.mtn_mha_param_grad_work if isinstance(A, L.MhaArgs) else lib.mtn_ffn_param_grad_work
+    probs = (L.GemmProblem * 3)()
+    ln = L.LnFinalizeDesc()
+    n = work(code, C.byref(A), probs, C.byref(ln))
+    queue.add(code, [probs[i] for i in range(n)], ln, keep)
+
+
+class MHASublayerFn(torch.autograd.Function):
+    """y = x + dropout(MHA(LN(x), mem, mem, mask)).  mem=None -> self-attention (key=value=LN(x), mtn.py:183,209).
+    Parameter gradients: returned through autograd (cfg.grads None), written at once to cfg.grads, or, with cfg.queue, deferred."""
 
     @staticmethod
-    def forward(ctx, x, ln_a, ln_b, w1, b1, w2, b2, cfg: FfnConfig):
-        _require_cuda(x, ln_a, w1)
-        lib = L.load()
-        x = x.contiguous()
-        d = x.size(-1)
-        rows = x.numel() // d
-        ff = w1.size(0)
-        lp = cfg.lp_dtype
-        code = L.dtype_code(lp)
-        dev = x.device
-        w1_lp = cfg.w1_lp if cfg.w1_lp is not None else cast_to_lp(w1, lp)
-        w2_lp = cfg.w2_lp if cfg.w2_lp is not None else cast_to_lp(w2, lp)
-        y = torch.empty_like(x)
-        xn = torch.empty(rows, d, device=dev, dtype=lp)
-        mean = torch.empty(rows, device=dev, dtype=torch.float32)
-        rstd = torch.empty_like(mean)
-        hid = torch.empty(rows, ff, device=dev, dtype=lp)
-        args = L.FfnArgs()
-        args.rows, args.d, args.d_ff, args.ln_eps = rows, d, ff, cfg.eps
-        args.drop_hidden = _drop(cfg.p_hidden, cfg.salt * 4 + 2, cfg.seed)
-        args.drop_out = _drop(cfg.p_out, cfg.salt * 4 + 1, cfg.seed)
-        args.x, args.ln_a, args.ln_b = x.data_ptr(), ln_a.data_ptr(), ln_b.data_ptr()
-        args.w1, args.b1, args.w2, args.b2 = w1_lp.data_ptr(), b1.data_ptr(), w2_lp.data_ptr(), b2.data_ptr()
-        args.y, args.xn, args.mean, args.rstd, args.hid = y.data_ptr(), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), hid.data_ptr()
-        L.check(lib.mtn_ffn_sublayer_fwd(code, C.byref(args), L.stream_ptr()))
-        ctx.save_for_backward(x, ln_a, ln_b, w1_lp, b1, w2_lp, b2, xn, mean, rstd, hid)
-        ctx.cfg = cfg
+    def forward(ctx, x, mem, mem_lp, mask, ln_a, ln_b, w_qkv, b_qkv, w_o, b_o, cfg: MhaConfig):
+        _require_cuda(x, mem, ln_a, w_qkv)
+        ctx.cfg, ctx.args = cfg, L.MhaArgs()
+        y, ctx.sv = _pack_mha_fwd(ctx.args, cfg, x.contiguous(), mem, mem_lp, mask, (ln_a, ln_b, b_qkv, b_o), w_qkv, w_o)
+        L.check(L.load().mtn_mha_sublayer_fwd(L.dtype_code(cfg.lp_dtype), C.byref(ctx.args), L.stream_ptr()))
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, ln_a, ln_b, w1_lp, b1, w2_lp, b2, xn, mean, rstd, hid = ctx.saved_tensors
-        cfg: FfnConfig = ctx.cfg
-        lib = L.load()
+        cfg, A, sv = ctx.cfg, ctx.args, ctx.sv
         code = L.dtype_code(cfg.lp_dtype)
-        dev = x.device
-        d = x.size(-1)
-        rows = x.numel() // d
-        ff = w1_lp.size(0)
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        g = cfg.grads
-
-        def dst(name, like):
-            return g[name] if g is not None else torch.empty(like.shape, device=dev, dtype=torch.float32)
-
-        d_ln_a, d_ln_b = dst("ln_a", ln_a), dst("ln_b", ln_b)
-        d_w1, d_b1, d_w2, d_b2 = dst("w1", w1_lp), dst("b1", b1), dst("w2", w2_lp), dst("b2", b2)
-        ws_lp = torch.empty(rows * d + rows * ff, device=dev, dtype=cfg.lp_dtype)
-        ws_f32 = torch.empty(lib.mtn_ffn_bwd_ws_f32_floats(rows, d, ff), device=dev, dtype=torch.float32)
-        args = L.FfnArgs()
-        args.rows, args.d, args.d_ff, args.ln_eps = rows, d, ff, cfg.eps
-        args.drop_hidden = _drop(cfg.p_hidden, cfg.salt * 4 + 2, cfg.seed)
-        args.drop_out = _drop(cfg.p_out, cfg.salt * 4 + 1, cfg.seed)
-        args.x, args.ln_a, args.ln_b = x.data_ptr(), ln_a.data_ptr(), ln_b.data_ptr()
-        args.w1, args.b1, args.w2, args.b2 = w1_lp.data_ptr(), b1.data_ptr(), w2_lp.data_ptr(), b2.data_ptr()
-        args.w1_t, args.w2_t = L.ptr(cfg.w1_lpT), L.ptr(cfg.w2_lpT)
-        args.xn, args.mean, args.rstd, args.hid = xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), hid.data_ptr()
-        args.dy, args.dx = dy.data_ptr(), dx.data_ptr()
-        args.d_ln_a, args.d_ln_b = d_ln_a.data_ptr(), d_ln_b.data_ptr()
-        args.d_w1, args.d_b1, args.d_w2, args.d_b2 = d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(), d_b2.data_ptr()
-        args.ws_lp, args.ws_f32 = ws_lp.data_ptr(), ws_f32.data_ptr()
-        args.ln_fold = L.ptr(cfg.ln_fold)
-        defer = g is not None and cfg.queue is not None
-        args.defer_param_grads = int(defer)
-        L.check(lib.mtn_ffn_sublayer_bwd(code, C.byref(args), L.stream_ptr()))
+        dx = torch.empty_like(sv["x"])
+        dmem = torch.empty(A.B, A.m, A.d, device=dx.device, dtype=torch.float32) if sv["need_dmem"] else None
+        g = _dests(cfg, sv)
+        defer = cfg.grads is not None and cfg.queue is not None
+        keep = _pack_mha_bwd(A, cfg, sv, dy.contiguous(), dx, g, defer, dmem)
+        L.check(L.load().mtn_mha_sublayer_bwd(code, C.byref(A), L.stream_ptr()))
         if defer:
-            probs = (L.GemmProblem * 2)()
-            ln = L.LnFinalizeDesc()
-            n = lib.mtn_ffn_param_grad_work(code, C.byref(args), probs, C.byref(ln))
-            cfg.queue.add(code, [probs[i] for i in range(n)], ln, [ws_lp, ws_f32, hid, xn])
-        if g is not None:
+            _queue_param_grads(cfg.queue, code, A, keep)
+        if cfg.grads is not None:
+            return dx, dmem, None, None, None, None, None, None, None, None, None
+        return dx, dmem, None, None, g["ln_a"], g["ln_b"], g["w_qkv"], g["b_qkv"], g["w_o"], g["b_o"], None
+
+
+class FFNSublayerFn(torch.autograd.Function):
+    """y = x + dropout(w_2(dropout(relu(w_1 LN(x))))).  Parameter gradients as for MHASublayerFn."""
+
+    @staticmethod
+    def forward(ctx, x, ln_a, ln_b, w1, b1, w2, b2, cfg: FfnConfig):
+        _require_cuda(x, ln_a, w1)
+        ctx.cfg, ctx.args = cfg, L.FfnArgs()
+        y, ctx.sv = _pack_ffn_fwd(ctx.args, cfg, x.contiguous(), (ln_a, ln_b, b1, b2), w1, w2)
+        L.check(L.load().mtn_ffn_sublayer_fwd(L.dtype_code(cfg.lp_dtype), C.byref(ctx.args), L.stream_ptr()))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        cfg, A, sv = ctx.cfg, ctx.args, ctx.sv
+        code = L.dtype_code(cfg.lp_dtype)
+        dx = torch.empty_like(sv["x"])
+        g = _dests(cfg, sv)
+        defer = cfg.grads is not None and cfg.queue is not None
+        keep = _pack_ffn_bwd(A, cfg, sv, dy.contiguous(), dx, g, defer)
+        L.check(L.load().mtn_ffn_sublayer_bwd(code, C.byref(A), L.stream_ptr()))
+        if defer:
+            _queue_param_grads(cfg.queue, code, A, keep)
+        if cfg.grads is not None:
             return dx, None, None, None, None, None, None, None
-        return dx, d_ln_a, d_ln_b, d_w1, d_b1, d_w2, d_b2, None
+        return dx, g["ln_a"], g["ln_b"], g["w1"], g["b1"], g["w2"], g["b2"], None
 
 
 # ------------------------------------------------------------------------------------------ lockstep sublayer groups
@@ -677,10 +770,10 @@ class GroupMember:
     params: tuple
     mask: Optional[torch.Tensor] = None
     mem_lp: Optional[torch.Tensor] = None
-    # gradient hand-off along a chain of sublayers (see include/mtn_hip.h, dyl_ready / next_dyl): `holder` travels with this
+    # gradient hand-off along a chain of sublayers (HandOff; include/mtn_hip.h, dyl_ready / next_dyl): `holder` travels with this
     # member's OUTPUT tensor to the sublayer that consumes it; `feeds` is the holder found on this member's INPUT tensor.
-    holder: Optional[dict] = None
-    feeds: Optional[dict] = None
+    holder: Optional[HandOff] = None
+    feeds: Optional[HandOff] = None
     kv_ready: Optional[torch.Tensor] = None     # K|V of a constant memory, projected ahead of the layer loop (project_memories)
     want_lp: bool = False                       # 'ffn': also write the output in the compute dtype (-> out_lp): it is attended as raw memory
     out_lp: Optional[torch.Tensor] = None
@@ -693,206 +786,76 @@ class SublayerGroupFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, members, *tensors):
-        lib = L.load()
         xs = [t.contiguous() for t in tensors[0::2]]
-        mems = list(tensors[1::2])
         _require_cuda(*xs)
-        dev = xs[0].device
-        lp = members[0].cfg.lp_dtype
-        code = L.dtype_code(lp)
+        code = L.dtype_code(members[0].cfg.lp_dtype)
         n_mha = sum(1 for m in members if m.kind == "mha")
         n_ffn = len(members) - n_mha
         mha_args = (L.MhaArgs * max(1, n_mha))()
         ffn_args = (L.FfnArgs * max(1, n_ffn))()
-        saved, ys = [], []
-        im = jf = 0
-        xaccs = []
-        for x_orig in tensors[0::2]:
-            # an input that an EARLIER sublayer already attends as memory (an auto-encoder output feeds the next layer's chain
-            # and is the memory of x's attention): both gradients meet in one buffer instead of an autograd add
-            xg = getattr(x_orig, "_mtn_gacc", None) if (_XACC and x_orig.requires_grad) else None     # (grad mode is off inside forward)
-            if xg is not None:
-                xg["remaining"] += 1
-            xaccs.append(xg)
-        for mem_t, x, mb in zip(mems, xs, members):
-            cfg = mb.cfg
-            ln_a, ln_b = mb.params[0], mb.params[1]
-            y = torch.empty_like(x)
-            d = x.size(-1)
+        # an input that an EARLIER sublayer already attends as memory (an auto-encoder output feeds the next layer's chain
+        # and is the memory of x's attention): both gradients meet in one buffer instead of an autograd add
+        xaccs = [GradMeet.join(t) if (_XACC and t.requires_grad) else None for t in tensors[0::2]]     # (grad mode is off inside forward)
+        slots = {"mha": iter(mha_args), "ffn": iter(ffn_args)}
+        args, saved, ys = [], [], []
+        for mem_t, x, mb in zip(tensors[1::2], xs, members):
+            A = next(slots[mb.kind])
             if mb.kind == "mha":
-                B, a, _ = x.shape
-                self_attn = mem_t is None
-                m = a if self_attn else mem_t.size(1)
-                mem_lp = mb.mem_lp
-                if not self_attn and mem_lp is None:
-                    mem_lp = cast_to_lp(mem_t, lp)
-                mask_u8, sb, sq = _mask_u8(mb.mask, B, a, m)
-                xn = torch.empty(B * a, d, device=dev, dtype=lp)
-                mean = torch.empty(B * a, device=dev, dtype=torch.float32)
-                rstd = torch.empty_like(mean)
-                qkv = torch.empty(B * a, 3 * d if self_attn else d, device=dev, dtype=lp)
-                kv = None if self_attn else (mb.kv_ready if mb.kv_ready is not None else torch.empty(B * m, 2 * d, device=dev, dtype=lp))
-                o = torch.empty(B * a, d, device=dev, dtype=lp)
-                lse = torch.empty(2 * B * cfg.heads * a, device=dev, dtype=torch.float32)
-                A = mha_args[im]; im += 1
-                A.kv_ready = int((not self_attn) and mb.kv_ready is not None)
-                A.B, A.a, A.m, A.d, A.h = B, a, m, d, cfg.heads
-                A.self_attn, A.ln_eps = int(self_attn), cfg.eps
-                A.drop_attn = _drop(cfg.p_attn, cfg.salt * 4 + 0, cfg.seed)
-                A.drop_out = _drop(cfg.p_out, cfg.salt * 4 + 1, cfg.seed)
-                A.x, A.mem = x.data_ptr(), L.ptr(mem_lp)
-                A.mask, A.mask_sb, A.mask_sq = L.ptr(mask_u8), sb, sq
-                A.ln_a, A.ln_b = ln_a.data_ptr(), ln_b.data_ptr()
-                A.w_qkv, A.b_qkv, A.w_o, A.b_o = cfg.w_qkv_lp.data_ptr(), mb.params[2].data_ptr(), cfg.w_o_lp.data_ptr(), mb.params[3].data_ptr()
-                A.w_qkv_t, A.w_o_t = L.ptr(cfg.w_qkv_lpT), L.ptr(cfg.w_o_lpT)
-                A.y, A.xn, A.mean, A.rstd = y.data_ptr(), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr()
-                A.qkv, A.kv, A.o, A.lse = qkv.data_ptr(), L.ptr(kv), o.data_ptr(), lse.data_ptr()
-                A.ln_fold = L.ptr(cfg.ln_fold)
-                need_dmem = (not self_attn) and mem_t.requires_grad
-                gacc = None
-                if need_dmem:          # a memory serves every layer: its gradient is accumulated in place by the dmem GEMMs
-                    gacc = getattr(mem_t, "_mtn_gacc", None)
-                    if gacc is None:
-                        gacc = {"buf": None, "remaining": 0}
-                        mem_t._mtn_gacc = gacc
-                    gacc["remaining"] += 1
-                saved.append(dict(x=x, mem_lp=mem_lp, mask=mask_u8, xn=xn, mean=mean, rstd=rstd, qkv=qkv, kv=kv, o=o, lse=lse,
-                                  need_dmem=need_dmem, gacc=gacc, m=m,
-                                  mem_next=getattr(mem_t, "_mtn_next", None) if need_dmem else None))   # the memory's producer (hand-off holder)
+                y, sv = _pack_mha_fwd(A, mb.cfg, x, mem_t, mb.mem_lp, mb.mask, mb.params, kv_ready=mb.kv_ready)
+                if sv["need_dmem"]:          # a memory serves every layer: its gradient is accumulated in place by the dmem GEMMs
+                    sv["gacc"] = GradMeet.join(mem_t, create=True)
+                    sv["mem_next"] = getattr(mem_t, "_mtn_next", None)     # the memory's producer (hand-off holder)
             else:
-                rows = x.numel() // d
-                ff = cfg.w1_lp.size(0)
-                xn = torch.empty(rows, d, device=dev, dtype=lp)
-                mean = torch.empty(rows, device=dev, dtype=torch.float32)
-                rstd = torch.empty_like(mean)
-                hid = torch.empty(rows, ff, device=dev, dtype=lp)
-                A = ffn_args[jf]; jf += 1
-                A.rows, A.d, A.d_ff, A.ln_eps = rows, d, ff, cfg.eps
-                A.drop_hidden = _drop(cfg.p_hidden, cfg.salt * 4 + 2, cfg.seed)
-                A.drop_out = _drop(cfg.p_out, cfg.salt * 4 + 1, cfg.seed)
-                A.x, A.ln_a, A.ln_b = x.data_ptr(), ln_a.data_ptr(), ln_b.data_ptr()
-                A.w1, A.b1, A.w2, A.b2 = cfg.w1_lp.data_ptr(), mb.params[2].data_ptr(), cfg.w2_lp.data_ptr(), mb.params[3].data_ptr()
-                A.w1_t, A.w2_t = L.ptr(cfg.w1_lpT), L.ptr(cfg.w2_lpT)
-                A.y, A.xn, A.mean, A.rstd, A.hid = y.data_ptr(), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), hid.data_ptr()
-                A.ln_fold = L.ptr(cfg.ln_fold)
-                if mb.want_lp and lp != torch.float32:
-                    mb.out_lp = torch.empty(y.shape, device=dev, dtype=lp)
-                    A.y_lp = mb.out_lp.data_ptr()
-                saved.append(dict(x=x, xn=xn, mean=mean, rstd=rstd, hid=hid))
-            ys.append(y)
-        L.check(lib.mtn_sublayer_group_fwd(code, n_mha, mha_args, n_ffn, ffn_args, L.stream_ptr()))
-        ctx.members, ctx.saved_bufs, ctx.code = members, saved, code
-        ctx.xaccs = xaccs
-        ctx.mha_args, ctx.ffn_args, ctx.n_mha, ctx.n_ffn = mha_args, ffn_args, n_mha, n_ffn
+                y, sv = _pack_ffn_fwd(A, mb.cfg, x, mb.params, want_lp=mb.want_lp)
+                mb.out_lp = sv["y_lp"]
+            args.append(A); saved.append(sv); ys.append(y)
+        L.check(L.load().mtn_sublayer_group_fwd(code, n_mha, mha_args, n_ffn, ffn_args, L.stream_ptr()))
+        ctx.members, ctx.saved_bufs, ctx.code, ctx.xaccs = members, saved, code, xaccs
+        ctx.args, ctx.mha_args, ctx.ffn_args, ctx.n_mha, ctx.n_ffn = args, mha_args, ffn_args, n_mha, n_ffn
         return tuple(ys)
 
     @staticmethod
     def backward(ctx, *dys):
-        lib = L.load()
-        members, saved, code = ctx.members, ctx.saved_bufs, ctx.code
-        mha_args, ffn_args = ctx.mha_args, ctx.ffn_args      # forward pointers are still valid (buffers are kept alive in `saved`)
-        grads_out, keep_all = [], []
-        im = jf = 0
-        work = []
+        code = ctx.code
+        queue = ctx.members[0].cfg.queue
+        grads_out, work = [], []
         post = []                    # (buffer, dx) pairs to sum after the launch: input-role accumulators that were not first
-        for dy, mb, sv, xg in zip(dys, members, saved, ctx.xaccs):
-            cfg, g = mb.cfg, mb.cfg.grads
+        for dy, mb, A, sv, xg in zip(dys, ctx.members, ctx.args, ctx.saved_bufs, ctx.xaccs):      # (forward pointers are still valid: `sv`)
+            cfg = mb.cfg
             x = sv["x"]
-            dev = x.device
             dy = dy.contiguous() if dy is not None else torch.zeros_like(x)
             dx = torch.empty_like(x)
-            dx_ret = dx
-            if xg is not None:           # see forward: the gradient of this input is collected in a shared buffer
-                xg["remaining"] -= 1
-                if xg["buf"] is None and xg["remaining"] > 0:
-                    xg["buf"], dx_ret = dx, None                      # first writer: the memory-role users accumulate into our dx
-                elif xg["buf"] is not None:
-                    buf = xg["buf"]
-                    post.append((buf, dx))
-                    dx_ret = None
-                    if xg["remaining"] == 0:
-                        dx_ret, xg["buf"] = buf, None
+            dx_ret = dx if xg is None else xg.settle(dx, post)       # see forward: the gradient of this input is collected in a shared buffer
             # hand-off, consumer side: the sublayer that ran before us in backward already wrote dy through OUR output dropout
-            ready = None
-            h = mb.holder
-            if h is not None and h.get("dyl") is not None:
-                # valid only if dy IS the dx that was handed off, untouched: same storage address, same shape, and the version
-                # counter it had (autograd sums gradients in place with add_, which bumps it; any tensor derived from dx — a sum,
-                # a clone — is allocated while dx is still alive, so it cannot sit at dx's address).  The dx tensor itself is not
-                # held: a leaf's .grad may then take it over without a copy (layer-segmented backward).
-                if h["dx_ptr"] == dy.data_ptr() and dy._version == h["ver"] and tuple(h["shape"]) == tuple(dy.shape):
-                    ready = h["dyl"]
-            if h is not None:
-                h["dyl"] = h["dx_ptr"] = None
+            ready = mb.holder.claim(dy) if mb.holder is not None else None
             # producer side: write our dx also as the next sublayer's masked compute-dtype dy
-            nxt = None
-            f = mb.feeds
-            if f is not None and f.get("lp") == cfg.lp_dtype and xg is None:
-                nxt = torch.empty(x.shape, device=dev, dtype=cfg.lp_dtype)
-                f["dyl"], f["dx_ptr"], f["ver"], f["shape"] = nxt, dx.data_ptr(), dx._version, dx.shape
+            nxt = mb.feeds if (mb.feeds is not None and mb.feeds.lp == cfg.lp_dtype and xg is None) else None
+            if nxt is not None:
+                nxt.offer(dx, cfg.lp_dtype)
             if mb.kind == "mha":
-                A = mha_args[im]; im += 1
-                B, a, d, m = A.B, A.a, A.d, sv["m"]
-                dmem, dmem_ret, accumulate = None, None, 0
-                A.dmem_lp = None
+                dmem = dmem_ret = mem_nxt = None
+                accumulate = 0
                 if sv["need_dmem"]:
-                    gacc = sv["gacc"]
-                    if gacc["buf"] is None:
-                        gacc["buf"] = torch.empty(B, m, d, device=dev, dtype=torch.float32)
-                    else:
-                        accumulate = 1
-                    dmem = gacc["buf"]
-                    gacc["remaining"] -= 1
-                    if gacc["remaining"] == 0:       # last user (first in forward order): hand the sum to autograd once
-                        dmem_ret, gacc["buf"] = dmem, None
+                    dmem, accumulate, last = sv["gacc"].buffer((A.B, A.m, A.d), x.device)
+                    if last:                         # last user (first in forward order): hand the sum to autograd once
+                        dmem_ret = dmem
                         # ... and, through the dmem GEMM's epilogue, to the sublayer that produced the memory: the sum once
                         # more, through that sublayer's output dropout, in the compute dtype (its backward then needs no cast)
-                        fm = sv.get("mem_next")
-                        if fm is not None and fm.get("lp") == cfg.lp_dtype and cfg.lp_dtype != torch.float32 and _HANDOFF_MEM:
-                            dmem_lp = torch.empty(dmem.shape, device=dev, dtype=cfg.lp_dtype)
-                            fm["dyl"], fm["dx_ptr"], fm["ver"], fm["shape"] = dmem_lp, dmem.data_ptr(), dmem._version, dmem.shape
-                            A.dmem_lp, A.dmem_lp_drop = dmem_lp.data_ptr(), _drop(fm["p"], fm["salt"], fm["seed"])
-                ws_lp = torch.empty(lib.mtn_mha_bwd_ws_lp_elems(B, a, m, d, A.self_attn), device=dev, dtype=cfg.lp_dtype)
-                ws_f32 = torch.empty(lib.mtn_mha_bwd_ws_f32_floats(B, a, m, d), device=dev, dtype=torch.float32)
-                A.dy, A.dx, A.dmem, A.dmem_accumulate = dy.data_ptr(), dx.data_ptr(), L.ptr(dmem), accumulate
-                A.d_ln_a, A.d_ln_b = g["ln_a"].data_ptr(), g["ln_b"].data_ptr()
-                A.d_w_qkv, A.d_b_qkv, A.d_w_o, A.d_b_o = g["w_qkv"].data_ptr(), g["b_qkv"].data_ptr(), g["w_o"].data_ptr(), g["b_o"].data_ptr()
-                A.ws_lp, A.ws_f32, A.defer_param_grads = ws_lp.data_ptr(), ws_f32.data_ptr(), 1
-                A.ln_fold = L.ptr(cfg.ln_fold)
-                A.dyl_ready, A.next_dyl = L.ptr(ready), L.ptr(nxt)
-                if nxt is not None:
-                    A.next_drop = _drop(f["p"], f["salt"], f["seed"])
+                        fm = sv["mem_next"]
+                        if fm is not None and fm.lp == cfg.lp_dtype and cfg.lp_dtype != torch.float32 and _HANDOFF_MEM:
+                            mem_nxt = fm
+                            fm.offer(dmem, cfg.lp_dtype)
+                keep = _pack_mha_bwd(A, cfg, sv, dy, dx, cfg.grads, 1, dmem, accumulate, mem_nxt, ready, nxt)
                 grads_out += [dx_ret, dmem_ret]
-                keep = [dy, ws_lp, ws_f32, sv["o"], sv["xn"]] + ([sv["mem_lp"]] if sv["mem_lp"] is not None else []) + ([ready] if ready is not None else [])
-                work.append(("mha", A, keep))
             else:
-                A = ffn_args[jf]; jf += 1
-                rows, d, ff = A.rows, A.d, A.d_ff
-                ws_lp = torch.empty(rows * d + rows * ff, device=dev, dtype=cfg.lp_dtype)
-                ws_f32 = torch.empty(lib.mtn_ffn_bwd_ws_f32_floats(rows, d, ff), device=dev, dtype=torch.float32)
-                A.dy, A.dx = dy.data_ptr(), dx.data_ptr()
-                A.d_ln_a, A.d_ln_b = g["ln_a"].data_ptr(), g["ln_b"].data_ptr()
-                A.d_w1, A.d_b1, A.d_w2, A.d_b2 = g["w1"].data_ptr(), g["b1"].data_ptr(), g["w2"].data_ptr(), g["b2"].data_ptr()
-                A.ws_lp, A.ws_f32, A.defer_param_grads = ws_lp.data_ptr(), ws_f32.data_ptr(), 1
-                A.ln_fold = L.ptr(cfg.ln_fold)
-                A.dyl_ready, A.next_dyl = L.ptr(ready), L.ptr(nxt)
-                if nxt is not None:
-                    A.next_drop = _drop(f["p"], f["salt"], f["seed"])
+                keep = _pack_ffn_bwd(A, cfg, sv, dy, dx, cfg.grads, 1, ready, nxt)
                 grads_out += [dx_ret, None]
-                keep = [dy, ws_lp, ws_f32, sv["hid"], sv["xn"]] + ([ready] if ready is not None else [])
-                work.append(("ffn", A, keep))
-            keep_all.append(dy)
-        L.check(lib.mtn_sublayer_group_bwd(code, ctx.n_mha, mha_args, ctx.n_ffn, ffn_args, L.stream_ptr()))
+            work.append((A, keep))
+        L.check(L.load().mtn_sublayer_group_bwd(code, ctx.n_mha, ctx.mha_args, ctx.n_ffn, ctx.ffn_args, L.stream_ptr()))
         for buf, dxp in post:
             buf.add_(dxp)
-        for kind, A, keep in work:
-            probs = (L.GemmProblem * 3)()
-            ln = L.LnFinalizeDesc()
-            if kind == "mha":
-                n = lib.mtn_mha_param_grad_work(code, C.byref(A), probs, C.byref(ln))
-            else:
-                n = lib.mtn_ffn_param_grad_work(code, C.byref(A), probs, C.byref(ln))
-            members[0].cfg.queue.add(code, [probs[i] for i in range(n)], ln, keep)
+        for A, keep in work:
+            _queue_param_grads(queue, code, A, keep)
         return (None, *grads_out)
 
 

@@ -519,23 +519,21 @@ class TrainStep:
         def bwd(outs, leaves):
             # An auto-encoder output is BOTH the next layer's chain input (across the cut: its gradient arrives as leaf.grad) and the
             # memory of x's attention inside this layer.  In the monolithic graph the two gradients meet in one buffer (ops.py, the
-            # `_mtn_gacc` protocol: first writer = the chain input's dx, the memory-gradient GEMM accumulates into it); across a cut
+            # ops.GradMeet: first writer = the chain input's dx, the memory-gradient GEMM accumulates into it); across a cut
             # autograd would ADD them (12 torch add launches per step, 112 us at batch 64: profiles/r04_x_*).  Here the leaf's gradient
-            # is handed to that buffer slot instead of to autograd: same summation order as the monolithic step, no add launch.
+            # seeds that meeting point instead of going to autograd: same summation order as the monolithic step, no add launch.
             roots, grads = [], []
             for o, l in zip(outs, leaves):
                 if l.grad is None:
                     continue
                 ga = getattr(o, "_mtn_gacc", None)
-                if (_CUT_GACC and ga is not None and ga["remaining"] > 0 and ga["buf"] is None and l.grad.is_contiguous()
-                        and l.grad.dtype == torch.float32 and l.grad.shape == o.shape):
-                    ga["buf"] = l.grad
-                    # the next layer handed THIS tensor (its dx, through the producer's output dropout, compute dtype) to the producer
-                    # of `o` as a ready-made dy, valid while the tensor is untouched — it is about to be accumulated into: withdraw
-                    # it (in bf16 mode the memory-gradient GEMM's epilogue hands the full sum over again; fp32 mode casts it)
+                if _CUT_GACC and ga is not None and ga.seed(l.grad, o.shape):
+                    # the next layer offered THIS tensor (its dx, through the producer's output dropout, compute dtype) to the producer
+                    # of `o` as a ready-made dy (ops.HandOff), valid while the tensor is untouched — it is about to be accumulated into:
+                    # withdraw it (in bf16 mode the memory-gradient GEMM's epilogue hands the full sum over again; fp32 mode casts it)
                     h = getattr(o, "_mtn_next", None)
-                    if h is not None and h.get("dx_ptr") == l.grad.data_ptr():
-                        h["dyl"] = h["dx_ptr"] = None
+                    if h is not None:
+                        h.withdraw(l.grad.data_ptr())
                     continue
                 roots.append(o); grads.append(l.grad)
             if roots:

@@ -46,9 +46,28 @@ def raw_batch(c, seed=1, **kw):
 
 
 # ------------------------------------------------------------------------------------------ fused sublayers
+# The three ways a single sublayer delivers its parameter gradients (ops.MHASublayerFn / FFNSublayerFn): returned through autograd,
+# written at once into fp32 destinations, deferred through a ParamGradQueue into the same destinations.
+DELIVERY = ["returned", "written", "queued"]
+
+
+def _delivery(ops, mode, params):
+    """params: name -> device parameter.  -> (cfg.grads, cfg.queue, collect): collect() = name -> the delivered gradient.  The
+    destinations start as NaN: a gradient that is never written fails the comparison."""
+    if mode == "returned":
+        return None, None, lambda: {k: p.grad for k, p in params.items()}
+    dests = {k: torch.full_like(p, float("nan"), requires_grad=False) for k, p in params.items()}
+
+    def collect():
+        assert all(p.grad is None for p in params.values()), "a gradient went through autograd although a destination was set"
+        return dests
+    return dests, (ops.ParamGradQueue() if mode == "queued" else None), collect
+
+
+@pytest.mark.parametrize("mode", DELIVERY)
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("cross", [False, True])
-def test_mha_sublayer_fwd_bwd(dev, dtype, cross):
+def test_mha_sublayer_fwd_bwd(dev, dtype, cross, mode):
     from mtn_amd import ops
     B, a, m, d, h = 3, 20, 37 if cross else 20, 128, 4
     g = torch.Generator().manual_seed(11 + cross)
@@ -78,17 +97,19 @@ def test_mha_sublayer_fwd_bwd(dev, dtype, cross):
     wqkv, bqkv = D(torch.cat(w[:3], 0)), D(torch.cat(b[:3], 0))
     wo, bo = D(w[3]), D(b[3])
     memd = D(mem) if cross else None
-    cfg = ops.MhaConfig(heads=h, lp_dtype=dtype)
+    grads, queue, collect = _delivery(ops, mode, dict(ln_a=ad, ln_b=bd, w_qkv=wqkv, b_qkv=bqkv, w_o=wo, b_o=bo))
+    cfg = ops.MhaConfig(heads=h, lp_dtype=dtype, grads=grads, queue=queue)
     y = ops.MHASublayerFn.apply(xd, memd, None, mask.to(dev), ad, bd, wqkv, bqkv, wo, bo, cfg)
     y.backward(gy.to(dev))
     torch.cuda.synchronize()
+    G = collect()
     tol = TOL[dtype]
     assert relmax(y, yr) < tol
     assert relmax(xd.grad, xr.grad) < tol * 2
-    assert relmax(ad.grad, ar.grad) < tol * 2 and relmax(bd.grad, br.grad) < tol * 2
-    assert relmax(wqkv.grad, torch.cat([t.grad for t in wr[:3]], 0)) < tol * 2
-    assert relmax(bqkv.grad, torch.cat([t.grad for t in bbr[:3]], 0)) < tol * 2
-    assert relmax(wo.grad, wr[3].grad) < tol * 2 and relmax(bo.grad, bbr[3].grad) < tol * 2
+    assert relmax(G["ln_a"], ar.grad) < tol * 2 and relmax(G["ln_b"], br.grad) < tol * 2
+    assert relmax(G["w_qkv"], torch.cat([t.grad for t in wr[:3]], 0)) < tol * 2
+    assert relmax(G["b_qkv"], torch.cat([t.grad for t in bbr[:3]], 0)) < tol * 2
+    assert relmax(G["w_o"], wr[3].grad) < tol * 2 and relmax(G["b_o"], bbr[3].grad) < tol * 2
     if cross:
         assert relmax(memd.grad, leaves[11].grad) < tol * 2
 
@@ -108,8 +129,9 @@ class _RoundLP(torch.autograd.Function):
         return g.to(ctx.dtype).float(), None
 
 
+@pytest.mark.parametrize("mode", DELIVERY)
 @pytest.mark.parametrize("dtype", DTYPES)
-def test_ffn_sublayer_fwd_bwd(dev, dtype):
+def test_ffn_sublayer_fwd_bwd(dev, dtype, mode):
     from mtn_amd import ops
     rows, d, ff = 70, 128, 512
     g = torch.Generator().manual_seed(3)
@@ -126,13 +148,81 @@ def test_ffn_sublayer_fwd_bwd(dev, dtype):
     yr.backward(gy)
     y_exact = x + orc.feed_forward(orc.layer_norm(x, ln_a, ln_b), w1, b1, w2, b2)
     dl = [t.to(dev).requires_grad_() for t in (x, ln_a, ln_b, w1, b1, w2, b2)]
-    y = ops.FFNSublayerFn.apply(*dl, ops.FfnConfig(lp_dtype=dtype))
+    names = ("ln_a", "ln_b", "w1", "b1", "w2", "b2")
+    grads, queue, collect = _delivery(ops, mode, dict(zip(names, dl[1:])))
+    y = ops.FFNSublayerFn.apply(*dl, ops.FfnConfig(lp_dtype=dtype, grads=grads, queue=queue))
     y.backward(gy.to(dev))
     torch.cuda.synchronize()
+    G = collect()
     tol = TOL[dtype]
     assert relmax(y, y_exact) < tol               # forward output vs the exact fp32 oracle
-    for t, r in zip(dl, leaves):
-        assert relmax(t.grad, r.grad) < tol * 2   # gradients vs the oracle fed the same rounded operands
+    for t, r in zip([dl[0].grad] + [G[k] for k in names], leaves):
+        assert relmax(t, r.grad) < tol * 2        # gradients vs the oracle fed the same rounded operands
+
+
+def _single_and_group_case(dev, kind):
+    """One sublayer at the shapes of the two tests above, bf16, every dropout site at 0.1 under a fixed seed, destinations and a
+    queue set.  -> run(grouped) = (y, dx, dmem or None, destinations) of a fresh forward + backward."""
+    from mtn_amd import ops
+    g = torch.Generator().manual_seed(29)
+    bf16 = torch.bfloat16
+    seed = torch.full((1,), 1234, device=dev, dtype=torch.int64)
+    if kind == "ffn":
+        rows, d, ff = 70, 128, 512
+        x, mem, mask = torch.randn(2, rows // 2, d, generator=g), None, None
+        P = dict(ln_a=1 + 0.1 * torch.randn(d, generator=g), ln_b=0.1 * torch.randn(d, generator=g),
+                 w1=torch.randn(ff, d, generator=g) * d ** -0.5, b1=0.1 * torch.randn(ff, generator=g),
+                 w2=torch.randn(d, ff, generator=g) * ff ** -0.5, b2=0.1 * torch.randn(d, generator=g))
+    else:
+        B, a, m, d, h = 3, 20, 37, 128, 4
+        x, mem = torch.randn(B, a, d, generator=g), torch.randn(B, m, d, generator=g)
+        lens = torch.randint(1, m + 1, (B,), generator=g)
+        mask = (torch.arange(m).unsqueeze(0) < lens.unsqueeze(1)).unsqueeze(1).to(dev)
+        P = dict(ln_a=1 + 0.1 * torch.randn(d, generator=g), ln_b=0.1 * torch.randn(d, generator=g),
+                 w_qkv=torch.randn(3 * d, d, generator=g) * d ** -0.5, b_qkv=0.1 * torch.randn(3 * d, generator=g),
+                 w_o=torch.randn(d, d, generator=g) * d ** -0.5, b_o=0.1 * torch.randn(d, generator=g))
+    gy = torch.randn(x.shape, generator=g).to(dev)
+    P = {k: v.to(dev) for k, v in P.items()}
+    lp = {k: v.to(bf16) for k, v in P.items() if k.startswith("w")}
+
+    def run(grouped):
+        xd = x.to(dev).requires_grad_()
+        memd = mem.to(dev).requires_grad_() if mem is not None else None
+        G = {k: torch.full_like(v, float("nan")) for k, v in P.items()}
+        common = dict(p_out=0.1, salt=5, seed=seed, lp_dtype=bf16, grads=G, queue=ops.ParamGradQueue())
+        if kind == "ffn":
+            cfg = ops.FfnConfig(p_hidden=0.1, w1_lp=lp["w1"], w2_lp=lp["w2"], **common)
+            params = (P["ln_a"], P["ln_b"], P["b1"], P["b2"])
+        else:
+            cfg = ops.MhaConfig(heads=h, p_attn=0.1, w_qkv_lp=lp["w_qkv"], w_o_lp=lp["w_o"], **common)
+            params = (P["ln_a"], P["ln_b"], P["b_qkv"], P["b_o"])
+        if grouped:
+            y, = ops.SublayerGroupFn.apply([ops.GroupMember(kind, cfg, params, mask=mask)], xd, memd)
+        elif kind == "ffn":
+            y = ops.FFNSublayerFn.apply(xd, P["ln_a"], P["ln_b"], P["w1"], P["b1"], P["w2"], P["b2"], cfg)
+        else:
+            y = ops.MHASublayerFn.apply(xd, memd, None, mask, P["ln_a"], P["ln_b"], P["w_qkv"], P["b_qkv"], P["w_o"], P["b_o"], cfg)
+        y.backward(gy)
+        torch.cuda.synchronize()
+        return y.detach(), xd.grad, (memd.grad if memd is not None else None), G
+    return run
+
+
+@pytest.mark.parametrize("kind", ["mha", "ffn"])
+def test_single_sublayer_equals_one_member_group_bitwise(dev, kind):
+    """A single-sublayer Function and a SublayerGroupFn of that one member pack the same arguments for the same C entry point:
+    outputs, dx, dmem and every parameter-gradient destination are equal bit for bit (bf16, dropout 0.1 at every site)."""
+    run = _single_and_group_case(dev, kind)
+    y1, dx1, dmem1, G1 = run(grouped=False)
+    y2, dx2, dmem2, G2 = run(grouped=True)
+    assert bool(torch.isfinite(y1).all()) and not torch.equal(y1 - y1, y1)      # (not an all-zero comparison)
+    assert torch.equal(y1, y2) and torch.equal(dx1, dx2)
+    assert (dmem1 is None) == (dmem2 is None) == (kind == "ffn")
+    if dmem1 is not None:
+        assert bool(torch.isfinite(dmem1).all()) and torch.equal(dmem1, dmem2)
+    for k in G1:
+        assert bool(torch.isfinite(G1[k]).all()), k
+        assert torch.equal(G1[k], G2[k]), k
 
 
 # ------------------------------------------------------------------------------------------ whole model vs golden

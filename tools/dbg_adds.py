@@ -1,3 +1,5 @@
+"""One eager cfg2 step: how many sublayer-group inputs join a gradient meeting point (ops.GradMeet, kept in ctx.xaccs), and
+how many torch elementwise launches (add, copy, fill ...) autograd still issues."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
