@@ -108,6 +108,8 @@ typedef struct {
  * instead of writing g for a separate LayerNorm-backward launch.  u | c ("fold vectors", float [2K]) come from mtn_ln_fold().
  *   mode MTN_LN_EMIT    (the GEMM that produces dq itself: dh = (dy W2) gated, FFN sublayers; N % 64 == 0, 64-column tiles):
  *       part[row][N/64][2] += {sum v u, sum v (gate * gate_inv_scale - c)} over each 64-column block of the row; v = the stored value
+ *       (`gate` is required, and ldc — and ldr, with a residual — must be a multiple of 4: the gate value is read on the epilogue's
+ *        16-byte path only; anything else is refused, MTN_ERR_ARG)
  *   mode MTN_LN_CONSUME (g = dq W, N = d_model <= 512):  out_f32 / out_lp of the problem are ignored (may be NULL);
  *       part[row][np][2] are summed in index order; dx, dx_lp (through dx_lp_drop, as mtn_ln_bwd_desc) are written;
  *       colpart [ceil(M/8)][2N] receives the da2 | db2 partial rows of mtn_layernorm_bwd (same layout: finalize unchanged).

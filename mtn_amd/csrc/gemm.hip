@@ -2027,6 +2027,8 @@ extern "C" int mtn_gemm(int dtype, int count, const mtn_gemm_problem* problems, 
             sl.colpart = e.colpart; sl.dx_lp_drop = e.dx_lp_drop; sl.gate_inv_scale = e.gate_inv_scale; sl.eps = e.eps;
             if (e.mode == MTN_LN_EMIT) {
                 MTN_CHECK_ARG(e.fold && p.N % 64 == 0 && p.out_lp && (((uintptr_t)e.fold) & 15) == 0, "LayerNorm epilogue (emit): fold vectors, N % 64 == 0, a compute-dtype output");
+                // the second partial reads the gate VALUE, which epilogue4 reports on its vector path only
+                MTN_CHECK_ARG(p.gate && p.ldc % 4 == 0 && (!p.residual || p.ldr % 4 == 0), "LayerNorm epilogue (emit): a gate, and ldc (ldr) % 4 == 0");
                 lne_emit = true;
             } else {
                 MTN_CHECK_ARG(e.mode == MTN_LN_CONSUME, "LayerNorm epilogue: bad mode");
