@@ -48,8 +48,8 @@ const char* mtn_last_error(void);
  * 121: new entry point mtn_mbr_select.  122: new entry points mtn_eval_metrics and mtn_eval_workspace_bytes.
  * 123: new entry points mtn_distill_fwd / _bwd.  124: new entry points mtn_lerp_f32, mtn_ema_step and mtn_swap_f32.
  * 125: new entry points mtn_wlosshead_fwd / _bwd, mtn_eval_table_build, mtn_eval_score_rows, mtn_scst_assemble and mtn_scst_advantage.
- * Entry points added since (mtn_ulosshead_fwd / _bwd; mtn_grad_sumsq_partials, mtn_grad_sumsq, mtn_clip_scale; mtn_grad_accum) are
- * detected by symbol: additions only, the version stays 125. */
+ * Entry points added since (mtn_ulosshead_fwd / _bwd; mtn_grad_sumsq_partials, mtn_grad_sumsq, mtn_clip_scale; mtn_grad_accum;
+ * mtn_sched_mix) are detected by symbol: additions only, the version stays 125. */
 int mtn_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -739,6 +739,56 @@ int mtn_clip_scale(int n_partial, const double* partial, float max_norm, const f
 #define MTN_ACCUM_LAST 2
 int mtn_grad_accum(int mode, long n, float* acc, float* g, const float* w, const float* total_in, float* total_out, double* partial,
                    void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Scheduled sampling, the token mix (csrc/sched.hip; detected by symbol, version 125): the two-pass, parallel form (Mihaylova & Martins
+ * 2019; Duckworth et al. 2019).  logits [B * T, ldx] (fp32, row stride ldx >= V; columns V..ldx-1 are never read) are the generator's rows
+ * of a teacher-forced pass over the gold decoder inputs trg [B, T]; row (b, t - 1) predicts trg[b][t].  One launch writes mixed [B, T]:
+ * a copy of trg in which a fraction p of the positions holds the model's own prediction.  tests/sched_refs.py is the definition in numpy.
+ *   step     = state[0], the optimiser's device state (the step number mtn_noam_tick maintains, a float holding an integer); only
+ *              state[0] is read.
+ *   p        = p_max * min(1, max(0, step - start) / ramp) in fp32: a subtract, a max, a divide, a min and a multiply, each rounded
+ *              separately (no fma), start and ramp converted to float.  ramp == 0: p = p_max when step >= start, else 0.
+ *   coin     u = (sample_hash(seed + (uint64)step, ((uint64)key[b] << 12) | t, 0xFFFFFFFF) >> 8) * 2^-24 (exact in fp32; sample_hash is
+ *              mtn_sample_rows' counter hash, csrc/common.h).  Position (b, t) is ELIGIBLE iff t >= 1 and trg[b][t] != pad; it is
+ *              replaced iff it is eligible, u < p, and its row yields a pick (below).  Everywhere else mixed[b][t] = trg[b][t].
+ *   pick     over the columns c of row (b, t - 1) with c != pad and c not among banned[0..n_banned-1]:
+ *     MTN_SCHED_ARGMAX  the score is s_c = z_c;
+ *     MTN_SCHED_SAMPLE  Gumbel-max, one pass, no CDF scan: s_c = z_c * inv_temperature + g_c (a multiply, then an add),
+ *              g_c = -log(-log(u_c)), u_c = ((sample_hash(the coin's seed, the coin's key, c) >> 8) + 0.5) * 2^-24, which lies strictly
+ *              inside (0, 1).  With k = hash >> 8: for k < 2^23, u_c is exact in fp32 and w_c = -logf(u_c); for k >= 2^23, u_c is not an
+ *              fp32 number (rounded it would reach 1 at k = 2^24 - 1), but v_c = 1 - u_c = ((2^24 - 1 - k) + 0.5) * 2^-24 is, and
+ *              w_c = -log1pf(-v_c); then g_c = -logf(w_c).  V < 2^24, so the coin's position word 0xFFFFFFFF collides with no column.
+ *     The largest s_c wins, ties to the lowest c (-inf scores take part: a row of -inf picks its lowest admitted column).  A row with
+ *     every column excluded, or with a NaN among its admitted scores, yields no pick: the gold token stays and the position does not
+ *     count as replaced.  The mix never writes pad or a banned id, and never changes a pad position.
+ *   stats    3 unsigned 64-bit counters, accumulated (atomic adds; zero them to start a count): [0] += eligible positions,
+ *            [1] += replaced positions, [2] += replaced positions whose pick != trg[b][t].
+ *   pick_score (optional, [B, T] fp32): s of the winning column at a replaced position, NaN elsewhere.
+ * One workgroup of 256 threads per (b, t); the coin is evaluated first, uniformly, and a kept position returns without touching its
+ * logits row.  A replaced row is read once, with 16-byte loads when the row starts at a 16-byte boundary and scalar loads otherwise.
+ * Stream-ordered, capturable; nothing allocated, no host read.  seed is a host scalar: draws differ between replays because step does.
+ * MTN_ERR_ARG, nothing launched: a null pointer (pick_score may be NULL) or a misaligned one (logits, state, pick_score at 4 bytes, the
+ * rest at 8); mixed == trg (the gold ids must survive replays); B or T negative; T >= 4096; V < 1 or V >= 2^24; ldx < V; pick neither
+ * MTN_SCHED_ARGMAX nor MTN_SCHED_SAMPLE; p_max outside [0, 1] or NaN; start or ramp negative; n_banned outside [0, 4];
+ * inv_temperature not finite or <= 0.  B == 0 or T == 0 returns MTN_OK with nothing launched.
+ * ------------------------------------------------------------------------------------------ */
+#define MTN_SCHED_ARGMAX 0
+#define MTN_SCHED_SAMPLE 1
+typedef struct {
+    int B, T, V; long ldx;
+    const float* logits;              /* device: [B * T, ldx] */
+    const long* trg;                  /* device: [B, T] */
+    const long* key;                  /* device: [B] */
+    const float* state;               /* device: the optimiser state, [0] = step */
+    long pad; int n_banned; int banned[4];
+    float p_max; int start, ramp;
+    int pick; float inv_temperature; long seed;
+    long* mixed;                      /* device: [B, T], not trg */
+    unsigned long long* stats;        /* device: 3 */
+    float* pick_score;                /* device: [B, T], or NULL */
+} mtn_sched_args;
+int mtn_sched_mix(const mtn_sched_args* args /* host */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Device-side batch assembly (replaces the host padding of data_handler.py:206-274 `make_batch` and the mask passes of

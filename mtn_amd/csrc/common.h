@@ -144,6 +144,17 @@ __device__ __forceinline__ bool drop_keep_at(const DropState& s, const DropBase&
     return (r >> 8) >= s.thresh;
 }
 
+// ---------------------------------------------------------------- counter hash of the sampling kernels
+// u of (seed, key, position): the key words enter as an index does in drop_keep, the position as a Weyl step behind a second
+// mixer.  Integer arithmetic only (tests/sample_refs.py sample_hash is the same function in numpy).  For a fixed position the map
+// key (low word) -> hash is a bijection, and so is position -> hash for a fixed key.  (sample.hip, sched.hip)
+__device__ __forceinline__ uint32_t sample_hash(uint64_t seed, uint64_t key, uint32_t pos) {
+    const uint32_t k0 = mix32((uint32_t)seed ^ 0x9E3779B9u);
+    const uint32_t k1 = mix32((uint32_t)(seed >> 32) + 0x85EBCA6Bu + 0x165667B1u);
+    const uint32_t r = mix32(((uint32_t)key ^ k0) + (uint32_t)(key >> 32) * DROP_HI_MUL + k1);
+    return mix32(r + pos * 0x9E3779B1u + 0x7F4A7C15u);
+}
+
 // ---------------------------------------------------------------- Noam schedule tick (data_utils.py:111-117), one thread
 // state = [step, lr, 1 - b1^step, 1 - b2^step]; shared by noam_tick_kernel and the step-head launch (same bits)
 __device__ __forceinline__ void noam_tick_body(float* state, float factor, float model_size, float warmup, float beta1, float beta2) {

@@ -18,15 +18,7 @@
 static constexpr int SMP_THREADS = 256;
 static constexpr int SMP_PER = 16;                            // columns per thread on the register path
 
-// u of (seed, key, position): the key words enter as an index does in drop_keep (common.h), the position as a Weyl step behind a second
-// mixer.  Integer arithmetic only (tests/sample_refs.py sample_hash is the same function in numpy).  For a fixed position the map
-// key (low word) -> hash is a bijection, and so is position -> hash for a fixed key.
-__device__ __forceinline__ uint32_t sample_hash(uint64_t seed, uint64_t key, uint32_t pos) {
-    const uint32_t k0 = mix32((uint32_t)seed ^ 0x9E3779B9u);
-    const uint32_t k1 = mix32((uint32_t)(seed >> 32) + 0x85EBCA6Bu + 0x165667B1u);
-    const uint32_t r = mix32(((uint32_t)key ^ k0) + (uint32_t)(key >> 32) * DROP_HI_MUL + k1);
-    return mix32(r + pos * 0x9E3779B1u + 0x7F4A7C15u);
-}
+// sample_hash(seed, key, position), the counter hash of the draw, lives in common.h (sched.hip draws from it too).
 
 // monotone integer key of a float: a < b  <=>  key(a) < key(b)  (-0 below +0)
 __device__ __forceinline__ uint32_t float_key(float f) {

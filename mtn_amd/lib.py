@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libmtn_hip.so")
 
 MTN_F32, MTN_BF16 = 0, 1
 MTN_ACCUM_FIRST, MTN_ACCUM_ADD, MTN_ACCUM_LAST = 0, 1, 2      # mtn_grad_accum's modes (include/mtn_hip.h)
+MTN_SCHED_ARGMAX, MTN_SCHED_SAMPLE = 0, 1                     # mtn_sched_mix's picks
 
 
 class Dropout(C.Structure):
@@ -224,6 +225,13 @@ class ScstAdvantageArgs(C.Structure):
                 ("adv", C.c_void_p), ("mean_reward", C.c_void_p), ("mean_baseline", C.c_void_p)]
 
 
+class SchedArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("T", C.c_int), ("V", C.c_int), ("ldx", C.c_long), ("logits", C.c_void_p), ("trg", C.c_void_p),
+                ("key", C.c_void_p), ("state", C.c_void_p), ("pad", C.c_long), ("n_banned", C.c_int), ("banned", C.c_int * 4),
+                ("p_max", C.c_float), ("start", C.c_int), ("ramp", C.c_int), ("pick", C.c_int), ("inv_temperature", C.c_float),
+                ("seed", C.c_long), ("mixed", C.c_void_p), ("stats", C.c_void_p), ("pick_score", C.c_void_p)]
+
+
 class LnFinalizeDesc(C.Structure):
     _fields_ = [("partial", C.c_void_p), ("nparts", C.c_int), ("d", C.c_int), ("da2", C.c_void_p), ("db2", C.c_void_p)]
 
@@ -338,6 +346,7 @@ SYMBOLS = {
     "mtn_grad_sumsq": (C.c_int, [C.c_long, _P, _P, _P]),
     "mtn_clip_scale": (C.c_int, [C.c_int, _P, C.c_float, _P, _P, _P, _P, _P]),
     "mtn_grad_accum": (C.c_int, [C.c_int, C.c_long, _P, _P, _P, _P, _P, _P, _P]),
+    "mtn_sched_mix": (C.c_int, [C.POINTER(SchedArgs), _P]),
 }
 
 _lib = None

@@ -972,6 +972,58 @@ def sample_rows(logp, seed, keys, step, log=None, max_len=1, **kw):
     return log
 
 
+SCHED_PICKS = {"argmax": L.MTN_SCHED_ARGMAX, "sample": L.MTN_SCHED_SAMPLE}
+
+
+def sched_mix(logits, trg, keys, state, *, pad, prob, start=0, ramp=0, pick="argmax", temperature=1.0, seed=0, banned=(), out=None,
+              stats=None, pick_score=None):
+    """Scheduled sampling's token mix (csrc/sched.hip; include/mtn_hip.h mtn_sched_mix gives every formula): logits (B * T, V) fp32
+    (unit column stride, any row stride >= V) are the generator's rows of a teacher-forced pass over the gold decoder inputs ``trg``
+    (B, T) int64; row (b, t - 1) predicts trg[b, t].  Returns ``out`` (B, T) int64 (created when None; never ``trg`` itself): trg with a
+    fraction p = prob * min(1, max(0, step - start) / ramp) of its eligible positions (t >= 1, not <pad>) replaced by the row's arg-max
+    ("argmax") or a Gumbel-max draw at ``temperature`` ("sample") over the columns that are neither ``pad`` nor ``banned``.  ``keys``
+    (B,) int64 name the rows to the counter hash; ``state`` is the optimiser's device state (FusedAdam.state): state[0], the step
+    number, is read on the device, so a captured launch draws anew on every replay.  ``stats`` (3,) int64 accumulates [eligible,
+    replaced, replaced with a token other than gold]; ``pick_score`` (B, T) fp32 receives the winning score (NaN where gold stays)."""
+    _require_cuda(logits, trg, keys, state)
+    if pick not in SCHED_PICKS:
+        raise ValueError("sched_mix: pick is 'argmax' or 'sample'")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or (logits.size(1) > 1 and logits.stride(1) != 1):
+        raise ValueError("sched_mix: logits is (B * T, V) fp32 with unit column stride")
+    if trg.dtype != torch.int64 or trg.dim() != 2 or not trg.is_contiguous() or keys.dtype != torch.int64 or not keys.is_contiguous():
+        raise ValueError("sched_mix: trg is a contiguous (B, T) int64 tensor, keys a contiguous (B,) int64 tensor")
+    B, T = trg.shape
+    if logits.size(0) != B * T or keys.numel() != B or state.dtype != torch.float32 or state.numel() < 1:
+        raise ValueError("sched_mix: one logits row per target position, one key per sequence, an fp32 optimiser state")
+    banned = [int(b) for b in banned]
+    if len(banned) > 4:
+        raise ValueError("sched_mix: at most 4 banned tokens")
+    if not float(temperature) > 0.0:
+        raise ValueError("sched_mix: temperature > 0")
+    dev = trg.device
+    if out is None:
+        out = torch.empty_like(trg)
+    if stats is None:
+        stats = torch.zeros(3, dtype=torch.int64, device=dev)
+    for name, t, dt, n in (("out", out, torch.int64, B * T), ("stats", stats, torch.int64, 3)) + \
+            ((("pick_score", pick_score, torch.float32, B * T),) if pick_score is not None else ()):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != dev:
+            raise ValueError("sched_mix: %s is a contiguous %s tensor of %d elements on trg's device" % (name, dt, n))
+    if B * T == 0:                    # (an empty tensor has no address to hand over)
+        return out
+    a = L.SchedArgs()
+    a.B, a.T, a.V, a.ldx = B, T, logits.size(1), (logits.stride(0) if logits.size(0) > 1 else logits.size(1))
+    a.logits, a.trg, a.key, a.state = logits.data_ptr(), trg.data_ptr(), keys.data_ptr(), state.data_ptr()
+    a.pad, a.n_banned = int(pad), len(banned)
+    for i, b in enumerate(banned):
+        a.banned[i] = b
+    a.p_max, a.start, a.ramp, a.pick = float(prob), int(start), int(ramp), SCHED_PICKS[pick]
+    a.inv_temperature, a.seed = 1.0 / float(temperature), int(seed)
+    a.mixed, a.stats, a.pick_score = out.data_ptr(), stats.data_ptr(), L.ptr(pick_score)
+    L.check(L.load().mtn_sched_mix(C.byref(a), L.stream_ptr()))
+    return out
+
+
 def constrain_rows(logp, ngram=0, theta=1.0, *, hist=None, hist_len=None, log_tok=None, log_parent=None, step=None, width=1,
                    rows_per_step=1, log_len=None, out=None):
     """N-gram blocking and repetition penalty on the rows of logp (rows, V) fp32 from each row's history (csrc/constrain.hip;

@@ -123,9 +123,22 @@ def parse(argv=None):
                    help="K > 1: the optimiser updates once per window of K consecutive batches, from the token-weighted mean of their "
                         "gradients, accumulated on the device (an epoch's last window may be shorter); under several ranks the gradient "
                         "exchange runs once per window; every epoch logs its updates (1: off)")
+    # scheduled sampling: the decoder is fed a mix of gold tokens and the model's own predictions from one extra eval() forward per step
+    p.add_argument("--sched-sample-prob", default=0.0, type=float, metavar="P",
+                   help="0 < P <= 1: before every training forward the model runs once over the gold prefix and a fraction P of the "
+                        "decoder's input tokens is replaced by its predictions (two-pass scheduled sampling: Mihaylova & Martins 2019, "
+                        "Duckworth et al. 2019); targets, validation and checkpoints are unchanged; every epoch logs the replaced "
+                        "tokens (0: off)")
+    p.add_argument("--sched-sample-start", default=0, type=int, metavar="S", help="optimiser updates before any token is replaced")
+    p.add_argument("--sched-sample-ramp", default=0, type=int, metavar="R",
+                   help="the fraction grows linearly from 0 to P over R updates after --sched-sample-start (0: P at once)")
+    p.add_argument("--sched-sample-pick", default="argmax", choices=["argmax", "sample"],
+                   help="argmax: the most likely token; sample: a draw from softmax(logits / --sched-sample-temperature)")
+    p.add_argument("--sched-sample-temperature", default=1.0, type=float)
+    p.add_argument("--sched-sample-seed", default=0, type=int, help="seed of the coins and draws (the update count is added on the device)")
     args = p.parse_args(argv)
     err = (distill_flag_error(args) or ema_flag_error(args) or scst_flag_error(args) or unlikelihood_flag_error(args) or clip_flag_error(args)
-           or accum_flag_error(args))
+           or accum_flag_error(args) or sched_flag_error(args))
     if err:
         p.error(err)
     return args
@@ -243,6 +256,52 @@ def accum_flag_error(args, world=None):
         return ("--accum-steps does not combine with the sharded data-parallel optimiser (MTN_DP_SHARDED=%s): accumulation under it is out "
                 "of scope; leave MTN_DP_SHARDED unset or 0" % os.environ["MTN_DP_SHARDED"])
     return None
+
+
+def sched_flag_error(args, world=None):
+    """What is wrong with the --sched-sample-* flags, or what they conflict with, as one line (None: nothing).  0 = off.  ``world``: the
+    number of ranks (scheduled sampling runs under any number; the argument keeps the siblings' signature)."""
+    import math
+    pr = args.sched_sample_prob
+    if not 0.0 <= pr <= 1.0:                       # (nan fails the comparison)
+        return "--sched-sample-prob must be 0 (off) or lie in (0, 1] (got %r)" % pr
+    if args.sched_sample_start < 0:
+        return "--sched-sample-start must be >= 0 (got %r)" % args.sched_sample_start
+    if args.sched_sample_ramp < 0:
+        return "--sched-sample-ramp must be >= 0 (got %r)" % args.sched_sample_ramp
+    if not (args.sched_sample_temperature > 0.0 and math.isfinite(args.sched_sample_temperature)):
+        return "--sched-sample-temperature must be finite and > 0 (got %r)" % args.sched_sample_temperature
+    if not 0 <= args.sched_sample_seed < 2 ** 62:
+        return "--sched-sample-seed must lie in [0, 2^62) (got %r)" % args.sched_sample_seed
+    if pr == 0.0:
+        return None
+    if args.distill_model:
+        return ("--sched-sample-prob does not combine with --distill-model: the teacher would have to see the mixed inputs; scheduled "
+                "sampling under distillation is out of scope")
+    if args.scst_samples:
+        return "--sched-sample-prob does not combine with --scst-samples: scheduled sampling under self-critical training is out of scope"
+    return None
+
+
+def sched_config(args):
+    """The --sched-sample-* flags as a train_step.SchedConfig (None: off).  <sos> = 2 is never picked (nor is <pad>)."""
+    if args.sched_sample_prob == 0.0:
+        return None
+    from .train_step import SchedConfig
+    return SchedConfig(args.sched_sample_prob, start=args.sched_sample_start, ramp=args.sched_sample_ramp, pick=args.sched_sample_pick,
+                       temperature=args.sched_sample_temperature, seed=args.sched_sample_seed, banned=(2,))
+
+
+def sched_epoch_report(cfg, stats, step_count, epoch, rank):
+    """The epoch's scheduled-sampling line from the device counter block (one small D2H copy; the block is reset; the ranks' counts are
+    summed).  ``step_count``: the optimiser's update count, at which p is quoted."""
+    st = stats.clone()
+    stats.zero_()
+    if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        torch.distributed.all_reduce(st)
+    n, k, d = (int(v) for v in st.tolist())
+    if rank == 0:
+        print("epoch %d scheduled sampling: p %f replaced %d of %d target tokens, %d differ from gold" % (epoch + 1, cfg.prob_at(step_count), k, n, d))
 
 
 def clip_epoch_report(adam, epoch, rank):
@@ -495,7 +554,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(asctime)s %(levelname)s: %(message)s")
     cut_a = cut_a_applies(args)
     rank, world, local = dp.init_distributed()
-    err = scst_flag_error(args, world) or clip_flag_error(args, world) or accum_flag_error(args, world)
+    err = scst_flag_error(args, world) or clip_flag_error(args, world) or accum_flag_error(args, world) or sched_flag_error(args, world)
     if err:
         raise SystemExit("mtn_amd.train: " + err)
     local = local % torch.cuda.device_count()      # (several ranks may share a GPU in a gloo dry run)
@@ -577,7 +636,8 @@ def main(argv=None):
             logging.info("self-critical training: %d samples per dialogue, reward %s, baseline %s, %d reference answers on the device",
                          scst.samples, scst.reward, scst.baseline, corpus.n_dialogs)
         accum = args.accum_steps > 1                          # (--eager then runs the trainer's steps eagerly, as under scst)
-        if args.eager and scst is None and not accum:
+        sched = sched_config(args)                            # (likewise: the first pass and the mix belong to the trainer's step)
+        if args.eager and scst is None and not accum and sched is None:
             opt = NoamOpt(args.d_model, 1, args.warmup_steps, FusedAdam(model))
             if args.ema_decay:
                 opt.optimizer.enable_ema(args.ema_decay)
@@ -589,8 +649,9 @@ def main(argv=None):
             from .train_step import BucketedTrainer
             trainer = BucketedTrainer(model, corpus, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l,
                                       bucket=args.bucket, grad_sync=sync, ema_decay=args.ema_decay, scst=scst,
-                                      use_graph=not (args.eager and (scst is not None or accum)), unlikelihood=args.unlikelihood_alpha,
-                                      clip_grad_norm=args.clip_grad_norm, accum_steps=args.accum_steps, **distill)
+                                      use_graph=not (args.eager and (scst is not None or accum or sched is not None)),
+                                      unlikelihood=args.unlikelihood_alpha, clip_grad_norm=args.clip_grad_norm, accum_steps=args.accum_steps,
+                                      sched=sched, **distill)
         valid = None
         if args.valid_videos > 0 or valid_data is not None:
             vdata = valid_data if valid_data is not None else synthetic_corpus(args.valid_videos, args.vocab_size, args.ft_sizes, args.rand_seed + 1000)
@@ -598,7 +659,7 @@ def main(argv=None):
             valid = (DeviceCorpus(vdata, dev), vidx)
             logging.info("#validation sample = %d  #validation batch = %d", vn, len(vidx))
         min_valid = min_valid_ema = 1.0e10
-        graphed = not args.eager or scst is not None or accum  # (self-critical / accumulating --eager: the trainer's steps, run eagerly)
+        graphed = not args.eager or scst is not None or accum or sched is not None  # (then --eager: the trainer's steps, run eagerly)
         the_opt = trainer.opt if graphed else opt
         if args.resume:
             model.load_state_dict(torch.load(args.resume + ".pth.tar", map_location=dev), strict=False)
@@ -631,6 +692,8 @@ def main(argv=None):
                     print("epoch %d mean reward: %f mean baseline: %f" % (epoch + 1, stats["reward"], stats["baseline"]))
             if args.clip_grad_norm:
                 clip_epoch_report(the_opt.optimizer, epoch, rank)
+            if sched is not None and trainer.sched_stats is not None:
+                sched_epoch_report(sched, trainer.sched_stats, the_opt.step_count(), epoch, rank)
             if args.model:
                 # EVERY rank builds the optimiser state: with the sharded optimiser (dp.ShardedOptimizerSync) a rank holds the
                 # Adam moments of its shards only (and, with the compute-dtype gather, the current fp32 masters of its shards
@@ -679,7 +742,8 @@ def main(argv=None):
     Q, H, C, T, V = args.lens
     batch = synthetic_batch(args.vocab_size, args.batch_size, Q, H, C, T, [V] * len(args.ft_sizes), args.ft_sizes, device=dev, seed=1 + rank)
     step = TrainStep(model, batch, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l, grad_sync=sync, ema_decay=args.ema_decay,
-                     unlikelihood=args.unlikelihood_alpha, clip_grad_norm=args.clip_grad_norm, accumulate=args.accum_steps > 1, **distill)
+                     unlikelihood=args.unlikelihood_alpha, clip_grad_norm=args.clip_grad_norm, accumulate=args.accum_steps > 1,
+                     sched=sched_config(args), **distill)
     ntok = int(batch.ntokens) * world
     K = args.accum_steps
     for epoch in range(args.num_epochs):
@@ -713,6 +777,8 @@ def main(argv=None):
             print("epoch %d optimiser updates: %d over %d batches" % (epoch + 1, -(-args.steps_per_epoch // K), args.steps_per_epoch))
         if args.clip_grad_norm:
             clip_epoch_report(step.opt.optimizer, epoch, rank)
+        if step.sched is not None:
+            sched_epoch_report(step.sched, step.sched_stats, step.opt.step_count(), epoch, rank)
         if args.model:
             model_state = model.state_dict()      # every rank: under the sharded optimiser's compute-dtype gather this gathers the fp32
             if rank == 0:                         # masters of the other ranks' shards (a collective) — rank 0 alone writes

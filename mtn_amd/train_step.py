@@ -85,12 +85,50 @@ class ScstConfig:
         return c
 
 
+class SchedConfig:
+    """Scheduled sampling in its two-pass, parallel form (Mihaylova & Martins 2019; Duckworth et al. 2019) for TrainStep(sched=...):
+    ahead of every training forward the model runs once under eval() / no_grad over the gold decoder inputs, and one mtn_sched_mix
+    launch (include/mtn_hip.h gives the formulas) replaces a fraction p of the decoder's INPUT tokens by that pass's predictions; the
+    step then trains on the mixed inputs against the gold targets.  p = ``prob`` * min(1, max(0, step - ``start``) / ``ramp``) with step
+    the optimiser's update count, read on the device (``ramp`` 0: ``prob`` from ``start`` on).  ``pick``: "argmax", or "sample" (a
+    Gumbel-max draw from softmax(logits / ``temperature``)).  ``banned``: up to 4 ids never picked (<sos>; <pad> is always excluded).
+    ``seed``: of the counter hash, to which the device adds the step."""
+
+    def __init__(self, prob: float, start: int = 0, ramp: int = 0, pick: str = "argmax", temperature: float = 1.0, seed: int = 0,
+                 banned=(2,)):
+        prob, temperature = float(prob), float(temperature)
+        if not 0.0 < prob <= 1.0:
+            raise ValueError("sched: 0 < prob <= 1")
+        if int(start) != start or int(ramp) != ramp or not (0 <= int(start) < 2 ** 31 and 0 <= int(ramp) < 2 ** 31):
+            raise ValueError("sched: start and ramp are integers >= 0 (update counts)")
+        if pick not in ("argmax", "sample"):
+            raise ValueError("sched: pick is argmax or sample")
+        if not (0.0 < temperature < float("inf")):
+            raise ValueError("sched: temperature is finite and > 0")
+        if int(seed) != seed or not 0 <= int(seed) < 2 ** 62:
+            raise ValueError("sched: seed is an integer in [0, 2^62)")
+        banned = tuple(int(b) for b in banned)
+        if len(banned) > 4 or any(b < 0 for b in banned):
+            raise ValueError("sched: at most 4 banned token ids, none negative")
+        self.prob, self.start, self.ramp, self.pick = prob, int(start), int(ramp), pick
+        self.temperature, self.seed, self.banned = temperature, int(seed), banned
+
+    def prob_at(self, step: int) -> float:
+        """p at update count ``step``, in the kernel's fp32 arithmetic."""
+        import numpy as np
+        f = np.float32
+        if self.ramp == 0:
+            return float(f(self.prob)) if step >= self.start else 0.0
+        d = max(f(0.0), f(step) - f(self.start))
+        return float(f(self.prob) * min(f(1.0), f(d / f(self.ramp))))
+
+
 class TrainStep:
     def __init__(self, model, batch, vocab: int, pad: int = 1, warmup: int = 4000, factor: float = 1.0, lam: float = 1.0,
                  smoothing: float = 0.1, grad_sync=None, use_graph: bool = True, overlap: Optional[bool] = None, opt=None,
                  dynamic_norms: bool = False, fuse_optimizer: Optional[bool] = None, teacher=None, distill_alpha: float = 0.5,
                  distill_temperature: float = 1.0, ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, unlikelihood: float = 0.0,
-                 clip_grad_norm: float = 0.0, accumulate: bool = False):
+                 clip_grad_norm: float = 0.0, accumulate: bool = False, sched: Optional[SchedConfig] = None):
         """``opt``: share an existing NoamOpt (several TrainSteps over one model, e.g. one per batch shape).
         ``dynamic_norms``: the batch tensors are refilled in place between steps, so the loss normalisers (token counts,
         train.py:35-39) are recomputed from them inside the step instead of once at construction.
@@ -149,8 +187,22 @@ class TrainStep:
         accumulate launch (and the exchange) between the replays; nothing in a window synchronises with the host.  The returned
         loss is the micro-step's own.  Data parallelism: the whole-buffer, non-overlapped all-reduce, once per window, after the
         closing launch; MTN_DP_SHARDED=1 raises.  With clipping on one rank the closing launch also writes the partials of G's sum
-        of squares and the update skips its mtn_grad_sumsq launch.  Not together with scst."""
+        of squares and the update skips its mtn_grad_sumsq launch.  Not together with scst.
+        ``sched``: scheduled sampling (SchedConfig).  Inside the step (and its captured graph), before the training forward, the student
+        itself runs an eval() forward on the gold batch under no_grad, its generator logits go through one mtn_sched_mix launch into
+        ``sched_mixed`` (allocated once), and the training forward reads a shallow copy of the batch whose ``trg`` is that buffer:
+        ``trg_y``, the masks and the normalisers are the gold batch's (the mix never writes <pad> and never changes a <pad> position).
+        The first pass leaves nothing behind and no gradient flows through it.  ``sched_keys`` (B,) int64 name the rows to the counter
+        hash: rank * B + b unless the caller refills them (BucketedTrainer: the batch's QA ids); the step word is the optimiser's
+        update count on the device, so every replay draws anew, a resumed run continues the stream, and the micro-steps of an
+        accumulation window share it (on a fixed batch they repeat their draws).  ``sched_stats`` (3,) int64 on the device counts
+        [eligible, replaced, replaced with another token than gold] until the caller zeroes it.  None = off: nothing is allocated or
+        launched.  Not together with a teacher (it would have to see the mixed inputs) or scst."""
         self.model, self.batch = model, batch
+        self.sched = sched
+        if sched is not None and (teacher is not None or scst is not None):
+            raise ValueError("TrainStep: sched (scheduled sampling) does not combine with %s" % ("a teacher (distillation)" if teacher is not None
+                                                                                                  else "scst"))
         clip_grad_norm = float(clip_grad_norm)
         if not clip_grad_norm >= 0.0:              # (nan fails the comparison)
             raise ValueError("TrainStep: clip_grad_norm is 0 (off) or > 0 (inf allowed)")
@@ -229,6 +281,7 @@ class TrainStep:
         self._norms = torch.stack([batch.ntokens, (ae_y != pad).sum()]).float()
         if grad_sync is not None:
             grad_sync.all_reduce_scalars(self._norms)
+        self._init_sched()
 
     @property
     def last_grad_norm(self):
@@ -280,10 +333,56 @@ class TrainStep:
     def _teacher_pass(self):
         """The teacher's rows for this batch, into the buffer allocated once; returns it (None without a teacher).  eval() forwards
         under no_grad: no dropout stream is advanced, nothing enters a parameter-gradient queue, and every forward ends by flushing
-        its rider work (EncoderDecoder.forward), so the student's launches that follow are those of the undistilled step."""
+        its rider work (EncoderDecoder.forward), so the student's launches that follow are those of the undistilled step.
+        Scheduled sampling's first pass is such a forward too, by the student itself: it runs here."""
+        if self.sched is not None:
+            self._sched_pass()
         if self._teacher_rows is None:
             return None
         return teacher_rows(self.teacher, self.batch, out=self._teacher_rows)
+
+    # ---- scheduled sampling
+    def _init_sched(self):
+        """``_fwd_batch``: what the training forward reads.  The gold batch itself without scheduled sampling."""
+        self._fwd_batch, self.sched_mixed, self.sched_keys, self.sched_stats = self.batch, None, None, None
+        if self.sched is None:
+            return
+        import copy
+        b = self.batch
+        if b.trg.size(1) >= 4096 or not b.trg.is_contiguous():
+            raise ValueError("TrainStep: sched needs contiguous decoder inputs of fewer than 4096 target positions")
+        rank = 0
+        if self.grad_sync is not None and torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank = torch.distributed.get_rank(getattr(self.grad_sync, "group", None))
+        B, dev = b.trg.size(0), b.trg.device
+        self.sched_keys = torch.arange(rank * B, rank * B + B, dtype=torch.int64, device=dev)
+        self.sched_stats = torch.zeros(3, dtype=torch.int64, device=dev)
+        self.sched_mixed = b.trg.detach().clone().contiguous()
+        self._fwd_batch = copy.copy(b)
+        self._fwd_batch.trg = self.sched_mixed
+
+    def _sched_pass(self):
+        """The first pass: the student's eval() forward over the GOLD batch under no_grad, its generator logits, one mtn_sched_mix
+        launch into ``sched_mixed``."""
+        from . import ops
+        cfg, m, b = self.sched, self.model, self.batch
+        training = m.training
+        m.eval()
+        try:
+            with torch.no_grad():
+                state = self.opt.optimizer.state
+                if self.overlap and self.sharded is not None:
+                    # the one schedule that advances the optimiser state BEFORE the forward (begin_sharded_step ahead of the segment
+                    # graphs): the draws are those of the update count every other schedule reads, so no schedule changes the stream
+                    state = (state[:1] - 1.0).clamp_(min=0.0)
+                o, _ = m.forward(b)
+                z = m.generator.logits(o)
+                ops.sched_mix(z.reshape(-1, z.size(-1)), b.trg, self.sched_keys, state, pad=self.pad, prob=cfg.prob,
+                              start=cfg.start, ramp=cfg.ramp, pick=cfg.pick, temperature=cfg.temperature, seed=cfg.seed,
+                              banned=cfg.banned, out=self.sched_mixed, stats=self.sched_stats)
+        finally:
+            if training:
+                m.train()
 
     # ---- self-critical sequence training
     def _init_scst(self, src, pad):
@@ -475,7 +574,7 @@ class TrainStep:
         if fuse:
             self.opt.begin_fused_step()
         try:
-            out, ae_out = m.forward(b)
+            out, ae_out = m.forward(self._fwd_batch)
             loss = self._loss_of(out, ae_out, teacher_rows)
             loss.backward(self._unit_grad(loss))          # (a kept ones scalar: autograd would launch a fill for the implicit one)
         except BaseException:
@@ -544,7 +643,7 @@ class TrainStep:
             self._refresh_norms()
             teacher_rows = self._teacher_pass()
             m.zero_glue_grads()
-            st = m.forward_segmented(b)
+            st = m.forward_segmented(self._fwd_batch)
             self._st = st
             loss = self._loss_of(st["out"], st["ae_out"], teacher_rows)
             loss.backward(self._unit_grad(loss))                # loss head + final LayerNorms
@@ -599,6 +698,15 @@ class TrainStep:
         self.grad_sync.wait(works)
 
     def _capture(self):
+        """Warm-up and capture.  The warm-up passes launch scheduled sampling's mix like any step: its counters are put back after."""
+        keep = None if self.sched_stats is None else self.sched_stats.clone()
+        try:
+            self._capture_schedule()
+        finally:
+            if keep is not None:
+                self.sched_stats.copy_(keep)
+
+    def _capture_schedule(self):
         m = self.model
         m.prepare()
         self._fused()                               # decides (and builds its device-side tables) outside the capture
@@ -781,7 +889,7 @@ class BucketedTrainer:
     def __init__(self, model, corpus, vocab_size: int, pad: int = 1, warmup: int = 4000, lam: float = 1.0, bucket: int = 8,
                  grad_sync=None, max_shapes: int = 64, teacher=None, distill_alpha: float = 0.5, distill_temperature: float = 1.0,
                  ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, use_graph: bool = True, unlikelihood: float = 0.0,
-                 clip_grad_norm: float = 0.0, accum_steps: int = 1):
+                 clip_grad_norm: float = 0.0, accum_steps: int = 1, sched: Optional[SchedConfig] = None):
         """``scst``: self-critical sequence training — every padded shape keeps, next to its static source Batch, a TrainStep(scst=...)
         whose own static batch holds the drawn rows; a step refills the source in place and calls rl_step with the batch's QA ids as
         corpus items and sampling keys and the seed ``scst.seed + rl_steps`` (``rl_steps``: steps taken; set it after a resume).  With
@@ -792,7 +900,14 @@ class BucketedTrainer:
         ``accum_steps``: K > 1 = gradient accumulation (TrainStep's ``accumulate``): step() is one micro-step and every K-th one, or
         one called with ``last=True``, closes the window and updates.  The accumulator belongs to the shared optimiser, so the
         micro-steps of one window may fall into different padded shapes.  ``micro_steps`` / ``updates``: counted on the host.
-        1 = off: today's step, launch for launch.  Not together with scst."""
+        1 = off: today's step, launch for launch.  Not together with scst.
+        ``sched``: scheduled sampling (TrainStep's ``sched``) for every shape: the rows' hash keys are the batch's QA ids, refilled
+        before every step, and ``sched_stats`` is the one (3,) int64 device counter block all shapes add to (zero it to start a count).
+        ``use_graph`` = False runs these steps eagerly.  Not together with a teacher or scst."""
+        if sched is not None and (teacher is not None or scst is not None):
+            raise ValueError("BucketedTrainer: sched (scheduled sampling) does not combine with %s" % ("a teacher (distillation)" if teacher is not None
+                                                                                                        else "scst"))
+        self.sched, self.sched_stats = sched, None
         if int(accum_steps) != accum_steps or int(accum_steps) < 1:
             raise ValueError("BucketedTrainer: accum_steps is an integer >= 1")
         self.accum_steps, self.micro_steps, self.updates, self._in_window = int(accum_steps), 0, 0, 0
@@ -857,11 +972,17 @@ class BucketedTrainer:
             ts = TrainStep(self.model, batch, self.vocab, pad=self.pad, lam=self.lam, grad_sync=self.grad_sync, opt=self.opt,
                            dynamic_norms=True, teacher=self.teacher, distill_alpha=self.distill_alpha,
                            distill_temperature=self.distill_temperature, scst=cfg, use_graph=self.use_graph,
-                           unlikelihood=self.unlikelihood)
+                           unlikelihood=self.unlikelihood, sched=self.sched)
+            if self.sched is not None:                           # one counter block for every shape (read at launch: set before the capture)
+                if self.sched_stats is None:
+                    self.sched_stats = ts.sched_stats
+                ts.sched_stats = self.sched_stats
             self.steps[key] = hit = (batch, ts)
         else:
             make_batch(self.corpus, pidx, self.pad, separate_caption=True, out=hit[0], cut_a=cut_a, rng=rng)
         hit[1].refresh_norms_eager()
+        if self.sched is not None:
+            hit[1].sched_keys.copy_(torch.tensor([int(q) for q in index[1]], dtype=torch.int64), non_blocking=False)
         if self.scst is not None:
             loss = hit[1].rl_step(list(index[1]), seed=self.scst.seed + self.rl_steps)
             self.rl_steps += 1
