@@ -587,7 +587,7 @@ __device__ __forceinline__ void fh_body(const FhGroup& G, const FhMember& M, con
                                             fh_pack2(st[2 * u + 1][0], st[2 * u + 1][1]), fh_pack2(st[2 * u + 1][2], st[2 * u + 1][3]));
                 uint4 vf[4];
 #pragma unroll
-                for (int nt = 0; nt < 4; ++nt) vf[nt] = fh_vfrag(vi_s, krow0 + c0 + 32 * u, nt * 16, l15, lg);
+                for (int nt = 0; nt < 4; ++nt) vf[nt] = tr_frag<FH_HROWB, SwzPair7>(vi_s, krow0 + c0 + 32 * u, nt * 16, l15, lg);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll

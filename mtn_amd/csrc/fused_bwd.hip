@@ -124,25 +124,9 @@ __device__ __forceinline__ void fb_dma_head_rows(const bf16_t* base, int ld_elem
         fh_dma16(rs, (unsigned)(size_t)(img + i * 1024), vo);
     }
 }
-// A-operand fragment of X^T from a row-major [row][64] image swizzled with row & 7: head columns n_off + (lane & 15),
-// rows row0 + 8*lg .. +7 (ds_read_b64_tr_b16)
-__device__ __forceinline__ uint4 fb_tfrag(const unsigned char* img, int row0, int n_off, int l15, int lg) {
-    uint4 f;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int krow = row0 + 8 * lg + 4 * r + (l15 >> 2);
-        const int col = n_off + 4 * (l15 & 3);
-        const int slot = (col >> 3) ^ (krow & 7);
-        const unsigned addr = (unsigned)(size_t)(img + krow * FH_HROWB + slot * 16 + (col & 7) * 2);
-        unsigned long long v;
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-        if (r == 0) { f.x = (unsigned)v; f.y = (unsigned)(v >> 32); }
-        else { f.z = (unsigned)v; f.w = (unsigned)(v >> 32); }
-    }
-    return f;
-}
-// the same transposing read on a tile image [32 rows][32 columns] with FB_DSROW-byte rows (no swizzle): columns n_off + (lane & 15),
-// rows 8*lg .. +7
+// the transposing read of tr_frag (lds_tile.h) on a tile image [32 rows][32 columns] with FB_DSROW-byte rows (no swizzle): columns
+// n_off + (lane & 15), rows 8*lg .. +7.  (Kept as a function of its own: through tr_frag with a zero swizzle the compiler emits other
+// address arithmetic and schedules the kernel differently, and this file's counted waits are checked against the instructions as they are.)
 __device__ __forceinline__ uint4 fb_tfrag_img(const unsigned char* img, int n_off, int l15, int lg) {
     uint4 f;
 #pragma unroll
@@ -503,9 +487,9 @@ __device__ __forceinline__ void fb_body(const FbMember& M, const int slice, cons
                     // ---- phase 2: head columns 16 w4 .. +15.  dV^T += dO^T P, dK^T += Q^T dS (contraction over the block's 32 queries,
                     // per key sub-tile), dQ^T += K^T dS^T (contraction over the tile's 32 keys); A operands by transposing reads of the
                     // row-major images
-                    const uint4 dot_ = fb_tfrag(doi_s, qrow0 + 32 * qb, w4 * 16, l15, lg);
-                    const uint4 qt_ = fb_tfrag(qi_s, qrow0 + 32 * qb, w4 * 16, l15, lg);
-                    const uint4 kt_ = fb_tfrag(ki_s, jimg, w4 * 16, l15, lg);
+                    const uint4 dot_ = tr_frag<FH_HROWB, SwzRow<7>>(doi_s, qrow0 + 32 * qb, w4 * 16, l15, lg);
+                    const uint4 qt_ = tr_frag<FH_HROWB, SwzRow<7>>(qi_s, qrow0 + 32 * qb, w4 * 16, l15, lg);
+                    const uint4 kt_ = tr_frag<FH_HROWB, SwzRow<7>>(ki_s, jimg, w4 * 16, l15, lg);
                     uint4 pf[2], sf[2], sfq[2];
 #pragma unroll
                     for (int k2 = 0; k2 < 2; ++k2) {

@@ -4,6 +4,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "lds_tile.h"
 
 static constexpr int FH_D = 512;          // d_model
 static constexpr int FH_DK = 64;          // head width
@@ -14,8 +15,6 @@ static constexpr int FH_THREADS = 512;    // 8 waves: column block (wave & 3) x 
 enum { FH_SELF = 0, FH_CROSS_READY = 1, FH_CROSS_RAW = 2, FH_FFN = 3 };
 #define FH_MAX_MEMBERS (2 * MTN_SUBLAYER_MAX_GROUP)
 
-
-typedef __attribute__((address_space(3))) void fh_lds_void_t;
 
 // LDS-DMA issued by INLINE ASM (round 3).  With the builtin the compiler knows that LDS-DMA is outstanding and puts
 // s_waitcnt vmcnt(0) in front of every LDS read it can see afterwards (it cannot tell the image being filled from the bytes being
@@ -58,23 +57,8 @@ __device__ __forceinline__ uint4 fh_xfrag(const unsigned char* img, int row, int
 __device__ __forceinline__ uint4 fh_hfrag(const unsigned char* img, int row, int chunk) {          // [row][64] image, Q / K
     return *(const uint4*)(img + row * FH_HROWB + ((chunk ^ (row & 7)) << 4));
 }
-// A-operand fragment of V^T from the row-major V image: head columns n_off + (lane & 15), keys row0 + 8*lg .. +7
-// (ds_read_b64_tr_b16, semantics as in gemm.hip ttd_frag; 16-byte slots swizzled with (row >> 1) & 7)
-__device__ __forceinline__ uint4 fh_vfrag(const unsigned char* img, int row0, int n_off, int l15, int lg) {
-    uint4 f;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int krow = row0 + 8 * lg + 4 * r + (l15 >> 2);
-        const int col = n_off + 4 * (l15 & 3);
-        const int slot = (col >> 3) ^ ((krow >> 1) & 7);
-        const unsigned addr = (unsigned)(size_t)(img + krow * FH_HROWB + slot * 16 + (col & 7) * 2);
-        unsigned long long v;
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-        if (r == 0) { f.x = (unsigned)v; f.y = (unsigned)(v >> 32); }
-        else { f.z = (unsigned)v; f.w = (unsigned)(v >> 32); }
-    }
-    return f;
-}
+// (A-operand fragments of V^T / X^T come out of the row-major head images by tr_frag<FH_HROWB, swizzle of the image>, lds_tile.h:
+//  head columns n_off + (lane & 15), rows row0 + 8*lg .. +7.  The V image is swizzled with SwzPair7, the Q / K / dO images with SwzRow<7>.)
 
 // Counted waits of the fused kernels.  They wait with `s_waitcnt vmcnt(N)`, N = the vector-memory operations the compiler emits TODAY behind
 // the LDS-DMA images / row loads a stage needs (each site spells its count out and static_asserts what it depends on).  -DMTN_SAFE_WAITS

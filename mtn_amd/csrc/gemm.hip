@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lds_tile.h"
 
 struct GemmGroup {
     int count;
@@ -548,67 +549,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmGroup grp, const ty
 }
 
 // ====================================================================================================================
-// dW = dY^T X (both operands contraction-major) with 128x128 tiles: the parameter-gradient launches carry ~2000 64x64
-// workgroups each re-reading its two operand panels; at 128x128 every panel byte feeds twice the outputs, which halves
-// the bytes each CU pulls (the bound, see gemm_dma_kernel).  4 waves x (4x4 MFMA tiles), 128 B of contraction per step,
-// 4x4 in-register block transposes on the way to LDS exactly as in gemm_kernel<T,true,true>.
-// ====================================================================================================================
-template <typename T> struct StageT128 {      // one 128-row x 128-byte contraction-major operand tile
-    uint4 r[sizeof(T) == 2 ? 4 : 4];
-    __device__ __forceinline__ void load(const T* __restrict__ base, int ld, int R, int K, int row0, int k0, int tid) {
-        if constexpr (sizeof(T) == 2) {       // 64 k x 128 rows: 16 x 32 blocks of 4x4, two per thread
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int blk = tid + 256 * j, kb = blk >> 5, rb = blk & 31;
-                const int gr = row0 + rb * 4;
-                uint2 v[4];
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    const int gk = k0 + kb * 4 + kk;
-                    v[kk] = (gk < K && gr < R) ? *(const uint2*)(base + (size_t)gk * ld + gr) : make_uint2(0, 0);
-                }
-                r[2 * j].x = (v[0].x & 0xffffu) | (v[1].x << 16);        r[2 * j].y = (v[2].x & 0xffffu) | (v[3].x << 16);
-                r[2 * j].z = (v[0].x >> 16) | (v[1].x & 0xffff0000u);    r[2 * j].w = (v[2].x >> 16) | (v[3].x & 0xffff0000u);
-                r[2 * j + 1].x = (v[0].y & 0xffffu) | (v[1].y << 16);    r[2 * j + 1].y = (v[2].y & 0xffffu) | (v[3].y << 16);
-                r[2 * j + 1].z = (v[0].y >> 16) | (v[1].y & 0xffff0000u); r[2 * j + 1].w = (v[2].y >> 16) | (v[3].y & 0xffff0000u);
-            }
-        } else {                              // 32 k x 128 rows: 8 x 32 blocks, one per thread
-            const int kb = tid >> 5, rb = tid & 31;
-            const int gr = row0 + rb * 4;
-            uint4 v[4];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const int gk = k0 + kb * 4 + kk;
-                v[kk] = (gk < K && gr < R) ? *(const uint4*)(base + (size_t)gk * ld + gr) : make_uint4(0, 0, 0, 0);
-            }
-            r[0] = make_uint4(v[0].x, v[1].x, v[2].x, v[3].x);
-            r[1] = make_uint4(v[0].y, v[1].y, v[2].y, v[3].y);
-            r[2] = make_uint4(v[0].z, v[1].z, v[2].z, v[3].z);
-            r[3] = make_uint4(v[0].w, v[1].w, v[2].w, v[3].w);
-        }
-    }
-    __device__ __forceinline__ void store(unsigned char* s, int tid) const {
-        if constexpr (sizeof(T) == 2) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int blk = tid + 256 * j, kb = blk >> 5, rb = blk & 31;
-                unsigned char* p = s + (rb * 4) * LDSROW + kb * 8;
-                *(uint2*)(p) = make_uint2(r[2 * j].x, r[2 * j].y);
-                *(uint2*)(p + LDSROW) = make_uint2(r[2 * j].z, r[2 * j].w);
-                *(uint2*)(p + 2 * LDSROW) = make_uint2(r[2 * j + 1].x, r[2 * j + 1].y);
-                *(uint2*)(p + 3 * LDSROW) = make_uint2(r[2 * j + 1].z, r[2 * j + 1].w);
-            }
-        } else {
-            const int kb = tid >> 5, rb = tid & 31;
-            unsigned char* p = s + (rb * 4) * LDSROW + kb * 16;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) *(uint4*)(p + q * LDSROW) = r[q];
-        }
-    }
-};
-
-
-// ====================================================================================================================
 // Fast path for row-major x row-major problems (forward Linears, and dX = dY (W^T)^T through the transposed weight
 // copy): the problems on this path are SMALL (M = B*L = 640..4096 rows, K = 512..2048) and latency-bound, so the
 // kernel is built around memory-level parallelism rather than MFMA issue rate:
@@ -622,54 +562,14 @@ template <typename T> struct StageT128 {      // one 128-row x 128-byte contract
 //   * counted vmcnt + raw s_barrier: the next stage stays in flight across the barrier.
 // ====================================================================================================================
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-// one operand tile of ROWS rows x ROWB bytes (512 or 256): ROWS*ROWB/4096 LDS-DMA instructions per wave, each 1 KiB
-// (2 rows of 512 B or 4 rows of 256 B); 16-byte slots XOR-swizzled with (row & 15) inside the row
-template <typename T, int ROWS, int ROWB, int NW = 4>
-__device__ __forceinline__ void dma_issue_tile(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_tile, int ld_bytes, int R,
-                                               int K, int row0, int k0, int wave, int lane) {
-    constexpr int EPV = LP<T>::EPV;
-    constexpr int CPR = ROWB / 16;                               // 16-byte chunks per row (32 or 16)
-    constexpr int RPI = 1024 / ROWB;                             // rows per wave-instruction (2 or 4)
-#pragma unroll
-    for (int j = 0; j < ROWS * ROWB / (1024 * NW); ++j) {
-        const int row = (j * NW + wave) * RPI + lane / CPR;      // tile row written by this lane
-        const int c = (lane % CPR) ^ (row & 15);                 // source chunk that lands in slot (lane % CPR)
-        const int gk = k0 + c * EPV;
-        int grow = row0 + row;
-        grow = grow < R ? grow : R - 1;                          // rows past the end only feed outputs that are never stored
-        unsigned voff = (gk < K) ? (unsigned)grow * (unsigned)ld_bytes + (unsigned)gk * (unsigned)sizeof(T) : 0x80000000u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(lds_tile + (j * NW + wave) * 1024), 16, voff, 0, 0, 0);
-    }
-}
-
-// B operand stored CONTRACTION-MAJOR ([K][N] row-major: a weight matrix W[out k][in n] used as dX = dY W — no transposed copy of
-// W has to exist): the [k][BN columns] tile lands in LDS as it is (rows of BN * 2 bytes) and the MFMA fragments come out of the
-// transposing LDS read ds_read_b64_tr_b16 (semantics: gemm_tt_dma_kernel above).  16-byte slots are XOR-swizzled so that the 8
-// rows one LDS cycle of the read touches (k0..k0+3 of two lane groups, 8 rows apart) sit in 8 different 32-byte bank groups:
-// 128-byte rows (BN = 64): even / odd rows own the two halves of the bank sweep, the slot PAIR moves with bits 1 and 3 of k;
-// 64-byte rows (BN = 32): four consecutive rows own a quarter each, bit 3 of k selects the 32-byte half.
-template <int BN> __device__ __forceinline__ int kn_swz(int krow) {
-    if constexpr (BN == 64) return ((((krow >> 1) & 1) | (((krow >> 3) & 1) << 1)) << 1);
-    else return ((krow >> 3) & 1) << 1;
-}
-template <int BN, int ROWB, int NW = 4>
-__device__ __forceinline__ void dma_issue_tile_kn(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_tile, int ld_bytes, int N, int K,
-                                                  int col0, int k0, int wave, int lane) {
-    constexpr int RP = BN * 2;                                   // bytes per tile row
-    constexpr int CPR = RP / 16;                                 // 16-byte chunks per row (8 or 4)
-    constexpr int RPI = 1024 / RP;                               // k rows per wave-instruction (8 or 16)
-#pragma unroll
-    for (int j = 0; j < BN * ROWB / (1024 * NW); ++j) {
-        const int krow = (j * NW + wave) * RPI + lane / CPR;
-        const int c = (lane % CPR) ^ kn_swz<BN>(krow);           // source chunk that lands in slot (lane % CPR)
-        const int gk = k0 + krow, gn = col0 + c * 8;
-        unsigned voff = (gk < K && gn < N) ? (unsigned)gk * (unsigned)ld_bytes + (unsigned)gn * 2u : 0x80000000u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(lds_tile + (j * NW + wave) * 1024), 16, voff, 0, 0, 0);
-    }
-}
-// fragment for column tile n_off (multiple of 16 inside the tile) and contraction step ks (32 rows) of a [k][BN] image
+// (the tile movers, the swizzles and the transposing fragment read: lds_tile.h)
+// B operand stored CONTRACTION-MAJOR (BTR; [K][N] row-major: a weight matrix W[out k][in n] used as dX = dY W — no transposed copy of
+// W has to exist): the [k][BN columns] tile lands in LDS as it is (rows of BN * 2 bytes, swizzle SwzKn<BN>) and the MFMA fragments
+// come out of the transposing LDS read.
+//
+// Fragment for column tile n_off (multiple of 16 inside the tile) and contraction step ks (32 rows) of the [k][BN] image: tr_frag's
+// read, written out.  (Through tr_frag<BN * 2, SwzKn<BN>>(img, ks * 32, ...) the six BN = 64 kernels come out with two address
+// instructions in another order and other register numbers — tools/kernel_isa_diff.py; this copy keeps them as they were measured.)
 template <int BN>
 __device__ __forceinline__ uint4 kn_frag(const unsigned char* img, int n_off, int ks, int l15, int lg) {
     uint4 f;
@@ -677,7 +577,7 @@ __device__ __forceinline__ uint4 kn_frag(const unsigned char* img, int n_off, in
     for (int r = 0; r < 2; ++r) {
         const int krow = ks * 32 + 8 * lg + 4 * r + (l15 >> 2);
         const int col = n_off + 4 * (l15 & 3);
-        const int slot = (col >> 3) ^ kn_swz<BN>(krow);
+        const int slot = (col >> 3) ^ SwzKn<BN>::f(krow);
         const unsigned addr = (unsigned)(size_t)(img + krow * (BN * 2) + slot * 16 + (col & 7) * 2);
         unsigned long long v;
         asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
@@ -687,20 +587,20 @@ __device__ __forceinline__ uint4 kn_frag(const unsigned char* img, int n_off, in
     return f;
 }
 
-// Tile BM x BN (64x64, 32x64 or 32x32), 4 waves as 2x2, each wave (BM/32) x (BN/32) MFMA 16x16 tiles.  The smaller tiles
+// Tile BM x BN (64x64 or 32x32), 4 waves as 2x2, each wave (BM/32) x (BN/32) MFMA 16x16 tiles.  The smaller tiles
 // exist because these launches are bound by how fast ONE CU can pull its operand panels (~27 GB/s per CU measured, LDS-DMA
 // and register staging alike): a [640 x 512] output is 80 workgroups of 128 KiB at 64x64 but 320 workgroups of 64 KiB at
 // 32x32 — the whole chip pulls instead of a third of it.
 // ROWB = bytes of contraction per row per stage: 512 (whole K <= 512-byte contractions in flight at once: best latency for
 // launches of one round) or 256 (half the LDS: twice the resident workgroups, for launches that would otherwise need a
 // second round).
-// NBUF = 4 (round 3, long contractions in one round of workgroups): a ring of four half-size stages, stage s+3 issued while stage s
-// is computed — three stages in flight instead of "refill after compute", one barrier per stage instead of two.
+// Two stages, refilled after compute (a ring of four half-size stages for long contractions was measured at -0.8 % on the cfg2 step,
+// profiles/r03_x_deep_ring_ab.txt: not kept).
 // NW = 8 (round 3: the 64 x 64 tile on full stages, ONE workgroup per CU): eight waves instead of four.  A wave gets one 1 KiB
 // load through every ~180 ns however many it has queued (profiles/r03_fh_order.txt), so a CU's fill rate is its resident waves x
 // ~5.6 GB/s: four waves pulled 22-26 GB/s where the two-workgroups-per-CU variants (eight waves) reach twice that.  Waves as 2 row
 // halves x 4 column quarters (wave tile 32 x 16).
-template <typename T, int BM, int BN, int DMA_ROWB, bool BTR = false, int NBUF = 2, int NW = 4, bool LNE = false>
+template <typename T, int BM, int BN, int DMA_ROWB, bool BTR = false, int NW = 4, bool LNE = false>
 __global__ __launch_bounds__(64 * NW) void gemm_dma_kernel(const GemmGroup grp, const typename LnArg<LNE>::type lne) {
     constexpr int BK = DMA_ROWB / (int)sizeof(T);            // 256 / 128 bf16, 128 / 64 fp32
     constexpr int WR = NW == 16 ? 4 : 2;                     // waves across the rows (NW = 16: a 4 x 4 grid of 16 x 16 wave tiles on the 64 x 64 tile)
@@ -734,8 +634,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_dma_kernel(const GemmGroup grp, 
                                           : __builtin_amdgcn_make_buffer_rsrc((void*)P.B, 0, (N - 1) * ldb_b + K * (int)sizeof(T), 0x00020000);
     // the B tile of a stage: row-major [BN rows][DMA_ROWB bytes of k], or (BTR: B stored [K][N]) [BK k-rows][BN columns]
     auto issue_b = [&](unsigned char* dst, int k0) {
-        if constexpr (BTR) dma_issue_tile_kn<BN, DMA_ROWB, NW>(rB, dst, ldb_b, N, K, col0, k0, wave, lane);
-        else dma_issue_tile<T, BN, DMA_ROWB, NW>(rB, dst, ldb_b, N, K, col0, k0, wave, lane);
+        if constexpr (BTR) dma_issue_kn<BN * 2, BK, NW, SwzKn<BN>>(rB, dst, ldb_b, N, K, col0, k0, wave, lane);
+        else dma_issue_rows<T, DMA_ROWB, BN, NW>(rB, dst, ldb_b, N, K, col0, k0, wave, lane);
     };
 
     f32x4_t acc[TM][TN];
@@ -746,12 +646,12 @@ __global__ __launch_bounds__(64 * NW) void gemm_dma_kernel(const GemmGroup grp, 
 
     const int nstages = (K + BK - 1) / BK;
     auto issue_stage = [&](int st) {
-        unsigned char* dst = smem + (st & (NBUF - 1)) * STAGE_BYTES;
-        dma_issue_tile<T, BM, DMA_ROWB, NW>(rA, dst, lda_b, M, K, row0, st * BK, wave, lane);
+        unsigned char* dst = smem + (st & 1) * STAGE_BYTES;
+        dma_issue_rows<T, DMA_ROWB, BM, NW>(rA, dst, lda_b, M, K, row0, st * BK, wave, lane);
         issue_b(dst + A_BYTES, st * BK);
     };
-    // prologue: NBUF = 2: up to two stages in flight; NBUF = 4: up to three (NDMA LDS-DMA instructions per wave per stage, always)
-    for (int st = 0; st < (NBUF == 2 ? 2 : NBUF - 1) && st < nstages; ++st) issue_stage(st);
+    // prologue: up to two stages in flight (NDMA LDS-DMA instructions per wave per stage, always)
+    for (int st = 0; st < 2 && st < nstages; ++st) issue_stage(st);
     // LayerNorm epilogue (LNE): its loads go out right behind the first stages, so that their round trip hides under the contraction.
     // The counted waits below stay as they are: with these loads in the queue a wait for stage s also waits for the loads issued
     // before the stages behind s — at most a few instructions' worth of over-waiting in the first two iterations, exact afterwards.
@@ -800,32 +700,22 @@ __global__ __launch_bounds__(64 * NW) void gemm_dma_kernel(const GemmGroup grp, 
     }
     const DropState ds = drop_init(P.drop);        // scalar seed load + key hashing ride under the operand DMA
     for (int s = 0; s < nstages; ++s) {
-        // stage s landed; the stages behind it may still fly (NBUF = 2: one, NBUF = 4: two): counted vmcnt
+        // stage s landed; the stage behind it may still fly: counted vmcnt
         const int ahead = nstages - 1 - s;
-        static_assert(NDMA == 16 || NDMA == 12 || NDMA == 8 || NDMA == 6 || NDMA == 4 || NDMA == 2, "unexpected stage size");
-        if (NBUF > 2 && ahead >= 2) {
-            static_assert(NBUF == 2 || 2 * NDMA <= 16, "vmcnt immediates end at 63, keep the pipeline's count small");
-            if constexpr (NDMA == 8) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-            else if constexpr (NDMA == 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        } else if (ahead >= 1) {
+        static_assert(NDMA == 16 || NDMA == 8 || NDMA == 4 || NDMA == 2, "unexpected stage size");
+        if (ahead >= 1) {
             if constexpr (NDMA == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-            else if constexpr (NDMA == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
             else if constexpr (NDMA == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else if constexpr (NDMA == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
             else if constexpr (NDMA == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if constexpr (LNE) {                   // last stage: everything has landed, the epilogue's loads included — its row sums
-                if (lne_mode == MTN_LN_CONSUME) ln_consume_publish<TM, TN>(lnq, tid, (float*)(smem + NBUF * STAGE_BYTES), tid < 8 * BM);     // ride on this barrier
+                if (lne_mode == MTN_LN_CONSUME) ln_consume_publish<TM, TN>(lnq, tid, (float*)(smem + 2 * STAGE_BYTES), tid < 8 * BM);     // ride on this barrier
             }
         }
         __builtin_amdgcn_s_barrier();
-        if constexpr (NBUF > 2) {                  // every wave is done with stage s-1: its buffer takes stage s + NBUF - 1
-            if (s + NBUF - 1 < nstages) issue_stage(s + NBUF - 1);
-        }
-        const unsigned char* sA = smem + (s & (NBUF - 1)) * STAGE_BYTES;
+        const unsigned char* sA = smem + (s & 1) * STAGE_BYTES;
         const unsigned char* sB = sA + A_BYTES;
         const int kleft = K - s * BK;
         int ksteps = kleft >= BK ? DMA_ROWB / 64 : (kleft * (int)sizeof(T) + 63) / 64;   // 64-byte contraction steps holding data
@@ -887,12 +777,10 @@ __global__ __launch_bounds__(64 * NW) void gemm_dma_kernel(const GemmGroup grp, 
                 }
             }
         }
-        if constexpr (NBUF == 2) {
-            if (s + 2 < nstages) {       // refill this buffer with stage s+2 once every wave is done reading it
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                issue_stage(s + 2);
-            }
+        if (s + 2 < nstages) {       // refill this buffer with stage s+2 once every wave is done reading it
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            issue_stage(s + 2);
         }
     }
 
@@ -905,7 +793,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_dma_kernel(const GemmGroup grp, 
         if (sl != 0) {
             const LnEpiSlot& E = lne.s[sl - 1];
             if (lne_mode == MTN_LN_CONSUME) {
-                ln_consume_epilogue<TM, TN, BM>(E, lnq, acc, M, N, row0, row0 + wr * (BM / WR), col0 + wc * (BN / WC), l15, lg, tid, (float*)(smem + NBUF * STAGE_BYTES));
+                ln_consume_epilogue<TM, TN, BM>(E, lnq, acc, M, N, row0, row0 + wr * (BM / WR), col0 + wc * (BN / WC), l15, lg, tid, (float*)(smem + 2 * STAGE_BYTES));
                 return;
             }
             float p1[TM], p2[TM];
@@ -931,7 +819,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_dma_kernel(const GemmGroup grp, 
                     }
                 }
             }
-            ln_emit_partials<TM, BM, WC>(E, p1, p2, M, N / 64, col0 / 64, row0, row0 + wr * (BM / WR), wc, l15, lg, tid, (float*)(smem + NBUF * STAGE_BYTES));
+            ln_emit_partials<TM, BM, WC>(E, p1, p2, M, N / 64, col0 / 64, row0, row0 + wr * (BM / WR), wc, l15, lg, tid, (float*)(smem + 2 * STAGE_BYTES));
             return;
         }
     }
@@ -951,47 +839,13 @@ __global__ __launch_bounds__(64 * NW) void gemm_dma_kernel(const GemmGroup grp, 
 // ====================================================================================================================
 // dW = dY^T X on LDS-DMA (bf16).  Both operands are contraction-major in memory ([rows of the batch][features]), which is
 // exactly what LDS-DMA can copy (lane-linear 16-byte chunks, no transposition in flight): the [k][n] tiles land in LDS
-// as they are and the MFMA fragments are read with the transposing LDS read ds_read_b64_tr_b16.  Semantics measured on
-// gfx950 (tools/tr_probe.hip): inside each 16-lane group, result lane i element j = element (i%4) of the 8-byte chunk
-// supplied by lane 4j + i/4.  So lane t of a group supplies &T[k0 + t/4][n0 + 4*(t%4)] and lane i receives T[k0..k0+3][n0+i]:
-// a 4(k) x 16(n) block delivered column-per-lane; two reads (k0 and k0+4) make one 16x16x32 fragment with the standard
-// slot order (lane group g covers k = 8g..8g+7).
+// as they are and the MFMA fragments are read with the transposing LDS read ds_read_b64_tr_b16 (tr_frag, lds_tile.h).
 // Stage = 128 contraction rows x (64+64) features = 32 KiB, two stages = 64 KiB -> two workgroups per CU.
 // Bias gradients (row sums of dY^T) ride on one extra MFMA per fragment against an all-ones operand.
 // ====================================================================================================================
 static constexpr int TTD_KS = 128;                        // contraction rows per stage
 static constexpr int TTD_TILE_BYTES = TTD_KS * 128;       // one operand tile per stage: 128 k x 64 features x 2 B
 static constexpr int TTD_LDS = 4 * TTD_TILE_BYTES;        // 2 operands x 2 stages
-
-__device__ __forceinline__ void ttd_issue_tile(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_tile, int ld_bytes, int R, int K,
-                                               int col0, int k0, int wave, int lane) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int krow = (j * 4 + wave) * 8 + (lane >> 3);           // row of the tile written by this lane
-        const int p = lane & 7;                                      // 16-byte slot inside the 128-byte row
-        const int c = p ^ ((krow >> 1) & 7);                         // source chunk (XOR swizzle: the 4 rows of a transposing read hit different banks)
-        const int gk = k0 + krow, gn = col0 + c * 8;
-        unsigned voff = (gk < K && gn < R) ? (unsigned)gk * (unsigned)ld_bytes + (unsigned)gn * 2u : 0x80000000u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(lds_tile + (j * 4 + wave) * 1024), 16, voff, 0, 0, 0);
-    }
-}
-
-// fragment for feature tile n_off (multiple of 16) and contraction step ks (32 rows) of a [k][64 features] image
-__device__ __forceinline__ uint4 ttd_frag(const unsigned char* img, int n_off, int ks, int l15, int lg) {
-    uint4 f;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int krow = ks * 32 + 8 * lg + 4 * r + (l15 >> 2);
-        const int col = n_off + 4 * (l15 & 3);                       // element column
-        const int slot = (col >> 3) ^ ((krow >> 1) & 7);             // swizzled 16-byte slot
-        const unsigned addr = (unsigned)(size_t)(img + krow * 128 + slot * 16 + (col & 7) * 2);
-        unsigned long long v;
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-        if (r == 0) { f.x = (unsigned)v; f.y = (unsigned)(v >> 32); }
-        else { f.z = (unsigned)v; f.w = (unsigned)(v >> 32); }
-    }
-    return f;
-}
 
 __global__ __launch_bounds__(256) void gemm_tt_dma_kernel(const GemmGroup grp, const AdamGroup adam) {
     typedef bf16_t T;
@@ -1025,11 +879,11 @@ __global__ __launch_bounds__(256) void gemm_tt_dma_kernel(const GemmGroup grp, c
     const uint4 ones = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);   // bf16 1.0 x 8
 
     const int nstages = (K + TTD_KS - 1) / TTD_KS;
-    ttd_issue_tile(rA, smem, lda_b, M, K, row0, 0, wave, lane);
-    ttd_issue_tile(rB, smem + TTD_TILE_BYTES, ldb_b, N, K, col0, 0, wave, lane);
+    dma_issue_kn<128, TTD_KS, 4, SwzPair7>(rA, smem, lda_b, M, K, row0, 0, wave, lane);
+    dma_issue_kn<128, TTD_KS, 4, SwzPair7>(rB, smem + TTD_TILE_BYTES, ldb_b, N, K, col0, 0, wave, lane);
     if (nstages > 1) {
-        ttd_issue_tile(rA, smem + 2 * TTD_TILE_BYTES, lda_b, M, K, row0, TTD_KS, wave, lane);
-        ttd_issue_tile(rB, smem + 3 * TTD_TILE_BYTES, ldb_b, N, K, col0, TTD_KS, wave, lane);
+        dma_issue_kn<128, TTD_KS, 4, SwzPair7>(rA, smem + 2 * TTD_TILE_BYTES, lda_b, M, K, row0, TTD_KS, wave, lane);
+        dma_issue_kn<128, TTD_KS, 4, SwzPair7>(rB, smem + 3 * TTD_TILE_BYTES, ldb_b, N, K, col0, TTD_KS, wave, lane);
     }
     for (int s = 0; s < nstages; ++s) {
         if (s + 1 < nstages) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");     // 8 LDS-DMA instructions per wave per stage
@@ -1042,8 +896,8 @@ __global__ __launch_bounds__(256) void gemm_tt_dma_kernel(const GemmGroup grp, c
             uint4 a[2], b[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                a[i] = ttd_frag(sA, wr * 32 + i * 16, ks, l15, lg);
-                b[i] = ttd_frag(sB, wc * 32 + i * 16, ks, l15, lg);
+                a[i] = tr_frag<128, SwzPair7>(sA, ks * 32, wr * 32 + i * 16, l15, lg);
+                b[i] = tr_frag<128, SwzPair7>(sB, ks * 32, wc * 32 + i * 16, l15, lg);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
@@ -1057,8 +911,8 @@ __global__ __launch_bounds__(256) void gemm_tt_dma_kernel(const GemmGroup grp, c
         if (s + 2 < nstages) {
             __builtin_amdgcn_s_barrier();
             unsigned char* dst = smem + (s & 1) * 2 * TTD_TILE_BYTES;
-            ttd_issue_tile(rA, dst, lda_b, M, K, row0, (s + 2) * TTD_KS, wave, lane);
-            ttd_issue_tile(rB, dst + TTD_TILE_BYTES, ldb_b, N, K, col0, (s + 2) * TTD_KS, wave, lane);
+            dma_issue_kn<128, TTD_KS, 4, SwzPair7>(rA, dst, lda_b, M, K, row0, (s + 2) * TTD_KS, wave, lane);
+            dma_issue_kn<128, TTD_KS, 4, SwzPair7>(rB, dst + TTD_TILE_BYTES, ldb_b, N, K, col0, (s + 2) * TTD_KS, wave, lane);
         }
     }
     if (do_rowsum && wc == 0 && lg == 0) {       // every accumulator row of rs[] holds the same sums; column l15 = output row
@@ -1089,46 +943,11 @@ __global__ __launch_bounds__(256) void gemm_tt_dma_kernel(const GemmGroup grp, c
 // The same contraction with 128 x 128 output tiles for the large parameter-gradient launches: every operand byte pulled
 // into LDS feeds twice the outputs of the 64 x 64 kernel, which is what bounds these launches (L2 -> LDS fill).  Stage = 64
 // contraction rows x (128 + 128) features = 32 KiB, two stages = 64 KiB -> two workgroups per CU; 4 waves x (4 x 4) MFMA
-// tiles.  Rows of the [k][128 features] image are 256 B = one full sweep of the LDS banks, so the 16-byte slots are
-// XOR-swizzled with s(k) = 2*(k & 3) + 8*((k >> 3) & 1): the 8 rows one transposing read touches per LDS cycle
-// (k0..k0+3 of lane groups 0 and 1, 8 rows apart) then sit in 8 different 32-byte bank groups.
+// tiles.  Rows of the [k][128 features] image are 256 B = one full sweep of the LDS banks: swizzle SwzK128 (lds_tile.h).
 // ====================================================================================================================
 static constexpr int TTB_KS = 64;                         // contraction rows per stage
 static constexpr int TTB_TILE_BYTES = TTB_KS * 256;       // one operand tile per stage: 64 k x 128 features x 2 B
 static constexpr int TTB_LDS = 4 * TTB_TILE_BYTES;        // 2 operands x 2 stages = 64 KiB
-
-__device__ __forceinline__ int ttb_swz(int krow) { return ((krow & 3) << 1) | (((krow >> 3) & 1) << 3); }
-
-__device__ __forceinline__ void ttb_issue_tile(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_tile, int ld_bytes, int R, int K,
-                                               int col0, int k0, int wave, int lane) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {                                    // 16 instructions per tile, 4 per wave: 4 rows of 256 B each
-        const int inst = j * 4 + wave;
-        const int krow = inst * 4 + (lane >> 4);
-        const int p = lane & 15;                                     // 16-byte slot inside the 256-byte row
-        const int c = p ^ ttb_swz(krow);                             // source chunk that lands in slot p
-        const int gk = k0 + krow, gn = col0 + c * 8;
-        unsigned voff = (gk < K && gn < R) ? (unsigned)gk * (unsigned)ld_bytes + (unsigned)gn * 2u : 0x80000000u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(lds_tile + inst * 1024), 16, voff, 0, 0, 0);
-    }
-}
-
-// fragment for feature tile n_off (multiple of 16) and contraction step ks (32 rows) of a [k][128 features] image
-__device__ __forceinline__ uint4 ttb_frag(const unsigned char* img, int n_off, int ks, int l15, int lg) {
-    uint4 f;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int krow = ks * 32 + 8 * lg + 4 * r + (l15 >> 2);
-        const int col = n_off + 4 * (l15 & 3);
-        const int slot = (col >> 3) ^ ttb_swz(krow);
-        const unsigned addr = (unsigned)(size_t)(img + krow * 256 + slot * 16 + (col & 7) * 2);
-        unsigned long long v;
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-        if (r == 0) { f.x = (unsigned)v; f.y = (unsigned)(v >> 32); }
-        else { f.z = (unsigned)v; f.w = (unsigned)(v >> 32); }
-    }
-    return f;
-}
 
 // Bias of the Linear whose weight gradient this problem is (table form, round 5): db = the row sums this tile produces anyway, so the
 // bias's Adam update is applied right there (p, m, v, compute-dtype copy at the bias's flat offset) instead of by a later pass.
@@ -1157,11 +976,11 @@ __device__ __forceinline__ void tt128_tile(const mtn_gemm_problem& P, const Adam
     const uint4 ones = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
 
     const int nstages = (K + TTB_KS - 1) / TTB_KS;
-    ttb_issue_tile(rA, smem, lda_b, M, K, row0, 0, wave, lane);
-    ttb_issue_tile(rB, smem + TTB_TILE_BYTES, ldb_b, N, K, col0, 0, wave, lane);
+    dma_issue_kn<256, TTB_KS, 4, SwzK128>(rA, smem, lda_b, M, K, row0, 0, wave, lane);
+    dma_issue_kn<256, TTB_KS, 4, SwzK128>(rB, smem + TTB_TILE_BYTES, ldb_b, N, K, col0, 0, wave, lane);
     if (nstages > 1) {
-        ttb_issue_tile(rA, smem + 2 * TTB_TILE_BYTES, lda_b, M, K, row0, TTB_KS, wave, lane);
-        ttb_issue_tile(rB, smem + 3 * TTB_TILE_BYTES, ldb_b, N, K, col0, TTB_KS, wave, lane);
+        dma_issue_kn<256, TTB_KS, 4, SwzK128>(rA, smem + 2 * TTB_TILE_BYTES, lda_b, M, K, row0, TTB_KS, wave, lane);
+        dma_issue_kn<256, TTB_KS, 4, SwzK128>(rB, smem + 3 * TTB_TILE_BYTES, ldb_b, N, K, col0, TTB_KS, wave, lane);
     }
     for (int s = 0; s < nstages; ++s) {
         if (s + 1 < nstages) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");     // 8 LDS-DMA instructions per wave per stage
@@ -1178,8 +997,8 @@ __device__ __forceinline__ void tt128_tile(const mtn_gemm_problem& P, const Adam
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                a[ks][i] = ttb_frag(sA, wr * 64 + i * 16, ks, l15, lg);
-                b[ks][i] = ttb_frag(sB, wc * 64 + i * 16, ks, l15, lg);
+                a[ks][i] = tr_frag<256, SwzK128>(sA, ks * 32, wr * 64 + i * 16, l15, lg);
+                b[ks][i] = tr_frag<256, SwzK128>(sB, ks * 32, wc * 64 + i * 16, l15, lg);
             }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -1197,8 +1016,8 @@ __device__ __forceinline__ void tt128_tile(const mtn_gemm_problem& P, const Adam
         if (s + 2 < nstages) {
             __builtin_amdgcn_s_barrier();
             unsigned char* dst = smem + (s & 1) * 2 * TTB_TILE_BYTES;
-            ttb_issue_tile(rA, dst, lda_b, M, K, row0, (s + 2) * TTB_KS, wave, lane);
-            ttb_issue_tile(rB, dst + TTB_TILE_BYTES, ldb_b, N, K, col0, (s + 2) * TTB_KS, wave, lane);
+            dma_issue_kn<256, TTB_KS, 4, SwzK128>(rA, dst, lda_b, M, K, row0, (s + 2) * TTB_KS, wave, lane);
+            dma_issue_kn<256, TTB_KS, 4, SwzK128>(rB, dst + TTB_TILE_BYTES, ldb_b, N, K, col0, (s + 2) * TTB_KS, wave, lane);
         }
     }
     if (do_rowsum && wc == 0 && lg == 0) {
@@ -1463,116 +1282,12 @@ __global__ __launch_bounds__(256, 2) void gemm_tt_dma128_table_kernel(const TTHe
 }
 
 // ====================================================================================================================
-// Row-major x row-major (both operands contraction-contiguous) with 128 x 128 output tiles, for launches with enough tiles
-// to fill the chip (memory K/V projections of all layers, the loss head, the memory-gradient groups): half the operand bytes
-// per output of the 64 x 64 kernels.  Stage = (128 + 128) rows x 64 contraction elements (128 B per row) = 32 KiB, two stages,
-// two workgroups per CU, 4 waves x (4 x 4) MFMA tiles.  128-byte rows: two rows per sweep of the LDS banks, 16-byte slots
-// XOR-swizzled with (row & 7) -> the 16 lanes one ds_read_b128 cycle serves hit 16 different slots.
-// ====================================================================================================================
-static constexpr int NTB_BK = 64;                          // contraction elements per stage (bf16)
-static constexpr int NTB_TILE_BYTES = 128 * 128;           // one operand tile per stage: 128 rows x 128 B
-static constexpr int NTB_LDS = 4 * NTB_TILE_BYTES;         // 64 KiB
-
-__device__ __forceinline__ void ntb_issue_tile(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_tile, int ld_bytes, int R, int K,
-                                               int row0, int k0, int wave, int lane) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {                                    // 16 instructions per tile, 4 per wave: 8 rows of 128 B each
-        const int inst = j * 4 + wave;
-        const int row = inst * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ (row & 7);                        // source chunk that lands in slot (lane & 7)
-        const int gk = k0 + c * 8;
-        int grow = row0 + row;
-        grow = grow < R ? grow : R - 1;                              // rows past the end only feed outputs that are never stored
-        unsigned voff = (gk < K) ? (unsigned)grow * (unsigned)ld_bytes + (unsigned)gk * 2u : 0x80000000u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(lds_tile + inst * 1024), 16, voff, 0, 0, 0);
-    }
-}
-
-__global__ __launch_bounds__(256, 2) void gemm_dma128_kernel(const GemmGroup grp) {
-    typedef bf16_t T;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x;
-    int g = 0;
-    while (g + 1 < grp.count && (int)blockIdx.x >= grp.tile_start[g + 1]) ++g;
-    const mtn_gemm_problem& P = grp.p[g];
-    const int M = P.M, N = P.N, K = P.K;
-    const int tiles_n = (N + 127) / 128;
-    const int t = (int)blockIdx.x - grp.tile_start[g];
-    const int tiles_m = (M + 128 - 1) / 128;
-    int tm_, tn_;
-    xcd_tile(grp, g, t, tiles_m * tiles_n, tiles_m, tiles_n, M >= N, tm_, tn_);
-    const int row0 = tm_ * 128, col0 = tn_ * 128;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 1, wc = wave & 1, lg = lane >> 4, l15 = lane & 15;
-    const int lda_b = P.lda * 2, ldb_b = P.ldb * 2;
-    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)P.A, 0, (M - 1) * lda_b + K * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)P.B, 0, (N - 1) * ldb_b + K * 2, 0x00020000);
-
-    f32x4_t acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    const int nstages = (K + NTB_BK - 1) / NTB_BK;
-    ntb_issue_tile(rA, smem, lda_b, M, K, row0, 0, wave, lane);
-    ntb_issue_tile(rB, smem + NTB_TILE_BYTES, ldb_b, N, K, col0, 0, wave, lane);
-    if (nstages > 1) {
-        ntb_issue_tile(rA, smem + 2 * NTB_TILE_BYTES, lda_b, M, K, row0, NTB_BK, wave, lane);
-        ntb_issue_tile(rB, smem + 3 * NTB_TILE_BYTES, ldb_b, N, K, col0, NTB_BK, wave, lane);
-    }
-    const DropState ds = drop_init(P.drop);
-    for (int s = 0; s < nstages; ++s) {
-        if (s + 1 < nstages) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");     // 8 LDS-DMA instructions per wave per stage
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        const unsigned char* sA = smem + (s & 1) * 2 * NTB_TILE_BYTES;
-        const unsigned char* sB = sA + NTB_TILE_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {                               // 32 contraction elements = one 16-byte chunk per lane group
-            uint4 a[4], b[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int ra = wr * 64 + i * 16 + l15, rb = wc * 64 + i * 16 + l15;
-                a[i] = *(const uint4*)(sA + ra * 128 + (((ks * 4 + lg) ^ (ra & 7)) << 4));
-                b[i] = *(const uint4*)(sB + rb * 128 + (((ks * 4 + lg) ^ (rb & 7)) << 4));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mma16<T>(acc[i][j], b[j], a[i]);     // transposed accumulator (vector epilogue)
-        }
-        if (s + 2 < nstages) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            unsigned char* dst = smem + (s & 1) * 2 * NTB_TILE_BYTES;
-            ntb_issue_tile(rA, dst, lda_b, M, K, row0, (s + 2) * NTB_BK, wave, lane);
-            ntb_issue_tile(rB, dst + NTB_TILE_BYTES, ldb_b, N, K, col0, (s + 2) * NTB_BK, wave, lane);
-        }
-    }
-    const bool vec_ok = ((N | P.ldc | (P.residual ? P.ldr : 0)) & 3) == 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = row0 + wr * 64 + i * 16 + l15;
-        if (row >= M) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int col = col0 + wc * 64 + j * 16 + lg * 4;
-            if (col >= N) continue;
-            epilogue4<T>(P, ds, vec_ok && col + 3 < N, row, col, N, acc[i][j]);
-        }
-    }
-}
-
-// ---------------------------------------------------------------- launch census (measurement support, bench.py)
-// While recording, every mtn_gemm call keeps a copy of its problem list; mtn_census_replay re-issues a recorded launch so
-// ====================================================================================================================
-// 128 x 128 output tiles, 512 threads, FOUR stages of 64 contraction elements in LDS (round 3).  For launches of one round of big
+// 128 x 128 output tiles, 1 024 threads, FOUR stages of 64 contraction elements in LDS (round 3).  For launches of one round of big
 // tiles with a long contraction — the memory-gradient GEMM dmem = dkv Wkv ([8 064 x 512 x 1 024]: 252 tiles) was 1 008 tiles of
 // 64 x 64 on half stages, 31 us: every CU pulled 1 MiB where 512 KiB do.  A row-major [128 rows][64 k]; B either row-major
-// [128 n][64 k] or (BTR) as the weight lies, [64 k][128 n] (256-byte rows, the table kernel's loader and transposing fragment
-// reads).  8 waves = 2 row halves x 4 column quarters, wave tile 64 x 32 (4 x 2 MFMA tiles).  Stage s+3 is issued while stage s
+// [128 n][64 k] or (BTR) as the weight lies, [64 k][128 n] (256-byte rows, the table kernel's swizzle and transposing fragment
+// reads).  16 waves = 4 row quarters x 4 column quarters, wave tile 32 x 32 (2 x 2 MFMA tiles): they pull the stages
+// faster than the 8 of round 3 did (a CU's fill rate grows with its resident waves; +0.5 %).  Stage s+3 is issued while stage s
 // is computed: three stages (96 KiB) in flight per workgroup, counted vmcnt, ONE barrier per stage; every fragment read is
 // inline asm (see gemm_dma_kernel: a visible LDS read would drain the stages in flight).
 // ====================================================================================================================
@@ -1582,12 +1297,10 @@ static constexpr int G8_STAGE = 2 * G8_OP_BYTES;           // 32 KiB
 static constexpr int G8_NST = 4;
 static constexpr int G8_LDS = G8_NST * G8_STAGE;           // 128 KiB
 
-// NW = 16 waves (1 024 threads, wave tile 32 x 32) pull the stages faster than 8 (a CU's fill rate grows with its resident waves).
-template <bool BTR, int NW = 16, bool LNE = false>
-__global__ __launch_bounds__(64 * NW) void gemm_dma128x_kernel(const GemmGroup grp, const typename LnArg<LNE>::type lne) {
-    constexpr int WR = NW / 4;                                     // waves down the rows (2 or 4); four across the columns
-    constexpr int TM = 128 / (16 * WR);                            // MFMA tiles per wave down the rows (4 or 2)
-    constexpr int IPW = 16 / NW;                                   // LDS-DMA instructions per wave per operand per stage (2 or 1)
+template <bool BTR, bool LNE = false>
+__global__ __launch_bounds__(1024) void gemm_dma128x_kernel(const GemmGroup grp, const typename LnArg<LNE>::type lne) {
+    constexpr int NW = 16;                                         // waves: four down the rows, four across the columns
+    constexpr int TM = 2;                                          // MFMA tiles per wave down the rows
     typedef bf16_t T;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
@@ -1607,36 +1320,12 @@ __global__ __launch_bounds__(64 * NW) void gemm_dma128x_kernel(const GemmGroup g
     const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)P.A, 0, (M - 1) * lda_b + K * 2, 0x00020000);
     const __amdgpu_buffer_rsrc_t rB = BTR ? __builtin_amdgcn_make_buffer_rsrc((void*)P.B, 0, (K - 1) * ldb_b + N * 2, 0x00020000)
                                           : __builtin_amdgcn_make_buffer_rsrc((void*)P.B, 0, (N - 1) * ldb_b + K * 2, 0x00020000);
-    // 2 * IPW LDS-DMA instructions per wave per stage, always: IPW for A (8 rows of 128 B each), IPW for B
-    auto issue_rows = [&](__amdgpu_buffer_rsrc_t rs, unsigned char* dst, int ld_bytes, int R, int r0, int k0) {
-#pragma unroll
-        for (int j = 0; j < IPW; ++j) {
-            const int inst = j * NW + wave;
-            const int row = inst * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ (row & 7);                    // source chunk that lands in slot (lane & 7)
-            const int gk = k0 + c * 8;
-            int grow = r0 + row;
-            grow = grow < R ? grow : R - 1;                          // rows past the end only feed outputs that are never stored
-            unsigned voff = (gk < K) ? (unsigned)grow * (unsigned)ld_bytes + (unsigned)gk * 2u : 0x80000000u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(dst + inst * 1024), 16, voff, 0, 0, 0);
-        }
-    };
-    auto issue_kn = [&](unsigned char* dst, int k0) {               // B as it lies: [64 k][128 n], 4 k-rows of 256 B per instruction
-#pragma unroll
-        for (int j = 0; j < IPW; ++j) {
-            const int inst = j * NW + wave;
-            const int krow = inst * 4 + (lane >> 4);
-            const int c = (lane & 15) ^ ttb_swz(krow);
-            const int gk = k0 + krow, gn = col0 + c * 8;
-            unsigned voff = (gk < K && gn < N) ? (unsigned)gk * (unsigned)ldb_b + (unsigned)gn * 2u : 0x80000000u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_void_t*)(dst + inst * 1024), 16, voff, 0, 0, 0);
-        }
-    };
+    // two LDS-DMA instructions per wave per stage, always: one for A (8 rows of 128 B), one for B (8 rows, or BTR: 4 k-rows of 256 B)
     auto issue = [&](int st) {
         unsigned char* dst = smem + (st & (G8_NST - 1)) * G8_STAGE;
-        issue_rows(rA, dst, lda_b, M, row0, st * G8_BK);
-        if constexpr (BTR) issue_kn(dst + G8_OP_BYTES, st * G8_BK);
-        else issue_rows(rB, dst + G8_OP_BYTES, ldb_b, N, col0, st * G8_BK);
+        dma_issue_rows<T, 128, 128, NW>(rA, dst, lda_b, M, K, row0, st * G8_BK, wave, lane);
+        if constexpr (BTR) dma_issue_kn<256, G8_BK, NW, SwzK128>(rB, dst + G8_OP_BYTES, ldb_b, N, K, col0, st * G8_BK, wave, lane);
+        else dma_issue_rows<T, 128, 128, NW>(rB, dst + G8_OP_BYTES, ldb_b, N, K, col0, st * G8_BK, wave, lane);
     };
 
     f32x4_t acc[TM][2];
@@ -1658,8 +1347,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_dma128x_kernel(const GemmGroup g
     const DropState ds = drop_init(P.drop);
     for (int s = 0; s < nstages; ++s) {
         const int ahead = nstages - 1 - s;                           // stages issued behind this one: min(ahead, 2) may still fly
-        if (ahead >= 2) { if constexpr (IPW == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-        else if (ahead == 1) { if constexpr (IPW == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
+        if (ahead >= 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else if (ahead == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if constexpr (LNE) { if (lne_slot != 0) ln_consume_publish<TM, 2>(lnq, tid, (float*)(smem + G8_LDS)); }       // (see gemm_dma_kernel)
@@ -1679,7 +1368,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_dma128x_kernel(const GemmGroup g
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 if constexpr (BTR) {
-                    const uint4 f = ttb_frag(sB, wc * 32 + j * 16, ks, l15, lg);
+                    const uint4 f = tr_frag<256, SwzK128>(sB, ks * 32, wc * 32 + j * 16, l15, lg);
                     b[j] = u32x4_t{f.x, f.y, f.z, f.w};
                 } else {
                     const int rb = wc * 32 + j * 16 + l15;
@@ -1732,7 +1421,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_dma128x_kernel(const GemmGroup g
     }
 }
 
-
+// ---------------------------------------------------------------- launch census (measurement support, bench.py)
+// While recording, every mtn_gemm call keeps a copy of its problem list; mtn_census_replay re-issues a recorded launch so
 // that the caller can time each of the step's GEMM launches with HIP events on the launch stream.
 #include <algorithm>
 #include <vector>
@@ -1748,44 +1438,44 @@ static int g_variant = 0, g_variant_tiles = 0;     // set by launch_gemm: which 
 enum { V_REG_NN = 0, V_REG_NT, V_REG_TN, V_REG_TT, V_DMA64, V_DMA3264, V_DMA32, V_TT_DMA, V_TT128, V_TT_DMA128, V_DMA128, V_DMA64H, V_DMA32H, V_TT_TABLE, V_K512, V_DMA128X, V_COUNT };
 static const char* const g_variant_name[V_COUNT] = {
     "gemm_kernel<N,N> 64x64 reg-staged", "gemm_kernel<N,T>", "gemm_kernel<T,N>", "gemm_kernel<T,T> 64x64 reg-staged",
-    "gemm_dma_kernel<64,64>", "gemm_dma_kernel<32,64>", "gemm_dma_kernel<32,32>", "gemm_tt_dma_kernel", "(gemm_tt128_kernel: removed in round 5)",
-    "gemm_tt_dma128_kernel", "gemm_dma128_kernel", "gemm_dma_kernel<64,64> half stages", "gemm_dma_kernel<32,32> half stages", "gemm_tt_dma128_table_kernel", "gemm_k512_kernel", "gemm_dma128x_kernel (128x128, four stages)"};
+    "gemm_dma_kernel<64,64>", "(gemm_dma_kernel<32,64>: removed)", "gemm_dma_kernel<32,32>", "gemm_tt_dma_kernel", "(gemm_tt128_kernel: removed in round 5)",
+    "gemm_tt_dma128_kernel", "(gemm_dma128_kernel: removed)", "gemm_dma_kernel<64,64> half stages", "gemm_dma_kernel<32,32> half stages", "gemm_tt_dma128_table_kernel", "gemm_k512_kernel", "gemm_dma128x_kernel (128x128, four stages)"};
 
-template <typename T, int BM, int BN, int ROWB, bool BTR = false, int NBUF = 2, int NW = 4, bool LNE = false>
+template <typename T, int BM, int BN, int ROWB, bool BTR = false, int NW = 4, bool LNE = false>
 static int launch_dma_impl(const GemmGroup& grp, const typename LnArg<LNE>::type& lne, int tiles, hipStream_t s) {
-    g_variant = (BM == 64) ? (ROWB == 512 ? V_DMA64 : V_DMA64H) : (BN == 64 ? V_DMA3264 : (ROWB == 512 ? V_DMA32 : V_DMA32H));
+    g_variant = (BM == 64) ? (ROWB == 512 ? V_DMA64 : V_DMA64H) : (ROWB == 512 ? V_DMA32 : V_DMA32H);
     g_variant_tiles = tiles;
-    constexpr int LDS = NBUF * (BM + BN) * ROWB + (LNE ? LNE_LDS_EXTRA : 0);       // (+ the LayerNorm epilogue's row-sum scratch)
+    constexpr int LDS = 2 * (BM + BN) * ROWB + (LNE ? LNE_LDS_EXTRA : 0);       // two stages (+ the LayerNorm epilogue's row-sum scratch)
     static bool attr_set = false;          // > 64 KiB of dynamic LDS needs the opt-in once per kernel
     if (!attr_set && LDS > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_kernel<T, BM, BN, ROWB, BTR, NBUF, NW, LNE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_kernel<T, BM, BN, ROWB, BTR, NW, LNE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         if (e != hipSuccess) { mtn_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return MTN_ERR_LAUNCH; }
         attr_set = true;
     }
-    hipLaunchKernelGGL((gemm_dma_kernel<T, BM, BN, ROWB, BTR, NBUF, NW, LNE>), dim3(tiles), dim3(64 * NW), LDS, s, grp, lne);
+    hipLaunchKernelGGL((gemm_dma_kernel<T, BM, BN, ROWB, BTR, NW, LNE>), dim3(tiles), dim3(64 * NW), LDS, s, grp, lne);
     MTN_CHECK_LAUNCH();
     return MTN_OK;
 }
 // `lne` (launches with a LayerNorm epilogue, mtn_ln_epilogue): only the tile shapes the step's launches take are instantiated with it —
 // bf16, a square tile whose rows are dealt to groups of eight threads (64 x 64 on eight waves, 32 x 32 on four), either B layout
-template <typename T, int BM, int BN, int ROWB, bool BTR = false, int NBUF = 2, int NW = 4>
+template <typename T, int BM, int BN, int ROWB, bool BTR = false, int NW = 4>
 static int launch_dma(const GemmGroup& grp, int tiles, hipStream_t s, const LnEpiGroup* lne = nullptr) {
     if (lne) {
-        if constexpr (sizeof(T) == 2 && NBUF == 2 && (64 * NW == 8 * BM || (NW == 16 && BM == 64)) && BM == BN)
-            return launch_dma_impl<T, BM, BN, ROWB, BTR, NBUF, NW, true>(grp, *lne, tiles, s);
+        if constexpr (sizeof(T) == 2 && (64 * NW == 8 * BM || (NW == 16 && BM == 64)) && BM == BN)
+            return launch_dma_impl<T, BM, BN, ROWB, BTR, NW, true>(grp, *lne, tiles, s);
         mtn_set_error("mtn_gemm: no LayerNorm-epilogue form of this kernel (tile %d x %d, stage %d B, %d waves)", BM, BN, ROWB, NW);
         return MTN_ERR_ARG;
     }
-    return launch_dma_impl<T, BM, BN, ROWB, BTR, NBUF, NW, false>(grp, NoLn{}, tiles, s);
+    return launch_dma_impl<T, BM, BN, ROWB, BTR, NW, false>(grp, NoLn{}, tiles, s);
 }
 
 // row-major B, or (btr: bf16 only) B stored [K][N]
-template <typename T, int BM, int BN, int ROWB, int NBUF = 2, int NW = 4>
+template <typename T, int BM, int BN, int ROWB, int NW = 4>
 static int launch_dma_any(const GemmGroup& grp, int tiles, bool btr, hipStream_t s, const LnEpiGroup* lne = nullptr) {
     if constexpr (sizeof(T) == 2) {
-        if (btr) return launch_dma<T, BM, BN, ROWB, true, NBUF, NW>(grp, tiles, s, lne);
+        if (btr) return launch_dma<T, BM, BN, ROWB, true, NW>(grp, tiles, s, lne);
     }
-    return launch_dma<T, BM, BN, ROWB, false, NBUF, NW>(grp, tiles, s, lne);
+    return launch_dma<T, BM, BN, ROWB, false, NW>(grp, tiles, s, lne);
 }
 
 // tile_start[] for a given tile shape; returns the total
@@ -1809,34 +1499,6 @@ static int launch_gemm(const GemmGroup& grp, const AdamGroup& adam, int total_ti
     g_variant_tiles = total_tiles;
     g_variant = at ? (bt ? V_REG_TT : V_REG_TN) : (bt ? V_REG_NT : V_REG_NN);
     if constexpr (sizeof(T) == 2) {
-        // 128x128 row-major tiles: measured 330-350 TFLOP/s on the memory K/V launches against 370-400 for the 64x64
-        // register-staged kernel at 5 workgroups per CU (K = 512 is too short to amortise a 16-fragment epilogue at two
-        // workgroups per CU) -> opt-in (MTN_GEMM_NTB_MIN_TILES=<tiles>), kept for larger contractions
-        if (!at && !bt && !lne && MTN_ENV("MTN_GEMM_NTB_MIN_TILES") != nullptr) {
-            bool ok = true;
-            int t128 = 0;
-            for (int i = 0; i < grp.count; ++i) {
-                const mtn_gemm_problem& q = grp.p[i];
-                ok = ok && !q.rowsum_out && q.K % 8 == 0 && (long)q.M * q.lda * 2 < (1L << 31) && (long)q.N * q.ldb * 2 < (1L << 31);
-                t128 += ((q.M + 127) / 128) * ((q.N + 127) / 128);
-            }
-            const char* tmin = MTN_ENV("MTN_GEMM_NTB_MIN_TILES");
-            if (ok && t128 >= atoi(tmin)) {
-                static bool attr_set = false;
-                if (!attr_set) {
-                    (void)hipFuncSetAttribute((const void*)gemm_dma128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NTB_LDS);
-                    attr_set = true;
-                }
-                GemmGroup g2 = grp;
-                const int tiles = retile(g2, 128, 128);
-                g_variant = V_DMA128; g_variant_tiles = tiles;
-                hipLaunchKernelGGL(gemm_dma128_kernel, dim3(tiles), block, NTB_LDS, s, g2);
-                MTN_CHECK_LAUNCH();
-                return MTN_OK;
-            }
-        }
-    }
-    if constexpr (sizeof(T) == 2) {
         // one round (or a few) of 128 x 128 tiles with four stages in flight: launches with >= 192 such tiles and a contraction of
         // >= 768 (at K = 512 the register-staged 64 x 64 kernel is as fast: 18.4 vs 19.0 us on the generator logits), either B layout:
         // the memory-gradient GEMM 23.6 -> 17.3 us per launch, step +0.9 % (profiles/r03_w_gemm128x_ab.txt)
@@ -1855,11 +1517,9 @@ static int launch_gemm(const GemmGroup& grp, const AdamGroup& adam, int total_ti
             static int attr_state = 0;                                  // 0 = not tried, 1 = the 128 KiB dynamic-LDS opt-in holds, -1 = refused
             if (ok && t128 >= x_min && (xmin || kmax >= 768) && attr_state == 0) {
                 const bool good =
-                    hipFuncSetAttribute((const void*)gemm_dma128x_kernel<false, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) == hipSuccess &&
-                    hipFuncSetAttribute((const void*)gemm_dma128x_kernel<true, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) == hipSuccess &&
-                    hipFuncSetAttribute((const void*)gemm_dma128x_kernel<false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) == hipSuccess &&
-                    hipFuncSetAttribute((const void*)gemm_dma128x_kernel<true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) == hipSuccess &&
-                    hipFuncSetAttribute((const void*)gemm_dma128x_kernel<true, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS + LNE_LDS_EXTRA) == hipSuccess;
+                    hipFuncSetAttribute((const void*)gemm_dma128x_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) == hipSuccess &&
+                    hipFuncSetAttribute((const void*)gemm_dma128x_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) == hipSuccess &&
+                    hipFuncSetAttribute((const void*)gemm_dma128x_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS + LNE_LDS_EXTRA) == hipSuccess;
                 attr_state = good ? 1 : -1;                              // refused: this and every later launch take the 64 x 64 / register-staged kernels below
                 if (!good) (void)hipGetLastError();
             }
@@ -1867,10 +1527,10 @@ static int launch_gemm(const GemmGroup& grp, const AdamGroup& adam, int total_ti
                 GemmGroup g2 = grp;
                 const int tiles = retile(g2, 128, 128);
                 g_variant = V_DMA128X; g_variant_tiles = tiles;
-                if (lne) hipLaunchKernelGGL((gemm_dma128x_kernel<true, 16, true>), dim3(tiles), dim3(1024), G8_LDS + LNE_LDS_EXTRA, s, g2, *lne);
+                if (lne) hipLaunchKernelGGL((gemm_dma128x_kernel<true, true>), dim3(tiles), dim3(1024), G8_LDS + LNE_LDS_EXTRA, s, g2, *lne);
                 else {                 // (sixteen waves: +0.5 % against eight, round 3)
-                    if (bt) hipLaunchKernelGGL((gemm_dma128x_kernel<true, 16>), dim3(tiles), dim3(1024), G8_LDS, s, g2, NoLn{});
-                    else hipLaunchKernelGGL((gemm_dma128x_kernel<false, 16>), dim3(tiles), dim3(1024), G8_LDS, s, g2, NoLn{});
+                    if (bt) hipLaunchKernelGGL((gemm_dma128x_kernel<true>), dim3(tiles), dim3(1024), G8_LDS, s, g2, NoLn{});
+                    else hipLaunchKernelGGL((gemm_dma128x_kernel<false>), dim3(tiles), dim3(1024), G8_LDS, s, g2, NoLn{});
                 }
                 MTN_CHECK_LAUNCH();
                 return MTN_OK;
@@ -1894,7 +1554,6 @@ static int launch_gemm(const GemmGroup& grp, const AdamGroup& adam, int total_ti
         const char* force = MTN_ENV("MTN_GEMM_TILE");
         int f = force ? atoi(force) : 0;
         if (lne_emit) f = 64;                          // the emitted row-sum partials are per 64-column block
-        if (lne && f == 3264) f = 0;
         double b64 = 0, b32 = 0, wg32max = 0;
         int t64 = 0;
         for (int i = 0; i < grp.count; ++i) {
@@ -1913,30 +1572,25 @@ static int launch_gemm(const GemmGroup& grp, const AdamGroup& adam, int total_ti
         if (c32 < wg32max) c32 = wg32max;
         // half-size stages (256 B of contraction per row) double the resident workgroups: taken when the launch would
         // otherwise need a second round (64x64: one workgroup per CU at 128 KiB; 32x32: two at 64 KiB)
-        const bool half_ok = true;
         const bool half_force = MTN_ENV("MTN_GEMM_FORCE_HALF") != nullptr;      // tests
         {   // eight waves pull a 64 x 64 workgroup's bytes faster than four did when the 0.75 above was fitted: the 64 x 64 cost is
             // weighted 0.8 (sweep in profiles/r03_ac_c64_scale_sweep.txt: cfg2 +0.3 %, batch 64 +2.1 % against 1.0; 0.5 loses)
             c64 *= 0.8;
         }
-        // (a ring of four half-size stages for long contractions was measured at -0.8 % on the cfg2 step, profiles/r03_x_deep_ring_ab.txt: not kept)
         if (f == 64 || (!f && c64 <= c32)) {
             const int t = retile(g2, 64, 64, true);
-            if (half_force || (half_ok && t > 256)) {
-                return launch_dma_any<T, 64, 64, 256, 2, 8>(g2, t, bt, s, lne);       // (eight waves: four were the rounds 1-2 form)
-            }
+            if (half_force || t > 256) return launch_dma_any<T, 64, 64, 256, 8>(g2, t, bt, s, lne);       // (eight waves: four were the rounds 1-2 form)
             if constexpr (sizeof(T) == 2) {
                 // sixteen waves (a 4 x 4 grid of 16 x 16 wave tiles): cfg2 step +0.6 %, batch 64 +0.4 % against eight (profiles/r04_s_nw16_ab.txt).
                 // MTN_GEMM_NW16 = 0 none, 1 plain launches only, 2 launches with a LayerNorm epilogue only (default 3: both)
                 const char* n16 = MTN_ENV("MTN_GEMM_NW16");
                 const int m16 = n16 ? atoi(n16) : 3;
-                if (((m16 & 1) && !lne) || ((m16 & 2) && lne)) return launch_dma_any<T, 64, 64, 512, 2, 16>(g2, t, bt, s, lne);
+                if (((m16 & 1) && !lne) || ((m16 & 2) && lne)) return launch_dma_any<T, 64, 64, 512, 16>(g2, t, bt, s, lne);
             }
-            return launch_dma_any<T, 64, 64, 512, 2, 8>(g2, t, bt, s, lne);     // eight waves: see the kernel
+            return launch_dma_any<T, 64, 64, 512, 8>(g2, t, bt, s, lne);     // eight waves: see the kernel
         }
-        if (f == 3264) return launch_dma_any<T, 32, 64, 512>(g2, retile(g2, 32, 64, true), bt, s);
         const int t = retile(g2, 32, 32, true);
-        if (half_force || (half_ok && t > 1024)) return launch_dma_any<T, 32, 32, 256>(g2, t, bt, s, lne);   // (measured in the step: 640 tiles 10.7 vs 10.1 us, 1280 tiles 12.7 vs 13.8 us)
+        if (half_force || t > 1024) return launch_dma_any<T, 32, 32, 256>(g2, t, bt, s, lne);   // (measured in the step: 640 tiles 10.7 vs 10.1 us, 1280 tiles 12.7 vs 13.8 us)
         return launch_dma_any<T, 32, 32, 512>(g2, t, bt, s, lne);
     } else if (!at && !bt) hipLaunchKernelGGL((gemm_kernel<T, false, false>), grid, block, 0, s, grp, NoAdam{});
     else if (!at && bt) hipLaunchKernelGGL((gemm_kernel<T, false, true>), grid, block, 0, s, grp, NoAdam{});

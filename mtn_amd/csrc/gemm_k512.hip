@@ -34,7 +34,7 @@ __global__ __launch_bounds__(GK_THREADS) void gemm_k512_kernel(const GkGroup G) 
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(P.A + (size_t)row0 * P.lda), 0, (R - 1) * ldab + FH_ROWB, 0x00020000);
         for (int r = wave; r < 128; r += 8) {
             const unsigned vo = r < R ? (unsigned)r * ldab + (unsigned)((lane ^ (r & 15)) << 4) : 0x80000000u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (fh_lds_void_t*)(smem + r * FH_ROWB), 16, vo, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(smem + r * FH_ROWB), 16, vo, 0, 0, 0);
         }
     }
     uint4 wf[16];
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(GK_THREADS, 2) void gemm_k512p_kernel(const GkGroup
         for (int i = 0; i < GP_ROWS / 4; ++i) {
             const int r = wave + 4 * i;
             const unsigned vo = r < R ? (unsigned)r * ldab + (unsigned)((lane ^ (r & 15)) << 4) : 0x80000000u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (fh_lds_void_t*)(img + r * FH_ROWB), 16, vo, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(img + r * FH_ROWB), 16, vo, 0, 0, 0);
         }
     };
     uint4 wf[16];

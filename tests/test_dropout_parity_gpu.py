@@ -185,7 +185,7 @@ def _gemm_problem(L, A, B, M, N, K, at, bt, lda, ldb):
 
 
 GEMM_VARIANTS = [("reg", {}, "gemm_kernel<N,N>"), ("dma64", {"MTN_GEMM_TILE": "64"}, "gemm_dma_kernel<64,64>"),
-                 ("dma32", {"MTN_GEMM_TILE": "32"}, "gemm_dma_kernel<32,32>"), ("dma128", {"MTN_GEMM_NTB_MIN_TILES": "1"}, "gemm_dma128_kernel"),
+                 ("dma32", {"MTN_GEMM_TILE": "32"}, "gemm_dma_kernel<32,32>"),
                  ("dma128x", {"MTN_GEMM_128X_MIN_TILES": "1"}, "gemm_dma128x_kernel")]
 GEMM_SHAPES = [(96, 128, 256), (33, 64, 256), (200, 192, 320)]          # ragged M as in test_gemm_epilogue_and_group; K >= 256 lets the 128x kernel take them
 GEMM_SALTS = [4 * 11 + 1, 0x80000000 + 4 * 3 + 2, 4 * 300 + 2]
@@ -205,10 +205,10 @@ def test_gemm_epilogue_drop(dev, dtype, variant, p):
       after   bias + residual, lp_drop_after_residual -> out_f32 unmasked; out_lp exactly zero where dropped
     Bars of test_gemm_epilogue_and_group: 2e-4 on out_f32, 1e-5 (fp32) / 1e-2 (bf16) on out_lp.  The kernel family is forced the way
     test_gemm_contraction_major_b_on_lds_dma does and checked in the launch census (the register-staged kernel is taken by asking for
-    row sums; the 128-row kernels are bf16 only)."""
+    row sums; the 128-row kernel is bf16 only)."""
     from mtn_amd import lib as L, ops
     name, env, kernel = next(v for v in GEMM_VARIANTS if v[0] == variant)
-    if dtype == torch.float32 and variant in ("dma128", "dma128x"):
+    if dtype == torch.float32 and variant == "dma128x":
         kernel = "gemm_dma_kernel"                          # no fp32 form: the launch stays on the LDS-DMA 64 / 32 tiles
     lib = L.load()
     g = torch.Generator().manual_seed(5)

@@ -65,7 +65,7 @@ def main():
 
     for label, shapes in CASES:
         print(label)
-        for env in ({}, {"MTN_GEMM_TILE": "64"}, {"MTN_GEMM_TILE": "32"}, {"MTN_GEMM_TILE": "3264"}, {"MTN_GEMM_128X_MIN_TILES": "0"}, {"MTN_GEMM_128X_MIN_TILES": "1"}):
+        for env in ({}, {"MTN_GEMM_TILE": "64"}, {"MTN_GEMM_TILE": "32"}, {"MTN_GEMM_128X_MIN_TILES": "0"}, {"MTN_GEMM_128X_MIN_TILES": "1"}):
             os.environ.update(env)
             L.reload_env()
             row = []

@@ -18,10 +18,6 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-# the cases must run on gemm_dma_kernel (the kernel whose traffic is in question), whatever their tile count
-os.environ["MTN_GEMM_DMA_MAX_TILES"] = "100000000"
-os.environ["MTN_GEMM_K512_MIN_TILES"] = "0"
-os.environ["MTN_GEMM_NO_HALF"] = "1"
 
 # name -> (M, N, K, residual fp32?, out fp32?)       A [M,K] bf16 is read once; B [N,K] is tiny; C [M,N]
 CASES = {
