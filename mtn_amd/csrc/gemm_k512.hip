@@ -368,8 +368,10 @@ int gemm_k512_try(int count, const mtn_gemm_problem* p, int min_tiles, hipStream
         if (tiles_out) *tiles_out = GP_GRID;
         return 1;
     }
-    // wide tiles (128 x 256) when every problem's N fills them: half the LDS reads per FLOP (MTN_K512_WIDE=0: 128 x 128 tiles)
-    bool wide = true;
+    // wide tiles (128 x 256) when every problem's N fills them: half the LDS reads per FLOP.  MTN_K512_WIDE=0 keeps the 128 x 128 tiles
+    // on such a launch too (same arithmetic per output element: the tests compare the two forms on one problem set)
+    const char* we = MTN_ENV("MTN_K512_WIDE");
+    bool wide = !(we && we[0] == '0');
     for (int i = 0; i < count; ++i) wide = wide && (p[i].N % 256) == 0;
     if (wide) {
         if (!gk_wide_attr()) return 0;
