@@ -49,7 +49,7 @@ const char* mtn_last_error(void);
  * 123: new entry points mtn_distill_fwd / _bwd.  124: new entry points mtn_lerp_f32, mtn_ema_step and mtn_swap_f32.
  * 125: new entry points mtn_wlosshead_fwd / _bwd, mtn_eval_table_build, mtn_eval_score_rows, mtn_scst_assemble and mtn_scst_advantage.
  * Entry points added since (mtn_ulosshead_fwd / _bwd; mtn_grad_sumsq_partials, mtn_grad_sumsq, mtn_clip_scale; mtn_grad_accum;
- * mtn_sched_mix) are detected by symbol: additions only, the version stays 125. */
+ * mtn_sched_mix; mtn_rlosshead_fwd / _bwd) are detected by symbol: additions only, the version stays 125. */
 int mtn_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -633,6 +633,52 @@ typedef struct {
 } mtn_ulosshead_args;
 int mtn_ulosshead_fwd(const mtn_ulosshead_args* args, void* stream);
 int mtn_ulosshead_bwd(int dtype, const mtn_ulosshead_args* args, void* stream);
+
+/* Loss head with a paired consistency term (csrc/losshead.hip; detected by symbol, mtn_version() stays 125): R-Drop (Liang et al. 2021),
+ * the symmetric KL divergence between the next-token distributions of two passes of one position under independent dropout masks.  Every
+ * field of mtn_losshead_args keeps its meaning.  pair[s] = 0: segment s is unpaired.  pair[s] = N > 0: the segment holds 2 N rows and local
+ * rows i and i + N are the two passes of one position.  For a row i of a paired segment whose OWN target is not <pad>, with partner
+ * j = i +- N, z_i / z_j their logits, m / lg the row maximum and log sum_c exp(z_c - m) of each (lse = m + lg), logp_c = (z_ic - m_i) - lg_i,
+ * logq_c = (z_jc - m_j) - lg_j (the maxima taken out: a common offset between the two rows costs no bits), p = exp(logp), q = exp(logq),
+ * d_c = logp_c - logq_c, scale = coef[s] / *norm[s], KL_ls, td, the zeroed rows and the lone-<pad> quirk the loss head's:
+ *   J       = sum_c (p_c - q_c) d_c          (= KL(p||q) + KL(q||p); every term is >= 0.  Summed in one fixed column order, so the two rows
+ *                                             of a pair hold the same float products in the same order: rowrd[i] == rowrd[i + N] bit for bit)
+ *   kl      = sum_c p_c d_c                  (= KL(p||q), the directed one)              rowkl ([sum rows]) = kl: the backward reads it
+ *   rd      = J / 4                          rowrd (optional, [sum rows]) = rd, unscaled
+ *   rowloss = scale (KL_ls + rd_alpha rd)    lse = as mtn_losshead_fwd writes it
+ *   bwd:      with p_k = exp(z_ik - lse[i]), q_k = exp(z_jk - lse[j]), d_k = (z_ik - lse[i]) - (z_jk - lse[j]), kl = rowkl[i]:
+ *             dlogits_k = *gloss scale [(softmax_k sum(td) - td_k) + rd_alpha / 2 (p_k (d_k - kl) + p_k - q_k)]; columns V..ldd-1 are +0.0.
+ *             Reads logits, lse and rowkl of the forward call.
+ * Both rows of a pair carry rd and the normaliser of a doubled batch counts both passes' tokens, so the sum of rowloss is the mean of the
+ * two passes' label-smoothed losses plus rd_alpha / 4 (KL(p||q) + KL(q||p)) per original token; the 1/2 of the backward is 2 * 1/4: a
+ * row's logits enter its own rd and its partner's.
+ * rd = +0.0, kl = +0.0 and no extra gradient on every row whose target is <pad> (the quirk row included): those rows never read their
+ * partner.  They, every row of a segment with pair[s] == 0, and every segment when rd_alpha == 0 (the host drops pair) run the plain
+ * head's code: lse, rowloss and dlogits are those of mtn_losshead_fwd / _bwd on the same inputs bit for bit, rowrd is +0.0.  No atomics:
+ * two launches on the same inputs give the same bytes.
+ * MTN_ERR_ARG, nothing launched: whatever mtn_losshead_fwd / _bwd refuse; rd_alpha negative or not finite; pair[s] < 0;
+ * rows[s] != 2 * pair[s] on a paired segment; rowkl == NULL with a paired segment and rd_alpha > 0.  Entries past n_seg are not looked at. */
+typedef struct {
+    int n_seg;
+    int rows[MTN_LOSSHEAD_MAX_SEG];
+    const long* target[MTN_LOSSHEAD_MAX_SEG];
+    const float* norm[MTN_LOSSHEAD_MAX_SEG];
+    float coef[MTN_LOSSHEAD_MAX_SEG];
+    int V, ldz, pad;
+    float smoothing;
+    const float* logits;
+    float* lse;
+    float* rowloss;
+    const float* gloss; /* backward: device scalar dL/dloss */
+    void* dlogits;
+    int ldd;
+    int pair[MTN_LOSSHEAD_MAX_SEG];
+    float rd_alpha;
+    float* rowrd; /* optional */
+    float* rowkl; /* forward: written; backward: read */
+} mtn_rlosshead_args;
+int mtn_rlosshead_fwd(const mtn_rlosshead_args* args, void* stream);
+int mtn_rlosshead_bwd(int dtype, const mtn_rlosshead_args* args, void* stream);
 
 /* Transposed compute-dtype weight copies (operand of dX = dY W on the LDS-DMA GEMM path): for each descriptor the
  * [rows, cols] matrix at src+off is written as [cols, rows] at dst+dst_off (v111: the copies have a compact buffer of

@@ -1,6 +1,7 @@
-// losshead.hip — generator log-softmax + label-smoothed KL divergence, fused per row, in its four forms: plain, with teacher soft
+// losshead.hip — generator log-softmax + label-smoothed KL divergence, fused per row, in its five forms: plain, with teacher soft
 // targets (word-level knowledge distillation, Hinton et al. 2015; Kim & Rush 2016), with a signed weight per row (the policy-gradient
-// loss of self-critical sequence training) and with token-level unlikelihood.  include/mtn_hip.h states the contracts of the eight entry points.
+// loss of self-critical sequence training), with token-level unlikelihood and with a paired consistency term (R-Drop, Liang et al. 2021).
+// include/mtn_hip.h states the contracts of the ten entry points.
 //   Generator.forward      : log_softmax(proj(x))                          (mtn.py:62-69)
 //   LabelSmoothing.forward : KLDivLoss(sum)(logp, smoothed one-hot)        (label_smoothing.py:20-32)
 //   SimpleLossCompute      : sum_i coef_i * KL_i / norm_i                  (data_utils.py:133-144)
@@ -23,12 +24,19 @@
 // and <pad>; ul = sum_C -log(max(1 - p_c, 1e-5)), r_c = p_c / (1 - p_c) on unclamped candidates, R their sum.  The set is a bitmap of V bits
 // in the wave's LDS slice (lanes OR the earlier targets in); ul and R come from a walk over its words, the backward sweep tests its own
 // columns' bits, so every dlogits element is written once.  Rows without candidates (<pad>, t = 0, seq_len 0) take the plain path.
+//   paired    rowloss = scale (KL_ls + rd_alpha J / 4)                 dz_k = g scale [(softmax_k * sum(td) - td_k) + rd_alpha / 2 (p_k (d_k - kl) + p_k - q_k)]
+// R-Drop: local rows i and i + N of a paired segment are two passes of one position; p / q their softmaxes, d = log p - log q,
+// J = sum_c (p_c - q_c) d_c = KL(p||q) + KL(q||p) (termwise >= 0, no cancellation), kl = sum_c p_c d_c.  Both rows differentiate through their
+// own softmax (the partner is no constant teacher).  A wave computes its partner's (max, log-sum-exp) itself with the code that wave runs
+// on its own row, and both form the same products in the same column order: the two rowrd of a pair are equal bit for bit.  The forward
+// is three sweeps over both rows (the partner's 12 KB are L2-resident), the backward one, with lse of both rows and kl from the forward.
 // The forms are instantiations of the same code, so a segment without a teacher (or alpha == 0: the host drops the teacher
 // pointers; no (1 - alpha) factor is applied there) and a segment without weights at the loss head's smoothing (the weight is applied by
 // a multiplication of its own, which cannot be contracted into anything) give the plain head's lse, rowloss and dlogits bit for bit.
 // One 64-lane wave per row, float4 loads (z and q of a sweep issued together), wave-shuffle reductions in a fixed order, no atomics.
 // Forward: two sweeps (maxima and S; the sums).  Backward: one sweep; with a teacher one more before it (a running (max, sum-exp) pair
-// per lane for lse(b) — and lse(a) when T != 1, else the forward's lse serves).  HBM/L2-bound: 12 KB per row at V = 3000, 24 KB with a teacher.
+// per lane for lse(b) — and lse(a) when T != 1, else the forward's lse serves).  HBM/L2-bound: 12 KB per row at V = 3000, 24 KB with a teacher
+// or a partner (the paired form: a third forward sweep for the divergence).
 #include "common.h"
 
 #include <math.h>
@@ -37,6 +45,7 @@
 template <typename Args> constexpr bool HEAD_DISTILL = std::is_same_v<Args, mtn_distill_args>;
 template <typename Args> constexpr bool HEAD_WEIGHTED = std::is_same_v<Args, mtn_wlosshead_args>;
 template <typename Args> constexpr bool HEAD_UL = std::is_same_v<Args, mtn_ulosshead_args>;
+template <typename Args> constexpr bool HEAD_RD = std::is_same_v<Args, mtn_rlosshead_args>;
 
 struct HeadRow {
     int seg, local;      // segment (stream) and row inside it
@@ -50,6 +59,7 @@ struct HeadRow {
     bool kd_seg = false;         // the segment is distilled: its hard part carries (1 - alpha)
     int ul_t = 0;                // unlikelihood: position inside the sequence; 0: this row takes the plain path
     const long* ul_prev = nullptr;   // the sequence's targets y_0 .. y_{t-1}
+    int rd_row = -1;             // R-Drop: the partner's flat row; -1: this row takes the plain path
 };
 
 template <typename Args>
@@ -93,6 +103,10 @@ __device__ __forceinline__ HeadRow head_row(const Args& A, int row, int lane) {
             r.ul_t = r.local % T;
             r.ul_prev = A.target[r.seg] + (r.local - r.ul_t);
         }
+    }
+    if constexpr (HEAD_RD<Args>) {
+        const int N = A.pair[r.seg];                        // rows[seg] == 2 N (checked on the host): the partner lies inside the segment
+        if (N > 0 && !r.t_is_pad) r.rd_row = base + (r.local < N ? r.local + N : r.local - N);
     }
     return r;
 }
@@ -221,8 +235,51 @@ __global__ __launch_bounds__(256) void losshead_fwd_kernel(const Args A, int tot
     const HeadRow r = head_row(A, row, lane);
     const float* z = A.logits + (size_t)row * A.ldz;
     const int V = A.V;
-    float lse, S, kd = 0.f, ul = 0.f;
-    if (r.q == nullptr) lse = head_lse(z, V, lane, S);
+    float lse, S, kd = 0.f, ul = 0.f, rd = 0.f, kl = 0.f;
+    if (r.q == nullptr && r.rd_row < 0) lse = head_lse(z, V, lane, S);
+    else if constexpr (HEAD_RD<Args>) {                      // head_lse's two sweeps on both rows of the pair, then the divergence sweep
+        const float* zj = A.logits + (size_t)r.rd_row * A.ldz;
+        float mx = -INFINITY, mj = -INFINITY;
+        S = 0.f;
+        for (int c = lane * 4; c < V; c += 256) {
+            const float4 v = *(const float4*)(z + c);
+            const float4 u = *(const float4*)(zj + c);
+            mx = head_max4(mx, v);
+            mj = head_max4(mj, u);
+            S += (v.x + v.y) + (v.z + v.w);
+        }
+        mx = wave_max(mx);
+        mj = wave_max(mj);
+        S = wave_sum(S);
+        float se = 0.f, sj = 0.f;
+        for (int c = lane * 4; c < V; c += 256) {
+            const float4 v = *(const float4*)(z + c);
+            const float4 u = *(const float4*)(zj + c);
+            se += (__expf(v.x - mx) + __expf(v.y - mx)) + (__expf(v.z - mx) + __expf(v.w - mx));
+            sj += (__expf(u.x - mj) + __expf(u.y - mj)) + (__expf(u.z - mj) + __expf(u.w - mj));
+        }
+        const float lg = __logf(wave_sum(se)), lgj = __logf(wave_sum(sj));   // the partner's wave computes (mj, lgj) as its own (mx, lg): same bits
+        lse = mx + lg;
+        float J = 0.f;
+        for (int c = lane * 4; c < V; c += 256) {
+            const float4 v = *(const float4*)(z + c);
+            const float4 u = *(const float4*)(zj + c);
+            const float* vv = &v.x;
+            const float* uu = &u.x;
+            float tj[4], tk[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float lp = (vv[k] - mx) - lg, lq = (uu[k] - mj) - lgj;
+                const float p = __expf(lp), q = __expf(lq), d = lp - lq;
+                tj[k] = (p - q) * d;                         // >= 0; the partner's wave forms (q - p) * (-d): the same product
+                tk[k] = p * d;
+            }
+            J += (tj[0] + tj[1]) + (tj[2] + tj[3]);
+            kl += (tk[0] + tk[1]) + (tk[2] + tk[3]);
+        }
+        rd = 0.25f * wave_sum(J);
+        kl = wave_sum(kl);
+    }
     else if constexpr (HEAD_DISTILL<Args>) {
         const float* q = r.q;
         const bool t1 = A.temperature == 1.0f;               // (uniform: a kernel argument)
@@ -275,7 +332,8 @@ __global__ __launch_bounds__(256) void losshead_fwd_kernel(const Args A, int tot
         A.lse[row] = lse;
         float loss = 0.f;
         if (!r.zero_row) {                                   // (the KL inside each branch: hoisted, the compiler contracts it otherwise)
-            if (!r.kd_seg && r.ul_t == 0) loss = head_hard_kl(r, z, V, A.pad, S, lse) * (r.weighted ? r.scale * r.w : r.scale);
+            if (!r.kd_seg && r.ul_t == 0 && r.rd_row < 0) loss = head_hard_kl(r, z, V, A.pad, S, lse) * (r.weighted ? r.scale * r.w : r.scale);
+            else if constexpr (HEAD_RD<Args>) loss = r.scale * (head_hard_kl(r, z, V, A.pad, S, lse) + A.rd_alpha * rd);
             else if constexpr (HEAD_UL<Args>) loss = r.scale * (head_hard_kl(r, z, V, A.pad, S, lse) + A.ul_alpha * ul);
             else if constexpr (HEAD_DISTILL<Args>)
                 loss = r.scale * ((1.0f - A.alpha) * head_hard_kl(r, z, V, A.pad, S, lse) + (A.alpha * A.temperature * A.temperature) * kd);
@@ -286,6 +344,10 @@ __global__ __launch_bounds__(256) void losshead_fwd_kernel(const Args A, int tot
         }
         if constexpr (HEAD_UL<Args>) {
             if (A.rowul) A.rowul[row] = ul;
+        }
+        if constexpr (HEAD_RD<Args>) {
+            if (A.rowrd) A.rowrd[row] = rd;
+            if (A.rowkl) A.rowkl[row] = kl;
         }
     }
 }
@@ -304,7 +366,32 @@ __global__ __launch_bounds__(256) void losshead_bwd_kernel(const Args A, int tot
     const float eps = r.eps, conf = r.conf;
     const float sum_td = r.zero_row ? 0.f : (r.t_is_pad ? (float)(V - 1) * eps : (float)(V - 2) * eps + conf);
     const float lse = A.lse[row];
-    if (!r.kd_seg && r.ul_t == 0) head_hard_bwd<T>(r, z, dz, V, A.ldd, A.pad, g, sum_td, lse, lane);
+    if (!r.kd_seg && r.ul_t == 0 && r.rd_row < 0) head_hard_bwd<T>(r, z, dz, V, A.ldd, A.pad, g, sum_td, lse, lane);
+    else if constexpr (HEAD_RD<Args>) {                      // (a paired row is live: never a zeroed row)
+        const float* zj = A.logits + (size_t)r.rd_row * A.ldz;
+        const float lsj = A.lse[r.rd_row], kl = A.rowkl[row], h = 0.5f * A.rd_alpha;
+        for (int c = lane * 4; c < A.ldd; c += 256) {
+            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (c < V) {
+                const float4 v = *(const float4*)(z + c);
+                const float4 u = *(const float4*)(zj + c);
+                float* ov = &o.x;
+                const float* vv = &v.x;
+                const float* uu = &u.x;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int j = c + k;
+                    float td = eps;
+                    if (j == A.pad) td = 0.f;
+                    else if (j == r.t) td = conf;
+                    const float lp = vv[k] - lse, lq = uu[k] - lsj;
+                    const float p = __expf(lp), q = __expf(lq);
+                    ov[k] = g * ((p * sum_td - td) + h * (p * ((lp - lq) - kl) + (p - q)));
+                }
+            }
+            store_lp4<T>(dz + c, o);
+        }
+    }
     else if constexpr (HEAD_UL<Args>) {                      // (a row with candidates is live: never a zeroed row)
         const unsigned* bits = head_ul_bitmap(r, V, A.pad, lane);
         const float R = head_ul_walk<true>(bits, V, z, lse, lane);
@@ -394,6 +481,7 @@ static int head_check(const char* fn, const Args* A, bool bwd, int dtype, Args* 
         HEAD_CHECK(isfinite(A->ul_alpha) && A->ul_alpha >= 0.f, "ul_alpha must be finite and >= 0");
         HEAD_CHECK(A->V <= MTN_ULOSSHEAD_MAX_V, "V above MTN_ULOSSHEAD_MAX_V");
     }
+    if constexpr (HEAD_RD<Args>) HEAD_CHECK(isfinite(A->rd_alpha) && A->rd_alpha >= 0.f, "rd_alpha must be finite and >= 0");
     *D = *A;
     *total = 0;
     for (int s = 0; s < A->n_seg; ++s) {
@@ -410,6 +498,11 @@ static int head_check(const char* fn, const Args* A, bool bwd, int dtype, Args* 
             HEAD_CHECK(A->seq_len[s] >= 0, "seq_len < 0");
             HEAD_CHECK(A->seq_len[s] == 0 || A->rows[s] % A->seq_len[s] == 0, "rows must be a multiple of seq_len");
         }
+        if constexpr (HEAD_RD<Args>) {
+            HEAD_CHECK(A->pair[s] >= 0, "pair < 0");
+            HEAD_CHECK(A->pair[s] == 0 || (A->rows[s] % 2 == 0 && A->rows[s] / 2 == A->pair[s]), "a paired segment holds 2 * pair rows");
+            HEAD_CHECK(A->pair[s] == 0 || A->rd_alpha == 0.f || A->rowkl, "a paired segment needs rowkl");
+        }
         *total += A->rows[s];
     }
 #undef HEAD_CHECK
@@ -420,6 +513,10 @@ static int head_check(const char* fn, const Args* A, bool bwd, int dtype, Args* 
     if constexpr (HEAD_UL<Args>) {
         for (int s = 0; s < MTN_LOSSHEAD_MAX_SEG; ++s)      // seq_len 0: the plain arithmetic, no bitmap
             if (s >= A->n_seg || A->ul_alpha == 0.f) D->seq_len[s] = 0;
+    }
+    if constexpr (HEAD_RD<Args>) {
+        for (int s = 0; s < MTN_LOSSHEAD_MAX_SEG; ++s)      // pair 0: the plain arithmetic, no partner read
+            if (s >= A->n_seg || A->rd_alpha == 0.f) D->pair[s] = 0;
     }
     return MTN_OK;
 }
@@ -471,3 +568,5 @@ extern "C" int mtn_wlosshead_fwd(const mtn_wlosshead_args* A, void* stream) { re
 extern "C" int mtn_wlosshead_bwd(int dtype, const mtn_wlosshead_args* A, void* stream) { return head_bwd(__func__, dtype, A, stream); }
 extern "C" int mtn_ulosshead_fwd(const mtn_ulosshead_args* A, void* stream) { return head_fwd(__func__, A, stream); }
 extern "C" int mtn_ulosshead_bwd(int dtype, const mtn_ulosshead_args* A, void* stream) { return head_bwd(__func__, dtype, A, stream); }
+extern "C" int mtn_rlosshead_fwd(const mtn_rlosshead_args* A, void* stream) { return head_fwd(__func__, A, stream); }
+extern "C" int mtn_rlosshead_bwd(int dtype, const mtn_rlosshead_args* A, void* stream) { return head_bwd(__func__, dtype, A, stream); }

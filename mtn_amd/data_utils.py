@@ -510,6 +510,17 @@ def unlikelihood_rows(logp, y, pad):
     return -(torch.where(cand, u, torch.ones_like(u)).log()).sum(2)
 
 
+def rdrop_rows(logp, y, pad):
+    """R-Drop (Liang et al. 2021) composed from PyTorch ops, the definition include/mtn_hip.h states for mtn_rlosshead_args: ``logp``
+    (2 N, V) log-probabilities whose rows i and i + N are two passes of one position, ``y`` (2 N,) targets -> (2 N,) rd =
+    (KL(p || q) + KL(q || p)) / 4 with p the row's distribution and q its partner's; 0 on rows whose own target is <pad>."""
+    N = logp.size(0) // 2
+    other = torch.cat([logp[N:], logp[:N]])
+    d = logp - other
+    rd = 0.25 * ((logp.exp() - other.exp()) * d).sum(-1)
+    return torch.where(y.reshape(-1) != pad, rd, torch.zeros_like(rd))
+
+
 class SimpleLossCompute:
     """generator -> label-smoothed KL (+ lambda * auto-encoder losses) -> backward -> optimiser step
     (data_utils.py:123-156).  ``sync=False`` returns the device tensor instead of ``loss.item()*norm`` so that the
@@ -521,9 +532,10 @@ class SimpleLossCompute:
         self.opt, self.l, self.sync, self.grad_sync, self.fused = opt, l, sync, grad_sync, fused
         self.last_kd_sum = None
         self.last_ul_sum = None
+        self.last_rd_sum = None
 
     def _fused_loss(self, x, y, norm, ae_x, ae_y, ae_norm, teacher_logp=None, alpha=0.0, temperature=1.0, row_weights=None, smoothing=None,
-                    unlikelihood=0.0):
+                    unlikelihood=0.0, rdrop=0.0):
         """Generator + log-softmax + label-smoothed KL + weighted sum as the fused HIP loss head (ops.GeneratorLossFn).
         Returns None when the fused path does not apply (CPU tensors, un-flattened model, vocab not a multiple of 8,
         foreign criterion): the caller then composes the same value from PyTorch ops."""
@@ -559,9 +571,12 @@ class SimpleLossCompute:
             spec["smoothing_seg"] = [smoothing] + [None] * (len(xs) - 1)
         if unlikelihood > 0.0:                  # the main stream only, as the teacher
             spec["unlikelihood"] = (unlikelihood, [y.size(1)] + [None] * (len(xs) - 1))
+        if rdrop > 0.0:                         # the main stream only, as the teacher: rows b T + t and (B + b) T + t are a pair
+            spec["rdrop"] = (rdrop, [y.numel() // 2] + [None] * (len(xs) - 1))
         out = ops.GeneratorLossFn.apply(spec, *xs)
         self.last_kd_sum = spec.get("kd_sum")
         self.last_ul_sum = spec.get("ul_sum")
+        self.last_rd_sum = spec.get("rd_sum")
         return out
 
     def _weighted_rows(self, logp, y, row_weights, smoothing):
@@ -579,7 +594,7 @@ class SimpleLossCompute:
         return kl.sum() if row_weights is None else (row_weights.detach().reshape(-1).to(kl.dtype) * kl).sum()
 
     def loss(self, x, y, norm, ae_x=None, ae_y=None, ae_norm=None, teacher_logp=None, alpha=0.0, temperature=1.0, row_weights=None,
-             smoothing=None, unlikelihood=0.0):
+             smoothing=None, unlikelihood=0.0, rdrop=0.0):
         """``teacher_logp``: (rows, V) fp32 teacher log-probabilities (or logits: they are normalised) for the main stream — word-level
         knowledge distillation, loss = (1 - alpha) KL_ls + alpha T^2 KL(softmax(q / T) || softmax(z / T)) over the rows whose target is
         not <pad>, both over ``norm`` (include/mtn_hip.h mtn_distill_args).  alpha == 0 is the plain loss.  ``last_kd_sum`` is left
@@ -591,7 +606,23 @@ class SimpleLossCompute:
         ``unlikelihood``: alpha >= 0 of token-level unlikelihood training on the main stream, ``y`` (B, T): loss = (KL_ls + alpha
         sum_rows ul) / norm with ul the row's sum over its sequence's earlier targets (a set, without the row's own target and <pad>) of
         -log(clamp(1 - p_c, 1e-5)) (include/mtn_hip.h mtn_ulosshead_args).  0 is the plain loss.  ``last_ul_sum`` is left holding
-        sum_rows ul (None at 0).  Not together with a teacher or row weights."""
+        sum_rows ul (None at 0).  Not together with a teacher or row weights.
+        ``rdrop``: alpha >= 0 of R-Drop on the main stream, ``y`` (2 B, T) with sequences b and B + b two passes of one dialogue: loss =
+        (KL_ls + alpha sum_rows rd) / norm, rd = (KL(p || q) + KL(q || p)) / 4 between a row and its partner, 0 on <pad>-target rows
+        (include/mtn_hip.h mtn_rlosshead_args).  0 is the plain loss.  ``last_rd_sum`` is left holding sum_rows rd (None at 0).  The
+        auto-encoder streams keep the plain loss.  Not together with a teacher, row weights or unlikelihood."""
+        rdrop = float(rdrop)
+        if not (rdrop >= 0.0 and math.isfinite(rdrop)):
+            raise ValueError("rdrop: alpha is finite and >= 0")
+        if rdrop > 0.0:
+            if teacher_logp is not None:
+                raise ValueError("rdrop and teacher soft targets do not combine")
+            if row_weights is not None or smoothing is not None:
+                raise ValueError("rdrop and row weights do not combine")
+            if float(unlikelihood) > 0.0:
+                raise ValueError("rdrop and unlikelihood do not combine")
+            if y.dim() != 2 or y.size(0) % 2 != 0:
+                raise ValueError("rdrop: y is (2 B, T)")
         unlikelihood = float(unlikelihood)
         if not (unlikelihood >= 0.0 and math.isfinite(unlikelihood)):
             raise ValueError("unlikelihood: alpha is finite and >= 0")
@@ -613,8 +644,9 @@ class SimpleLossCompute:
             raise ValueError("row_weights: one weight per target row")
         self.last_kd_sum = None
         self.last_ul_sum = None
+        self.last_rd_sum = None
         fused = self._fused_loss(x, y, norm, ae_x, ae_y, ae_norm, teacher_logp, alpha, temperature, row_weights,
-                                 None if smoothing is None else float(smoothing), unlikelihood) if self.fused else None
+                                 None if smoothing is None else float(smoothing), unlikelihood, rdrop) if self.fused else None
         if fused is not None:
             return fused
         if teacher_logp is not None and float(alpha) == 0.0:
@@ -639,6 +671,10 @@ class SimpleLossCompute:
             ul = unlikelihood_rows(out.reshape(y.size(0), y.size(1), out.size(-1)), y, self.criterion.padding_idx).sum()
             self.last_ul_sum = ul.detach()
             loss = loss + unlikelihood * ul / norm.float()
+        if rdrop > 0.0:
+            rd = rdrop_rows(out.reshape(-1, out.size(-1)), y, self.criterion.padding_idx).sum()
+            self.last_rd_sum = rd.detach()
+            loss = loss + rdrop * rd / norm.float()
         if ae_x is not None:
             xs = ae_x if isinstance(ae_x, (list, tuple)) else [ae_x]
             for i, ae_in in enumerate(xs):

@@ -110,6 +110,10 @@ class ULossHeadArgs(C.Structure):
     _fields_ = LossHeadArgs._fields_ + [("seq_len", C.c_int * 4), ("ul_alpha", C.c_float), ("rowul", C.c_void_p)]
 
 
+class RLossHeadArgs(C.Structure):
+    _fields_ = LossHeadArgs._fields_ + [("pair", C.c_int * 4), ("rd_alpha", C.c_float), ("rowrd", C.c_void_p), ("rowkl", C.c_void_p)]
+
+
 class TransposeDesc(C.Structure):
     _fields_ = [("off", C.c_long), ("rows", C.c_int), ("cols", C.c_int), ("tile_start", C.c_int), ("reserved", C.c_int), ("dst_off", C.c_long)]
 
@@ -331,6 +335,8 @@ SYMBOLS = {
     "mtn_wlosshead_bwd": (C.c_int, [C.c_int, C.POINTER(WLossHeadArgs), _P]),
     "mtn_ulosshead_fwd": (C.c_int, [C.POINTER(ULossHeadArgs), _P]),
     "mtn_ulosshead_bwd": (C.c_int, [C.c_int, C.POINTER(ULossHeadArgs), _P]),
+    "mtn_rlosshead_fwd": (C.c_int, [C.POINTER(RLossHeadArgs), _P]),
+    "mtn_rlosshead_bwd": (C.c_int, [C.c_int, C.POINTER(RLossHeadArgs), _P]),
     "mtn_eval_table_build": (C.c_int, [C.POINTER(EvalRowsArgs), _P]),
     "mtn_eval_score_rows": (C.c_int, [C.POINTER(EvalRowsArgs), _P]),
     "mtn_scst_assemble": (C.c_int, [C.POINTER(ScstAssembleArgs), _P]),

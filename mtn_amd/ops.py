@@ -1716,6 +1716,27 @@ def _unlikelihood(spec, rows):
     return alpha, lens
 
 
+def _rdrop(spec, rows):
+    """spec["rdrop"] = (alpha, pair distances per stream: an int N or None) checked against the streams: None when it is absent, alpha is 0
+    or no stream is paired (the plain loss head runs), else (alpha, [N per stream, 0 = unpaired])."""
+    rd = spec.get("rdrop")
+    if rd is None:
+        return None
+    alpha, pairs = rd
+    alpha = float(alpha)
+    if not (alpha >= 0.0 and math.isfinite(alpha)):
+        raise ValueError("GeneratorLossFn: the R-Drop alpha is finite and >= 0")
+    if len(pairs) != len(rows):
+        raise ValueError("GeneratorLossFn: spec['rdrop'] holds one pair distance (an int or None) per stream")
+    pairs = [0 if N is None else int(N) for N in pairs]
+    for N, r in zip(pairs, rows):
+        if N < 0 or (N > 0 and r != 2 * N):
+            raise ValueError("GeneratorLossFn: a paired stream holds 2 N rows, N its pair distance")
+    if alpha == 0.0 or not any(pairs):
+        return None
+    return alpha, pairs
+
+
 class GeneratorLossFn(torch.autograd.Function):
     """sum_i coef_i * KLDiv(log_softmax(x_i W_i^T + b_i), smooth(y_i)) / norm_i  — Generator (mtn.py:62-69) +
     LabelSmoothing (label_smoothing.py) + SimpleLossCompute's weighted sum (data_utils.py:133-144) as: one grouped cast,
@@ -1731,7 +1752,11 @@ class GeneratorLossFn(torch.autograd.Function):
     kernels are mtn_wlosshead_fwd / _bwd (csrc/losshead.hip); not together with a teacher.
     Unlikelihood training (Welleck et al. 2019): ``spec["unlikelihood"]`` = (alpha, per stream the sequence length T of its (B, T) targets
     or None).  With it present and alpha > 0 the row kernels are mtn_ulosshead_fwd / _bwd (csrc/losshead.hip; include/mtn_hip.h), casts and
-    GEMMs unchanged, and ``spec["ul_sum"]`` is left holding the device scalar sum_rows ul; not together with a teacher or row weights."""
+    GEMMs unchanged, and ``spec["ul_sum"]`` is left holding the device scalar sum_rows ul; not together with a teacher or row weights.
+    R-Drop (Liang et al. 2021): ``spec["rdrop"]`` = (alpha, per stream the pair distance N of its 2 N rows — rows i and i + N are two passes
+    of one position — or None).  With it present and alpha > 0 the row kernels are mtn_rlosshead_fwd / _bwd (csrc/losshead.hip;
+    include/mtn_hip.h), casts and GEMMs unchanged, and ``spec["rd_sum"]`` is left holding the device scalar sum_rows rd; not together with a
+    teacher, row weights or unlikelihood."""
 
     @staticmethod
     def forward(ctx, spec, *xs):
@@ -1789,7 +1814,13 @@ class GeneratorLossFn(torch.autograd.Function):
         if unlikely is not None and (teachers is not None or weighted is not None):
             raise ValueError("GeneratorLossFn: unlikelihood does not combine with %s" % ("teacher soft targets" if teachers is not None
                                                                                          else "row weights"))
-        if unlikely is not None:
+        rdrop = _rdrop(spec, rows)
+        if rdrop is not None and (teachers is not None or weighted is not None or unlikely is not None):
+            raise ValueError("GeneratorLossFn: R-Drop does not combine with %s" % ("teacher soft targets" if teachers is not None
+                                                                                   else "row weights" if weighted is not None else "unlikelihood"))
+        if rdrop is not None:
+            args_cls, fwd, bwd = L.RLossHeadArgs, lib.mtn_rlosshead_fwd, lib.mtn_rlosshead_bwd
+        elif unlikely is not None:
             args_cls, fwd, bwd = L.ULossHeadArgs, lib.mtn_ulosshead_fwd, lib.mtn_ulosshead_bwd
         elif weighted is not None:
             args_cls, fwd, bwd = L.WLossHeadArgs, lib.mtn_wlosshead_fwd, lib.mtn_wlosshead_bwd
@@ -1821,12 +1852,21 @@ class GeneratorLossFn(torch.autograd.Function):
             for i, T in enumerate(unlikely[1]):
                 A.seq_len[i] = T
             A.ul_alpha, A.rowul = unlikely[0], rowul.data_ptr()
+        elif rdrop is not None:
+            rowrd = torch.empty(R, device=dev, dtype=torch.float32)
+            rowkl = torch.empty(R, device=dev, dtype=torch.float32)
+            for i, N in enumerate(rdrop[1]):
+                A.pair[i] = N
+            A.rd_alpha, A.rowrd, A.rowkl = rdrop[0], rowrd.data_ptr(), rowkl.data_ptr()
         L.check(fwd(C.byref(A), L.stream_ptr()))
         if teachers is not None:
             spec["kd_sum"] = rowkd.sum()
         if unlikely is not None:
             spec["ul_sum"] = rowul.sum()
-        ctx.args, ctx.bwd, ctx.keep = A, bwd, (x_lp, logits, lse, norms, targets, teachers if weighted is None else weighted)
+        if rdrop is not None:
+            spec["rd_sum"] = rowrd.sum()
+        ctx.args, ctx.bwd = A, bwd
+        ctx.keep = (x_lp, logits, lse, norms, targets, teachers if weighted is None else weighted, rowkl if rdrop is not None else None)
         ctx.meta = (spec, segs, rows, offs, d, V, R, code, [x.shape for x in xs])
         return rowloss.sum()
 

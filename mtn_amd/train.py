@@ -136,9 +136,16 @@ def parse(argv=None):
                    help="argmax: the most likely token; sample: a draw from softmax(logits / --sched-sample-temperature)")
     p.add_argument("--sched-sample-temperature", default=1.0, type=float)
     p.add_argument("--sched-sample-seed", default=0, type=int, help="seed of the coins and draws (the update count is added on the device)")
+    # R-Drop: every dialogue runs through the model twice under independent dropout masks, in one doubled batch
+    p.add_argument("--rdrop-alpha", default=0.0, type=float, metavar="A",
+                   help="> 0: every batch is trained on twice in one step, rows b and B + b the same dialogue under two dropout masks, and "
+                        "the response stream's loss gains A / 4 * (KL(p || q) + KL(q || p)) between the two passes' next-token distributions "
+                        "per target token (R-Drop: Liang et al. 2021); --batch-size B keeps meaning B dialogues: the step runs 2 B rows and "
+                        "needs that much activation memory; validation stays the plain loss on the undoubled batch; every epoch logs the "
+                        "mean divergence (0: off)")
     args = p.parse_args(argv)
     err = (distill_flag_error(args) or ema_flag_error(args) or scst_flag_error(args) or unlikelihood_flag_error(args) or clip_flag_error(args)
-           or accum_flag_error(args) or sched_flag_error(args))
+           or accum_flag_error(args) or sched_flag_error(args) or rdrop_flag_error(args))
     if err:
         p.error(err)
     return args
@@ -218,6 +225,26 @@ def unlikelihood_flag_error(args):
         return "--unlikelihood-alpha does not combine with --distill-model: unlikelihood under distillation is out of scope"
     if a > 0.0 and args.scst_samples:
         return "--unlikelihood-alpha does not combine with --scst-samples: unlikelihood under self-critical training is out of scope"
+    return None
+
+
+def rdrop_flag_error(args):
+    """What is wrong with --rdrop-alpha, or what it conflicts with, as one line (None: nothing).  0 = off."""
+    import math
+    a = args.rdrop_alpha
+    if not (a >= 0.0 and math.isfinite(a)):        # (nan fails the comparison)
+        return "--rdrop-alpha must be finite and >= 0 (got %r)" % a
+    if a == 0.0:
+        return None
+    if args.distill_model:
+        return "--rdrop-alpha does not combine with --distill-model: R-Drop under distillation would be a combined loss head, out of scope"
+    if args.scst_samples:
+        return "--rdrop-alpha does not combine with --scst-samples: R-Drop under self-critical training is out of scope"
+    if args.unlikelihood_alpha > 0.0:
+        return "--rdrop-alpha does not combine with --unlikelihood-alpha: R-Drop with unlikelihood would be a combined loss head, out of scope"
+    if args.sched_sample_prob > 0.0:
+        return ("--rdrop-alpha does not combine with --sched-sample-prob: the mix keys rows by batch index, so the two passes of a dialogue "
+                "would see different inputs")
     return None
 
 
@@ -421,7 +448,8 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
     shape, batches assembled in place on the device; the host only syncs at the report interval.  ``cut``: the --cut-a
     RandomState (None = no truncation).  Returns (mean loss per token, target tokens of the epoch over all ranks).  ``stats``: a dict
     that receives "kd", the epoch's mean distillation KL per token, when the trainer has a teacher, "ul", the epoch's mean unlikelihood per
-    token, when it trains with unlikelihood, and "reward" / "baseline", the
+    token, when it trains with unlikelihood, "rd", the epoch's mean R-Drop divergence per token, when it trains with R-Drop (the token
+    counts are then the doubled batches': both passes), and "reward" / "baseline", the
     mean over the epoch's steps of the steps' mean reward and mean baseline, when it trains self-critically."""
     order = list(range(len(indices)))
     rng.shuffle(order)
@@ -431,6 +459,7 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
     rl_sum = torch.zeros(2, device=dev, dtype=torch.float64)
     kd_sum = torch.zeros((), device=dev) if trainer.teacher is not None else None
     ul_sum = torch.zeros((), device=dev) if getattr(trainer, "unlikelihood", 0.0) > 0.0 else None
+    rd_sum = torch.zeros((), device=dev) if getattr(trainer, "rdrop", 0.0) > 0.0 else None
     tok_sum = torch.zeros((), device=dev, dtype=torch.int64)
     t0, tok0 = time.time(), 0
     accum = getattr(trainer, "accum_steps", 1) > 1
@@ -448,6 +477,8 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
             kd_sum += trainer.last_kd * n_glob
         if ul_sum is not None:
             ul_sum += trainer.last_ul * n_glob
+        if rd_sum is not None:
+            rd_sum += trainer.last_rd * n_glob
         if scst:
             rl_sum += torch.stack([trainer.last_reward, trainer.last_baseline])
         if (j + 1) % report_interval == 0 and rank == 0:
@@ -461,7 +492,11 @@ def run_epoch_graphed(trainer, indices, epoch, report_interval, rank, rng, cut=N
             torch.distributed.all_reduce(kd_sum)
         if ul_sum is not None:
             torch.distributed.all_reduce(ul_sum)
+        if rd_sum is not None:
+            torch.distributed.all_reduce(rd_sum)
     ntok = int(tok_sum)
+    if rd_sum is not None and stats is not None:
+        stats["rd"] = float(rd_sum) / max(1, ntok)
     if ul_sum is not None and stats is not None:
         stats["ul"] = float(ul_sum) / max(1, ntok)
     if kd_sum is not None and stats is not None:
@@ -637,7 +672,8 @@ def main(argv=None):
                          scst.samples, scst.reward, scst.baseline, corpus.n_dialogs)
         accum = args.accum_steps > 1                          # (--eager then runs the trainer's steps eagerly, as under scst)
         sched = sched_config(args)                            # (likewise: the first pass and the mix belong to the trainer's step)
-        if args.eager and scst is None and not accum and sched is None:
+        rdrop = args.rdrop_alpha > 0.0                        # (likewise: the doubled batch belongs to the trainer's step)
+        if args.eager and scst is None and not accum and sched is None and not rdrop:
             opt = NoamOpt(args.d_model, 1, args.warmup_steps, FusedAdam(model))
             if args.ema_decay:
                 opt.optimizer.enable_ema(args.ema_decay)
@@ -649,9 +685,9 @@ def main(argv=None):
             from .train_step import BucketedTrainer
             trainer = BucketedTrainer(model, corpus, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l,
                                       bucket=args.bucket, grad_sync=sync, ema_decay=args.ema_decay, scst=scst,
-                                      use_graph=not (args.eager and (scst is not None or accum or sched is not None)),
+                                      use_graph=not (args.eager and (scst is not None or accum or sched is not None or rdrop)),
                                       unlikelihood=args.unlikelihood_alpha, clip_grad_norm=args.clip_grad_norm, accum_steps=args.accum_steps,
-                                      sched=sched, **distill)
+                                      sched=sched, rdrop=args.rdrop_alpha, **distill)
         valid = None
         if args.valid_videos > 0 or valid_data is not None:
             vdata = valid_data if valid_data is not None else synthetic_corpus(args.valid_videos, args.vocab_size, args.ft_sizes, args.rand_seed + 1000)
@@ -659,7 +695,7 @@ def main(argv=None):
             valid = (DeviceCorpus(vdata, dev), vidx)
             logging.info("#validation sample = %d  #validation batch = %d", vn, len(vidx))
         min_valid = min_valid_ema = 1.0e10
-        graphed = not args.eager or scst is not None or accum or sched is not None  # (then --eager: the trainer's steps, run eagerly)
+        graphed = not args.eager or scst is not None or accum or sched is not None or rdrop  # (then --eager: the trainer's steps, run eagerly)
         the_opt = trainer.opt if graphed else opt
         if args.resume:
             model.load_state_dict(torch.load(args.resume + ".pth.tar", map_location=dev), strict=False)
@@ -688,6 +724,8 @@ def main(argv=None):
                     print("epoch %d mean distillation KL per token: %f" % (epoch + 1, stats["kd"]))
                 if "ul" in stats:
                     print("epoch %d mean unlikelihood per token: %f" % (epoch + 1, stats["ul"]))
+                if "rd" in stats:
+                    print("epoch %d mean R-Drop divergence per token: %f" % (epoch + 1, stats["rd"]))
                 if "reward" in stats:
                     print("epoch %d mean reward: %f mean baseline: %f" % (epoch + 1, stats["reward"], stats["baseline"]))
             if args.clip_grad_norm:
@@ -743,19 +781,22 @@ def main(argv=None):
     batch = synthetic_batch(args.vocab_size, args.batch_size, Q, H, C, T, [V] * len(args.ft_sizes), args.ft_sizes, device=dev, seed=1 + rank)
     step = TrainStep(model, batch, args.vocab_size, pad=1, warmup=args.warmup_steps, lam=args.loss_l, grad_sync=sync, ema_decay=args.ema_decay,
                      unlikelihood=args.unlikelihood_alpha, clip_grad_norm=args.clip_grad_norm, accumulate=args.accum_steps > 1,
-                     sched=sched_config(args), **distill)
-    ntok = int(batch.ntokens) * world
+                     sched=sched_config(args), rdrop=args.rdrop_alpha, **distill)
+    ntok = int(step.batch.ntokens) * world             # (R-Drop: the step's own doubled batch, both passes' tokens)
     K = args.accum_steps
     for epoch in range(args.num_epochs):
         t0, tokens = time.time(), 0
         kd_sum = torch.zeros((), device=dev) if teacher is not None else None
         ul_sum = torch.zeros((), device=dev) if args.unlikelihood_alpha > 0.0 else None
+        rd_sum = torch.zeros((), device=dev) if args.rdrop_alpha > 0.0 else None
         for j in range(args.steps_per_epoch):
             # --accum-steps K: a call is one micro-step on the batch; every K-th one, and the epoch's last, closes the window and updates
             loss = step() if K == 1 else step((j + 1) % K == 0 or j == args.steps_per_epoch - 1)
             tokens += ntok
             if ul_sum is not None:
                 ul_sum += step.last_ul
+            if rd_sum is not None:
+                rd_sum += step.last_rd
             if kd_sum is not None:
                 kd_sum += step.last_kd
             if (j + 1) % args.report_interval == 0 and rank == 0:
@@ -773,6 +814,11 @@ def main(argv=None):
                 torch.distributed.all_reduce(ul_sum)
             if rank == 0:
                 print("epoch %d mean unlikelihood per token: %f" % (epoch + 1, float(ul_sum) / max(1, args.steps_per_epoch)))
+        if rd_sum is not None:
+            if world > 1:
+                torch.distributed.all_reduce(rd_sum)
+            if rank == 0:
+                print("epoch %d mean R-Drop divergence per token: %f" % (epoch + 1, float(rd_sum) / max(1, args.steps_per_epoch)))
         if K > 1 and rank == 0:
             print("epoch %d optimiser updates: %d over %d batches" % (epoch + 1, -(-args.steps_per_epoch // K), args.steps_per_epoch))
         if args.clip_grad_norm:

@@ -128,7 +128,8 @@ class TrainStep:
                  smoothing: float = 0.1, grad_sync=None, use_graph: bool = True, overlap: Optional[bool] = None, opt=None,
                  dynamic_norms: bool = False, fuse_optimizer: Optional[bool] = None, teacher=None, distill_alpha: float = 0.5,
                  distill_temperature: float = 1.0, ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, unlikelihood: float = 0.0,
-                 clip_grad_norm: float = 0.0, accumulate: bool = False, sched: Optional[SchedConfig] = None):
+                 clip_grad_norm: float = 0.0, accumulate: bool = False, sched: Optional[SchedConfig] = None, rdrop: float = 0.0,
+                 rdrop_paired: bool = False):
         """``opt``: share an existing NoamOpt (several TrainSteps over one model, e.g. one per batch shape).
         ``dynamic_norms``: the batch tensors are refilled in place between steps, so the loss normalisers (token counts,
         train.py:35-39) are recomputed from them inside the step instead of once at construction.
@@ -197,8 +198,35 @@ class TrainStep:
         update count on the device, so every replay draws anew, a resumed run continues the stream, and the micro-steps of an
         accumulation window share it (on a fixed batch they repeat their draws).  ``sched_stats`` (3,) int64 on the device counts
         [eligible, replaced, replaced with another token than gold] until the caller zeroes it.  None = off: nothing is allocated or
-        launched.  Not together with a teacher (it would have to see the mixed inputs) or scst."""
+        launched.  Not together with a teacher (it would have to see the mixed inputs) or scst.
+        ``rdrop``: alpha of R-Drop (Liang et al. 2021) on the MAIN decoder stream.  ``batch`` is then the SOURCE of B dialogues and the
+        step trains on a static batch of its own (``self.batch``) of 2 B rows, rows b and B + b the same dialogue: a dropout site's
+        keep-mask is a counter hash of (seed, salt, flat element index), so the two copies draw different masks in ONE forward pass.
+        The refill is device copies at the head of the step (one copy per tensor that writes both halves, the masks' kernel images included), captured
+        with it, with no host read: a caller that refills the source in place (``dynamic_norms``) keeps working.  The loss head is
+        mtn_rlosshead_fwd / _bwd (csrc/losshead.hip; include/mtn_hip.h gives the formulas) in the place of the two loss-head launches:
+        loss = the plain loss of the doubled batch (the mean of the two passes' label-smoothed losses: the normaliser counts both
+        passes' tokens) + rdrop * ``last_rd``, ``last_rd`` = the device scalar sum_rows rd / ``_norms[0]`` = (KL(p || q) + KL(q || p)) / 4
+        per original target token; the auto-encoder streams keep the plain loss.  The head is local to the rank, so data
+        parallelism needs nothing new.  ``rdrop_paired``: ``batch`` already holds 2 N rows in pair layout and is used as it is (checked
+        once: trg_y[:N] == trg_y[N:]).  0 = off: nothing is allocated or launched, the step is the plain step launch for launch and bit
+        for bit.  Combines with clip_grad_norm, ema_decay, accumulate, both optimiser paths, graph and eager and both data-parallel
+        schedules.  Not together with a teacher, scst, unlikelihood or sched (the mix keys rows by batch index: the halves would
+        see different inputs)."""
         self.model, self.batch = model, batch
+        self.rdrop, self.last_rd, self._rd_src = float(rdrop), None, None
+        if not (self.rdrop >= 0.0 and math.isfinite(self.rdrop)):
+            raise ValueError("TrainStep: rdrop is finite and >= 0")
+        if self.rdrop > 0.0:
+            for on, what in ((teacher is not None, "a teacher (distillation)"), (scst is not None, "scst"),
+                             (float(unlikelihood) > 0.0, "unlikelihood"), (sched is not None, "sched (scheduled sampling)")):
+                if on:
+                    raise ValueError("TrainStep: rdrop does not combine with %s" % what)
+            if rdrop_paired:
+                self._check_paired(batch)
+            else:
+                self._init_rdrop(batch, pad)
+                batch = self.batch
         self.sched = sched
         if sched is not None and (teacher is not None or scst is not None):
             raise ValueError("TrainStep: sched (scheduled sampling) does not combine with %s" % ("a teacher (distillation)" if teacher is not None
@@ -290,6 +318,10 @@ class TrainStep:
     # ---- pieces
     def local_norms(self):
         b = self.batch
+        if self._rd_src is not None:         # the doubled batch's counts, from the source: right before the step's refill too
+            src = self._rd_src
+            ae_y = src.cap if self.model.auto_encoder_ft in ("caption", "summary") else src.query
+            return 2.0 * torch.stack([(src.trg_y != self.pad).sum(), (ae_y != self.pad).sum()]).float()
         if self.scst is not None:            # the sampled rows alone: gold rows ride on the same normaliser
             return torch.stack([(b.trg_y[:self._n_sampled] != self.pad).sum(), (self._ae_y != self.pad).sum()]).float()
         return torch.stack([(b.trg_y != self.pad).sum(), (self._ae_y != self.pad).sum()]).float()
@@ -383,6 +415,60 @@ class TrainStep:
         finally:
             if training:
                 m.train()
+
+    # ---- R-Drop
+    @staticmethod
+    def _check_paired(batch):
+        """A pre-paired batch: 2 N rows, row N + b the second pass of row b.  One host read, at construction."""
+        y = batch.trg_y
+        if y.size(0) < 2 or y.size(0) % 2 != 0:
+            raise ValueError("TrainStep: rdrop_paired needs a batch of 2 N rows (got %d)" % y.size(0))
+        N = y.size(0) // 2
+        differ = (y[:N] != y[N:]).any(1).nonzero()
+        if differ.numel() > 0:
+            raise ValueError("TrainStep: rdrop_paired: the targets of row %d and of its partner, row %d, differ" % (int(differ[0]), int(differ[0]) + N))
+
+    def _init_rdrop(self, src, pad):
+        """The static batch of 2 B rows the step trains on, rows b and B + b both dialogue b of the source."""
+        from .data_utils import Batch
+        if getattr(src, "trg", None) is None:
+            raise ValueError("TrainStep: rdrop needs the source batch's answers")
+        two = lambda t: torch.cat([t, t]).contiguous()
+        b = Batch(two(src.query), two(src.his), None, None, None if src.cap is None else two(src.cap), two(src.trg), two(src.trg_y), pad=pad,
+                  device=src.query.device)
+        if src.fts is not None:                                    # (already cleaned by the source's constructor: not through it again)
+            b.fts, b.fts_mask = [two(f) for f in src.fts], [two(m) for m in src.fts_mask]
+        self._rd_src, self.batch = src, b
+
+    def _rdrop_refill(self):
+        """The source batch into both halves of the static batch, in place: one copy per tensor that writes both halves, and the masks' kernel images
+        (ops.prepare_masks).  Part of the (captured) step; nothing is read on the host."""
+        src, b = self._rd_src, self.batch
+        if src is None:
+            return
+        B = src.query.size(0)
+
+        def both(dst, rows):                     # one broadcast copy into the two halves (two slice copies if dst cannot be viewed so)
+            if dst.is_contiguous():
+                dst.view((2,) + tuple(rows.shape)).copy_(rows.unsqueeze(0).expand((2,) + tuple(rows.shape)))
+            else:
+                dst[:B].copy_(rows)
+                dst[B:].copy_(rows)
+
+        def put(dst, rows):
+            both(dst, rows)
+            u8 = getattr(dst, "_mtn_u8", None)
+            if u8 is not None and u8.data_ptr() != dst.data_ptr():
+                both(u8, rows)
+
+        for name in ("query", "his", "trg", "trg_y") + (("cap",) if src.cap is not None else ()):
+            put(getattr(b, name), getattr(src, name))
+        for name in ("query_mask", "his_mask", "trg_mask") + (("cap_mask",) if src.cap is not None else ()):
+            put(getattr(b, name), getattr(src, name))
+        if src.fts is not None:
+            for f, m, sf, sm in zip(b.fts, b.fts_mask, src.fts, src.fts_mask):
+                put(f, sf)
+                put(m, sm)
 
     # ---- self-critical sequence training
     def _init_scst(self, src, pad):
@@ -550,6 +636,10 @@ class TrainStep:
         if self.scst is not None:
             return self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], row_weights=self._roww,
                                 smoothing=0.0)
+        if self.rdrop > 0.0:
+            loss = self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], rdrop=self.rdrop)
+            self.last_rd = self.lc.last_rd_sum / self._norms[0]
+            return loss
         if self.unlikelihood > 0.0:
             loss = self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], unlikelihood=self.unlikelihood)
             self.last_ul = self.lc.last_ul_sum / self._norms[0]
@@ -564,6 +654,7 @@ class TrainStep:
 
     def _fwd_bwd(self, fuse: bool = False):
         m, b = self.model, self.batch
+        self._rdrop_refill()
         self._refresh_norms()
         teacher_rows = self._teacher_pass()
         m.zero_glue_grads()
@@ -640,6 +731,7 @@ class TrainStep:
 
         def top():
             b = self.batch
+            self._rdrop_refill()
             self._refresh_norms()
             teacher_rows = self._teacher_pass()
             m.zero_glue_grads()
@@ -889,7 +981,7 @@ class BucketedTrainer:
     def __init__(self, model, corpus, vocab_size: int, pad: int = 1, warmup: int = 4000, lam: float = 1.0, bucket: int = 8,
                  grad_sync=None, max_shapes: int = 64, teacher=None, distill_alpha: float = 0.5, distill_temperature: float = 1.0,
                  ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, use_graph: bool = True, unlikelihood: float = 0.0,
-                 clip_grad_norm: float = 0.0, accum_steps: int = 1, sched: Optional[SchedConfig] = None):
+                 clip_grad_norm: float = 0.0, accum_steps: int = 1, sched: Optional[SchedConfig] = None, rdrop: float = 0.0):
         """``scst``: self-critical sequence training — every padded shape keeps, next to its static source Batch, a TrainStep(scst=...)
         whose own static batch holds the drawn rows; a step refills the source in place and calls rl_step with the batch's QA ids as
         corpus items and sampling keys and the seed ``scst.seed + rl_steps`` (``rl_steps``: steps taken; set it after a resume).  With
@@ -903,7 +995,18 @@ class BucketedTrainer:
         1 = off: today's step, launch for launch.  Not together with scst.
         ``sched``: scheduled sampling (TrainStep's ``sched``) for every shape: the rows' hash keys are the batch's QA ids, refilled
         before every step, and ``sched_stats`` is the one (3,) int64 device counter block all shapes add to (zero it to start a count).
-        ``use_graph`` = False runs these steps eagerly.  Not together with a teacher or scst."""
+        ``use_graph`` = False runs these steps eagerly.  Not together with a teacher or scst.
+        ``rdrop``: TrainStep's R-Drop alpha for every shape: each padded shape's static Batch is the source its step doubles inside the
+        (captured) step; ``last_rd``: the last step's device scalar (None at 0).  Not together with a teacher, scst, unlikelihood or
+        sched."""
+        self.rdrop, self.last_rd = float(rdrop), None
+        if not (self.rdrop >= 0.0 and math.isfinite(self.rdrop)):
+            raise ValueError("BucketedTrainer: rdrop is finite and >= 0")
+        if self.rdrop > 0.0:
+            for on, what in ((teacher is not None, "a teacher (distillation)"), (scst is not None, "scst"),
+                             (float(unlikelihood) > 0.0, "unlikelihood"), (sched is not None, "sched (scheduled sampling)")):
+                if on:
+                    raise ValueError("BucketedTrainer: rdrop does not combine with %s" % what)
         if sched is not None and (teacher is not None or scst is not None):
             raise ValueError("BucketedTrainer: sched (scheduled sampling) does not combine with %s" % ("a teacher (distillation)" if teacher is not None
                                                                                                         else "scst"))
@@ -972,7 +1075,7 @@ class BucketedTrainer:
             ts = TrainStep(self.model, batch, self.vocab, pad=self.pad, lam=self.lam, grad_sync=self.grad_sync, opt=self.opt,
                            dynamic_norms=True, teacher=self.teacher, distill_alpha=self.distill_alpha,
                            distill_temperature=self.distill_temperature, scst=cfg, use_graph=self.use_graph,
-                           unlikelihood=self.unlikelihood, sched=self.sched)
+                           unlikelihood=self.unlikelihood, sched=self.sched, rdrop=self.rdrop)
             if self.sched is not None:                           # one counter block for every shape (read at launch: set before the capture)
                 if self.sched_stats is None:
                     self.sched_stats = ts.sched_stats
@@ -1001,6 +1104,7 @@ class BucketedTrainer:
             loss = hit[1]()
         self.last_kd = hit[1].last_kd               # (device scalar; None without a teacher)
         self.last_ul = hit[1].last_ul               # (device scalar; None without unlikelihood)
+        self.last_rd = hit[1].last_rd               # (device scalar; None without R-Drop)
         hit[0]._norms_global = hit[1]._norms        # [target tokens, auto-encoder tokens] the step's loss is divided by (all ranks)
         return loss, hit[0]
 
