@@ -160,6 +160,7 @@ extern "C" int mtn_layernorm_fwd_group(int dtype, int count, const mtn_ln_fwd_de
         MTN_CHECK_ARG(D.rows > 0 && D.d >= 4 && D.d % 4 == 0, "rows>0 and d%4==0 required");
         MTN_CHECK_ARG((D.x || (D.tokens && D.lut)) && (D.no_ln || (D.a2 && D.b2)), "null input");
         MTN_CHECK_ARG(!D.pe || D.seq_len > 0, "positional encoding needs seq_len");
+        MTN_CHECK_ARG(D.pe || !(D.drop.p > 0.f), "dropout on the source row needs pe (ln_src applies it only there)");
         grp.block_start[i] = blocks;
         blocks += (D.rows + 3) / 4;
         grp.d[i] = D;
