@@ -13,7 +13,7 @@ import logging
 import math
 import os
 
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -521,6 +521,46 @@ def rdrop_rows(logp, y, pad):
     return torch.where(y.reshape(-1) != pad, rd, torch.zeros_like(rd))
 
 
+class Objective(NamedTuple):
+    """The main decoder stream's objective: ``kind`` (a key of ops.LOSS_HEADS) and that kind's parameters.  ``alpha``: the weight of
+    the kind's extra term (distill, unlikelihood, rdrop)."""
+    kind: str = "plain"
+    alpha: float = 0.0
+    temperature: float = 1.0                      # distill
+    teacher: Optional[torch.Tensor] = None        # distill: (rows, V) log-probabilities or logits
+    row_weights: Optional[torch.Tensor] = None    # weighted: one weight per row, or None (all ones)
+    smoothing: Optional[float] = None             # weighted: in the place of the criterion's, or None
+
+
+def objective(y, teacher_logp=None, alpha=0.0, temperature=1.0, row_weights=None, smoothing=None, unlikelihood=0.0, rdrop=0.0) -> Objective:
+    """The Objective that SimpleLossCompute.loss's keywords describe for targets ``y``: every value check, and the one "at most one
+    kind" check (ops.one_loss_head).  unlikelihood == 0 and rdrop == 0 are the plain head; ``smoothing`` alone selects the weighted one;
+    a teacher at alpha == 0 stays "distill", whose kernels and composed form then never read it."""
+    from . import ops
+    unlikelihood, rdrop = float(unlikelihood), float(rdrop)
+    for name, a in (("rdrop", rdrop), ("unlikelihood", unlikelihood)):
+        if not (a >= 0.0 and math.isfinite(a)):
+            raise ValueError("%s: alpha is finite and >= 0" % name)
+    asked = {"distill": teacher_logp is not None, "weighted": row_weights is not None or smoothing is not None,
+             "unlikelihood": unlikelihood > 0.0, "rdrop": rdrop > 0.0}
+    kind = ops.one_loss_head([k for k in ops.LOSS_HEADS if asked.get(k)])
+    if kind == "rdrop" and (y.dim() != 2 or y.size(0) % 2 != 0):
+        raise ValueError("rdrop: y is (2 B, T)")
+    if kind == "unlikelihood" and y.dim() != 2:
+        raise ValueError("unlikelihood: y is (B, T)")
+    if kind == "distill" and not (0.0 <= float(alpha) <= 1.0 and 0.0 < float(temperature) < float("inf")):
+        raise ValueError("distillation: alpha in [0, 1] and a finite temperature > 0")
+    if smoothing is not None and not (0.0 <= float(smoothing) <= 1.0):
+        raise ValueError("smoothing in [0, 1]")
+    if row_weights is not None and row_weights.numel() != y.numel():
+        raise ValueError("row_weights: one weight per target row")
+    if kind == "distill":
+        return Objective(kind, float(alpha), float(temperature), teacher=teacher_logp)
+    if kind == "weighted":
+        return Objective(kind, row_weights=row_weights, smoothing=None if smoothing is None else float(smoothing))
+    return Objective(kind, {"unlikelihood": unlikelihood, "rdrop": rdrop}.get(kind, 0.0))
+
+
 class SimpleLossCompute:
     """generator -> label-smoothed KL (+ lambda * auto-encoder losses) -> backward -> optimiser step
     (data_utils.py:123-156).  ``sync=False`` returns the device tensor instead of ``loss.item()*norm`` so that the
@@ -530,15 +570,21 @@ class SimpleLossCompute:
     def __init__(self, generator, ae_generator, criterion, opt=None, l=1.0, sync=True, grad_sync=None, fused=True):
         self.generator, self.ae_generator, self.criterion = generator, ae_generator, criterion
         self.opt, self.l, self.sync, self.grad_sync, self.fused = opt, l, sync, grad_sync, fused
-        self.last_kd_sum = None
-        self.last_ul_sum = None
-        self.last_rd_sum = None
+        self._extra = (None, None)         # (spec key, value) of the last loss' extra row sum: what last_kd_sum / _ul_sum / _rd_sum read
+
+    last_kd_sum, last_ul_sum, last_rd_sum = (property(lambda self, key=key: self._extra[1] if self._extra[0] == key else None)
+                                             for key in ("kd_sum", "ul_sum", "rd_sum"))
 
     def _fused_loss(self, x, y, norm, ae_x, ae_y, ae_norm, teacher_logp=None, alpha=0.0, temperature=1.0, row_weights=None, smoothing=None,
                     unlikelihood=0.0, rdrop=0.0):
-        """Generator + log-softmax + label-smoothed KL + weighted sum as the fused HIP loss head (ops.GeneratorLossFn).
-        Returns None when the fused path does not apply (CPU tensors, un-flattened model, vocab not a multiple of 8,
-        foreign criterion): the caller then composes the same value from PyTorch ops."""
+        """_fused_head from ``loss``'s keywords."""
+        return self._fused_head(objective(y, teacher_logp, alpha, temperature, row_weights, smoothing, unlikelihood, rdrop), x, y, norm,
+                                ae_x, ae_y, ae_norm)[0]
+
+    def _fused_head(self, obj: Objective, x, y, norm, ae_x, ae_y, ae_norm):
+        """Generator + log-softmax + label-smoothed KL + weighted sum as the fused HIP loss head (ops.GeneratorLossFn): (loss, the
+        objective's extra row sum or None).  (None, None) when the fused path does not apply (CPU tensors, un-flattened model, vocab
+        not a multiple of 8, foreign criterion): the caller then composes the same value from PyTorch ops."""
         from . import ops
         gens = [self.generator]
         xs, ys, norms, coefs = [x], [y], [norm], [1.0]
@@ -551,33 +597,27 @@ class SimpleLossCompute:
                     gens.append(self.generator)
                 xs.append(a); ys.append(ae_y); norms.append(ae_norm); coefs.append(self.l)
         if not (isinstance(self.criterion, LabelSmoothing) and x.is_cuda and len(xs) <= 4):
-            return None
+            return None, None
         fused = [getattr(g, "_fused", None) for g in gens]
         if any(f is None for f in fused) or self.criterion.size % 8 != 0:
-            return None
-        if not torch.is_grad_enabled():
-            pass
+            return None, None
         spec = dict(targets=ys, norms=[n if torch.is_tensor(n) else torch.tensor(float(n), device=x.device) for n in norms], coefs=coefs,
                     gens=[(f["w_lp"], f["bias"], f["grad_w"], f["grad_b"], f.get("w_lpT")) for f in fused], vocab=self.criterion.size,
                     pad=self.criterion.padding_idx, smoothing=self.criterion.smoothing, lp_dtype=fused[0]["lp_dtype"],
                     queue=fused[0].get("queue"))
         spec["norms"] = [n.detach().float().reshape(1) for n in spec["norms"]]
-        if teacher_logp is not None:            # the main stream only: the auto-encoder streams keep the plain loss
-            spec["teacher"] = [teacher_logp.reshape(-1, teacher_logp.size(-1))] + [None] * (len(xs) - 1)
-            spec["alpha"], spec["temperature"] = float(alpha), float(temperature)
-        if row_weights is not None or smoothing is not None:      # the main stream only, as the teacher
-            w = None if row_weights is None else row_weights.detach().reshape(-1)
-            spec["row_weights"] = [w] + [None] * (len(xs) - 1)
-            spec["smoothing_seg"] = [smoothing] + [None] * (len(xs) - 1)
-        if unlikelihood > 0.0:                  # the main stream only, as the teacher
-            spec["unlikelihood"] = (unlikelihood, [y.size(1)] + [None] * (len(xs) - 1))
-        if rdrop > 0.0:                         # the main stream only, as the teacher: rows b T + t and (B + b) T + t are a pair
-            spec["rdrop"] = (rdrop, [y.numel() // 2] + [None] * (len(xs) - 1))
-        out = ops.GeneratorLossFn.apply(spec, *xs)
-        self.last_kd_sum = spec.get("kd_sum")
-        self.last_ul_sum = spec.get("ul_sum")
-        self.last_rd_sum = spec.get("rd_sum")
-        return out
+        rest = [None] * (len(xs) - 1)           # the main stream only: the auto-encoder streams keep the plain loss
+        if obj.kind == "distill":
+            spec["teacher"] = [obj.teacher.reshape(-1, obj.teacher.size(-1))] + rest
+            spec["alpha"], spec["temperature"] = obj.alpha, obj.temperature
+        elif obj.kind == "weighted":
+            spec["row_weights"] = [None if obj.row_weights is None else obj.row_weights.detach().reshape(-1)] + rest
+            spec["smoothing_seg"] = [obj.smoothing] + rest
+        elif obj.kind == "unlikelihood":
+            spec["unlikelihood"] = (obj.alpha, [y.size(1)] + rest)
+        elif obj.kind == "rdrop":               # rows b T + t and (B + b) T + t are a pair
+            spec["rdrop"] = (obj.alpha, [y.numel() // 2] + rest)
+        return ops.GeneratorLossFn.apply(spec, *xs), spec.get(ops.LOSS_HEADS[obj.kind].sum_key)
 
     def _weighted_rows(self, logp, y, row_weights, smoothing):
         """The composed form of the weighted loss head (include/mtn_hip.h mtn_wlosshead_args): sum_rows w KL_ls at ``smoothing``."""
@@ -595,86 +635,52 @@ class SimpleLossCompute:
 
     def loss(self, x, y, norm, ae_x=None, ae_y=None, ae_norm=None, teacher_logp=None, alpha=0.0, temperature=1.0, row_weights=None,
              smoothing=None, unlikelihood=0.0, rdrop=0.0):
-        """``teacher_logp``: (rows, V) fp32 teacher log-probabilities (or logits: they are normalised) for the main stream — word-level
+        """The main stream's objective is at most one of the following (``objective``); the auto-encoder streams keep the plain loss.
+        ``teacher_logp``: (rows, V) fp32 teacher log-probabilities (or logits: they are normalised) for the main stream — word-level
         knowledge distillation, loss = (1 - alpha) KL_ls + alpha T^2 KL(softmax(q / T) || softmax(z / T)) over the rows whose target is
         not <pad>, both over ``norm`` (include/mtn_hip.h mtn_distill_args).  alpha == 0 is the plain loss.  ``last_kd_sum`` is left
         holding the sum of the rows' KL (None without a teacher).
         ``row_weights``: one fp32 weight per main-stream row (signed; no gradient flows into it), loss = sum_rows w KL_ls / norm — the
         policy-gradient loss of self-critical sequence training when w = -(reward - baseline); ``smoothing``: the main stream's label
-        smoothing in the place of the criterion's (0: KL_ls = -log p(target)).  The auto-encoder streams keep the plain loss.  Not
-        together with a teacher (include/mtn_hip.h mtn_wlosshead_args).
+        smoothing in the place of the criterion's (0: KL_ls = -log p(target)) (include/mtn_hip.h mtn_wlosshead_args).
         ``unlikelihood``: alpha >= 0 of token-level unlikelihood training on the main stream, ``y`` (B, T): loss = (KL_ls + alpha
         sum_rows ul) / norm with ul the row's sum over its sequence's earlier targets (a set, without the row's own target and <pad>) of
         -log(clamp(1 - p_c, 1e-5)) (include/mtn_hip.h mtn_ulosshead_args).  0 is the plain loss.  ``last_ul_sum`` is left holding
-        sum_rows ul (None at 0).  Not together with a teacher or row weights.
+        sum_rows ul (None at 0).
         ``rdrop``: alpha >= 0 of R-Drop on the main stream, ``y`` (2 B, T) with sequences b and B + b two passes of one dialogue: loss =
         (KL_ls + alpha sum_rows rd) / norm, rd = (KL(p || q) + KL(q || p)) / 4 between a row and its partner, 0 on <pad>-target rows
-        (include/mtn_hip.h mtn_rlosshead_args).  0 is the plain loss.  ``last_rd_sum`` is left holding sum_rows rd (None at 0).  The
-        auto-encoder streams keep the plain loss.  Not together with a teacher, row weights or unlikelihood."""
-        rdrop = float(rdrop)
-        if not (rdrop >= 0.0 and math.isfinite(rdrop)):
-            raise ValueError("rdrop: alpha is finite and >= 0")
-        if rdrop > 0.0:
-            if teacher_logp is not None:
-                raise ValueError("rdrop and teacher soft targets do not combine")
-            if row_weights is not None or smoothing is not None:
-                raise ValueError("rdrop and row weights do not combine")
-            if float(unlikelihood) > 0.0:
-                raise ValueError("rdrop and unlikelihood do not combine")
-            if y.dim() != 2 or y.size(0) % 2 != 0:
-                raise ValueError("rdrop: y is (2 B, T)")
-        unlikelihood = float(unlikelihood)
-        if not (unlikelihood >= 0.0 and math.isfinite(unlikelihood)):
-            raise ValueError("unlikelihood: alpha is finite and >= 0")
-        if unlikelihood > 0.0:
-            if teacher_logp is not None:
-                raise ValueError("unlikelihood and teacher soft targets do not combine")
-            if row_weights is not None or smoothing is not None:
-                raise ValueError("unlikelihood and row weights do not combine")
-            if y.dim() != 2:
-                raise ValueError("unlikelihood: y is (B, T)")
-        if teacher_logp is not None and not (0.0 <= float(alpha) <= 1.0 and 0.0 < float(temperature) < float("inf")):
-            raise ValueError("distillation: alpha in [0, 1] and a finite temperature > 0")
-        weighted = row_weights is not None or smoothing is not None
-        if weighted and teacher_logp is not None:
-            raise ValueError("row weights and teacher soft targets do not combine")
-        if smoothing is not None and not (0.0 <= float(smoothing) <= 1.0):
-            raise ValueError("smoothing in [0, 1]")
-        if row_weights is not None and row_weights.numel() != y.numel():
-            raise ValueError("row_weights: one weight per target row")
-        self.last_kd_sum = None
-        self.last_ul_sum = None
-        self.last_rd_sum = None
-        fused = self._fused_loss(x, y, norm, ae_x, ae_y, ae_norm, teacher_logp, alpha, temperature, row_weights,
-                                 None if smoothing is None else float(smoothing), unlikelihood, rdrop) if self.fused else None
-        if fused is not None:
-            return fused
-        if teacher_logp is not None and float(alpha) == 0.0:
-            teacher_logp = None                 # as the fused head: the teacher is not read, nothing is multiplied by (1 - alpha)
+        (include/mtn_hip.h mtn_rlosshead_args).  0 is the plain loss.  ``last_rd_sum`` is left holding sum_rows rd (None at 0)."""
+        from . import ops
+        obj = objective(y, teacher_logp, alpha, temperature, row_weights, smoothing, unlikelihood, rdrop)
+        loss, extra = self._fused_head(obj, x, y, norm, ae_x, ae_y, ae_norm) if self.fused else (None, None)
+        if loss is None:
+            loss, extra = self._composed(obj, x, y, norm, ae_x, ae_y, ae_norm)
+        self._extra = (ops.LOSS_HEADS[obj.kind].sum_key, extra)
+        return loss
+
+    def _composed(self, obj: Objective, x, y, norm, ae_x, ae_y, ae_norm):
+        """The same (loss, extra row sum) from PyTorch ops."""
+        pad, extra = self.criterion.padding_idx, None
         out = self.generator(x)
-        if weighted:
-            loss = self._weighted_rows(out.reshape(-1, out.size(-1)), y.reshape(-1), row_weights, smoothing) / norm.float()
+        logp = out.reshape(-1, out.size(-1))
+        if obj.kind == "weighted":
+            loss = self._weighted_rows(logp, y.reshape(-1), obj.row_weights, obj.smoothing) / norm.float()
         else:
-            loss = self.criterion(out.reshape(-1, out.size(-1)), y.reshape(-1)) / norm.float()
-        if teacher_logp is not None:
+            loss = self.criterion(logp, y.reshape(-1)) / norm.float()
+        if obj.kind == "distill" and obj.alpha != 0.0:      # (0, as the fused head: the teacher is not read, nothing is multiplied by 1 - alpha)
             # the composed form of the fused head's soft term: the generator's output is log_softmax(z), and log_softmax(logp / T) ==
             # log_softmax(z / T) (the row's log-sum-exp is a common shift)
-            T = float(temperature)
-            logp = out.reshape(-1, out.size(-1))
-            live = (y.reshape(-1) != self.criterion.padding_idx)
-            q = teacher_logp.reshape(-1, teacher_logp.size(-1)).to(logp.dtype)
+            T = obj.temperature
+            q = obj.teacher.reshape(-1, obj.teacher.size(-1)).to(logp.dtype)
             kd = F.kl_div(torch.log_softmax(logp / T, dim=-1), torch.softmax(q / T, dim=-1), reduction="none").sum(-1)
-            kd = torch.where(live, kd, torch.zeros_like(kd)).sum()
-            self.last_kd_sum = kd.detach()
-            loss = (1.0 - float(alpha)) * loss + float(alpha) * T * T * kd / norm.float()
-        if unlikelihood > 0.0:
-            ul = unlikelihood_rows(out.reshape(y.size(0), y.size(1), out.size(-1)), y, self.criterion.padding_idx).sum()
-            self.last_ul_sum = ul.detach()
-            loss = loss + unlikelihood * ul / norm.float()
-        if rdrop > 0.0:
-            rd = rdrop_rows(out.reshape(-1, out.size(-1)), y, self.criterion.padding_idx).sum()
-            self.last_rd_sum = rd.detach()
-            loss = loss + rdrop * rd / norm.float()
+            extra = torch.where(y.reshape(-1) != pad, kd, torch.zeros_like(kd)).sum()
+            loss = (1.0 - obj.alpha) * loss + obj.alpha * T * T * extra / norm.float()
+        elif obj.kind == "unlikelihood":
+            extra = unlikelihood_rows(out.reshape(y.size(0), y.size(1), out.size(-1)), y, pad).sum()
+            loss = loss + obj.alpha * extra / norm.float()
+        elif obj.kind == "rdrop":
+            extra = rdrop_rows(logp, y, pad).sum()
+            loss = loss + obj.alpha * extra / norm.float()
         if ae_x is not None:
             xs = ae_x if isinstance(ae_x, (list, tuple)) else [ae_x]
             for i, ae_in in enumerate(xs):
@@ -684,7 +690,7 @@ class SimpleLossCompute:
                     gen = self.generator
                 ae_out = gen(ae_in)
                 loss = loss + self.l * self.criterion(ae_out.reshape(-1, ae_out.size(-1)), ae_y.reshape(-1)) / ae_norm.float()
-        return loss
+        return loss, None if extra is None else extra.detach()
 
     def __call__(self, x, y, norm, ae_x=None, ae_y=None, ae_norm=None, teacher_logp=None, alpha=0.0, temperature=1.0, unlikelihood=0.0):
         loss = self.loss(x, y, norm, ae_x, ae_y, ae_norm, teacher_logp, alpha, temperature, unlikelihood=unlikelihood)

@@ -12,7 +12,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass
-from typing import Optional
+from typing import Callable, Optional
 
 import torch
 
@@ -1651,13 +1651,18 @@ class FeatureEncodeFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------ loss head
-def _distill_teachers(spec, rows, V, dev):
-    """spec["teacher"] checked against the streams: None when no stream has a teacher (the plain loss head runs), else the list."""
-    teachers = spec.get("teacher")
-    if teachers is None or all(q is None for q in teachers):
+def _per_stream(vals, rows, key, what):
+    """``vals`` (of spec[key]) as a list of one entry per stream."""
+    if len(vals) != len(rows):
+        raise ValueError("GeneratorLossFn: spec['%s'] holds one %s per stream" % (key, what))
+    return list(vals)
+
+
+def _check_distill(spec, rows, V, dev):
+    """The teachers per stream (a tensor or None), alpha and the temperature; None when no stream has a teacher."""
+    if spec.get("teacher") is None or all(q is None for q in spec["teacher"]):
         return None
-    if len(teachers) != len(rows):
-        raise ValueError("GeneratorLossFn: spec['teacher'] holds one entry (a tensor or None) per stream")
+    teachers = _per_stream(spec["teacher"], rows, "teacher", "entry (a tensor or None)")
     alpha, T = float(spec.get("alpha", 0.5)), float(spec.get("temperature", 1.0))
     if not (0.0 <= alpha <= 1.0) or not (T > 0.0 and math.isfinite(T)):
         raise ValueError("GeneratorLossFn: alpha in [0, 1] and a finite temperature > 0")
@@ -1670,12 +1675,11 @@ def _distill_teachers(spec, rows, V, dev):
                              "multiple of 4, 16-byte aligned")
         if q.requires_grad:
             raise ValueError("GeneratorLossFn: teacher rows carry no gradient (detach them)")
-    return list(teachers)
+    return teachers, alpha, T
 
 
-def _row_weights(spec, rows, dev):
-    """spec["row_weights"] / spec["smoothing_seg"] checked against the streams: None when neither is given (the plain loss head runs), else
-    (weights per stream: a tensor or None, smoothing per stream: a float, negative = the spec's smoothing)."""
+def _check_weighted(spec, rows, V, dev):
+    """(weights per stream: a tensor or None, smoothing per stream: a float, negative = the spec's); None when neither key is given."""
     weights, sms = spec.get("row_weights"), spec.get("smoothing_seg")
     if (weights is None or all(w is None for w in weights)) and sms is None:
         return None
@@ -1695,46 +1699,88 @@ def _row_weights(spec, rows, dev):
     return weights, sms
 
 
-def _unlikelihood(spec, rows):
-    """spec["unlikelihood"] = (alpha, seq_lens per stream: an int or None) checked against the streams: None when it is absent, alpha is 0
-    or no stream has a sequence length (the plain loss head runs), else (alpha, [T per stream, 0 = none])."""
-    ul = spec.get("unlikelihood")
-    if ul is None:
-        return None
-    alpha, lens = ul
-    alpha = float(alpha)
-    if not (alpha >= 0.0 and math.isfinite(alpha)):
-        raise ValueError("GeneratorLossFn: the unlikelihood alpha is finite and >= 0")
-    if len(lens) != len(rows):
-        raise ValueError("GeneratorLossFn: spec['unlikelihood'] holds one sequence length (an int or None) per stream")
-    lens = [0 if T is None else int(T) for T in lens]
-    for T, r in zip(lens, rows):
-        if T < 0 or (T > 0 and r % T != 0):
-            raise ValueError("GeneratorLossFn: a stream's rows are a multiple of its sequence length")
-    if alpha == 0.0 or not any(lens):
-        return None
-    return alpha, lens
+def _check_alpha_ints(key, name, what, fits, misfit):
+    """The validator of a head that is spec[key] = (alpha, per stream an int or None): (alpha, [int per stream, 0 = none]); None when the
+    key is absent, alpha is 0 or no stream has an int (the plain head runs)."""
+    def check(spec, rows, V, dev):
+        if spec.get(key) is None:
+            return None
+        alpha = float(spec[key][0])
+        if not (alpha >= 0.0 and math.isfinite(alpha)):
+            raise ValueError("GeneratorLossFn: the %s alpha is finite and >= 0" % name)
+        ints = [0 if n is None else int(n) for n in _per_stream(spec[key][1], rows, key, what + " (an int or None)")]
+        if any(n < 0 or (n > 0 and not fits(r, n)) for n, r in zip(ints, rows)):
+            raise ValueError("GeneratorLossFn: " + misfit)
+        return (alpha, ints) if alpha != 0.0 and any(ints) else None
+    return check
 
 
-def _rdrop(spec, rows):
-    """spec["rdrop"] = (alpha, pair distances per stream: an int N or None) checked against the streams: None when it is absent, alpha is 0
-    or no stream is paired (the plain loss head runs), else (alpha, [N per stream, 0 = unpaired])."""
-    rd = spec.get("rdrop")
-    if rd is None:
-        return None
-    alpha, pairs = rd
-    alpha = float(alpha)
-    if not (alpha >= 0.0 and math.isfinite(alpha)):
-        raise ValueError("GeneratorLossFn: the R-Drop alpha is finite and >= 0")
-    if len(pairs) != len(rows):
-        raise ValueError("GeneratorLossFn: spec['rdrop'] holds one pair distance (an int or None) per stream")
-    pairs = [0 if N is None else int(N) for N in pairs]
-    for N, r in zip(pairs, rows):
-        if N < 0 or (N > 0 and r != 2 * N):
-            raise ValueError("GeneratorLossFn: a paired stream holds 2 N rows, N its pair distance")
-    if alpha == 0.0 or not any(pairs):
-        return None
-    return alpha, pairs
+def _fill_distill(A, p, R, dev):
+    teachers, A.alpha, A.temperature = p
+    for i, q in enumerate(teachers):
+        if q is not None:
+            A.teacher[i], A.ldq[i] = q.data_ptr(), q.stride(0)
+    rowkd = torch.empty(R, device=dev, dtype=torch.float32)
+    A.rowkd = rowkd.data_ptr()
+    return [rowkd]
+
+
+def _fill_weighted(A, p, R, dev):
+    for i, (w, sm) in enumerate(zip(*p)):
+        A.roww[i], A.smoothing_seg[i] = L.ptr(w), sm
+    return []
+
+
+def _fill_alpha_ints(alpha, ints, *row_fields):
+    """The fill of such a head: its alpha, its int per stream, and one fp32 row buffer per field of ``row_fields``."""
+    def fill(A, p, R, dev):
+        setattr(A, alpha, p[0])
+        for i, n in enumerate(p[1]):
+            getattr(A, ints)[i] = n
+        made = [torch.empty(R, device=dev, dtype=torch.float32) for _ in row_fields]
+        for f, t in zip(row_fields, made):
+            setattr(A, f, t.data_ptr())
+        return made
+    return fill
+
+
+@dataclass(frozen=True)
+class LossHead:
+    """One form of the loss head (csrc/losshead.hip).  ``keys``: the spec keys that switch it on; ``check(spec, rows, V, dev)``: its
+    validator, None = the spec does not ask for it, else its parameters; ``args`` / ``entry``: the lib.py argument struct and the stem of
+    the mtn_<entry>_fwd / _bwd entry points; ``fill(A, parameters, R, dev)`` writes the form's fields and returns the tensors it allocated,
+    the form's extra row term first; ``sum_key``: the spec key that term's sum is left under; ``label``: how a conflict names the form."""
+    keys: tuple
+    check: Optional[Callable]
+    args: str
+    entry: str
+    fill: Optional[Callable] = None
+    sum_key: Optional[str] = None
+    label: str = ""
+
+
+# At most one form besides "plain" per call (each is the plain head with one extra term: include/mtn_hip.h).  The validators run in this
+# order, and a conflict names the last form asked for, then the first.
+LOSS_HEADS = {
+    "distill": LossHead(("teacher", "alpha", "temperature"), _check_distill, "DistillHeadArgs", "distill", _fill_distill, "kd_sum",
+                        "teacher soft targets"),
+    "weighted": LossHead(("row_weights", "smoothing_seg"), _check_weighted, "WLossHeadArgs", "wlosshead", _fill_weighted, None, "row weights"),
+    "unlikelihood": LossHead(("unlikelihood",), _check_alpha_ints("unlikelihood", "unlikelihood", "sequence length", lambda r, T: r % T == 0,
+                                                                  "a stream's rows are a multiple of its sequence length"),
+                             "ULossHeadArgs", "ulosshead", _fill_alpha_ints("ul_alpha", "seq_len", "rowul"), "ul_sum", "unlikelihood"),
+    "rdrop": LossHead(("rdrop",), _check_alpha_ints("rdrop", "R-Drop", "pair distance", lambda r, N: r == 2 * N,
+                                                    "a paired stream holds 2 N rows, N its pair distance"),
+                      "RLossHeadArgs", "rlosshead", _fill_alpha_ints("rd_alpha", "pair", "rowrd", "rowkl"), "rd_sum", "R-Drop"),
+    "plain": LossHead((), None, "LossHeadArgs", "losshead"),
+}
+
+
+def one_loss_head(asked, prefix=""):
+    """The one form among ``asked`` (kinds, in LOSS_HEADS' order), "plain" for none; two do not combine."""
+    if len(asked) > 1:
+        a, b = LOSS_HEADS[asked[-1]].label, LOSS_HEADS[asked[0]].label
+        raise ValueError("%s%s %s not combine with %s" % (prefix, a, "do" if a.endswith("s") else "does", b))
+    return asked[0] if asked else "plain"
 
 
 class GeneratorLossFn(torch.autograd.Function):
@@ -1743,20 +1789,16 @@ class GeneratorLossFn(torch.autograd.Function):
     one grouped GEMM (logits), one row kernel (log-sum-exp + closed-form KL); backward: one row kernel (dlogits), two
     grouped GEMMs (dX, dW+db).  `spec`: targets, norms (device float scalars), coefs, gens [(w_lp, bias, grad_w, grad_b)],
     vocab, pad, smoothing, lp_dtype.  Generator gradients are written to the flat gradient buffer (not returned).
-    Knowledge distillation: ``spec["teacher"]`` = per stream a (rows_i, V) fp32 device tensor of teacher logits / log-probabilities or
-    None, with ``spec["alpha"]`` and ``spec["temperature"]``.  With any teacher present the row kernels are mtn_distill_fwd / _bwd
-    (csrc/losshead.hip; include/mtn_hip.h) in the place of the two loss-head calls, casts and GEMMs unchanged, and ``spec["kd_sum"]`` is
-    left holding the device scalar sum_rows kd; with none the calls are exactly the loss head's.
-    Signed row weights (self-critical sequence training): ``spec["row_weights"]`` = per stream a contiguous fp32 device tensor of one weight
-    per row or None (all ones), ``spec["smoothing_seg"]`` = per stream a smoothing or None (the spec's).  With either present the row
-    kernels are mtn_wlosshead_fwd / _bwd (csrc/losshead.hip); not together with a teacher.
-    Unlikelihood training (Welleck et al. 2019): ``spec["unlikelihood"]`` = (alpha, per stream the sequence length T of its (B, T) targets
-    or None).  With it present and alpha > 0 the row kernels are mtn_ulosshead_fwd / _bwd (csrc/losshead.hip; include/mtn_hip.h), casts and
-    GEMMs unchanged, and ``spec["ul_sum"]`` is left holding the device scalar sum_rows ul; not together with a teacher or row weights.
-    R-Drop (Liang et al. 2021): ``spec["rdrop"]`` = (alpha, per stream the pair distance N of its 2 N rows — rows i and i + N are two passes
-    of one position — or None).  With it present and alpha > 0 the row kernels are mtn_rlosshead_fwd / _bwd (csrc/losshead.hip;
-    include/mtn_hip.h), casts and GEMMs unchanged, and ``spec["rd_sum"]`` is left holding the device scalar sum_rows rd; not together with a
-    teacher, row weights or unlikelihood."""
+    One more term on any stream (LOSS_HEADS: at most one form per call) puts that form's row kernels, mtn_<entry>_fwd / _bwd of
+    csrc/losshead.hip (include/mtn_hip.h gives the formulas), in the place of the two loss-head calls, casts and GEMMs unchanged:
+    knowledge distillation: ``spec["teacher"]`` = per stream a (rows_i, V) fp32 device tensor of teacher logits / log-probabilities or
+    None, with ``spec["alpha"]`` and ``spec["temperature"]``; ``spec["kd_sum"]`` is left holding the device scalar sum_rows kd;
+    signed row weights (self-critical sequence training): ``spec["row_weights"]`` = per stream a contiguous fp32 device tensor of one weight
+    per row or None (all ones), ``spec["smoothing_seg"]`` = per stream a smoothing or None (the spec's);
+    unlikelihood training (Welleck et al. 2019): ``spec["unlikelihood"]`` = (alpha > 0, per stream the sequence length T of its (B, T)
+    targets or None); ``spec["ul_sum"]`` is left holding the device scalar sum_rows ul;
+    R-Drop (Liang et al. 2021): ``spec["rdrop"]`` = (alpha > 0, per stream the pair distance N of its 2 N rows — rows i and i + N are two
+    passes of one position — or None); ``spec["rd_sum"]`` is left holding the device scalar sum_rows rd."""
 
     @staticmethod
     def forward(ctx, spec, *xs):
@@ -1806,29 +1848,10 @@ class GeneratorLossFn(torch.autograd.Function):
             p.bias, p.gate_scale, p.out_f32, p.ldc = bias.data_ptr(), 1.0, logits[o:].data_ptr(), V
             probs.append(p)
         gemm(code, probs)
-        teachers = _distill_teachers(spec, rows, V, dev)
-        weighted = _row_weights(spec, rows, dev)
-        if teachers is not None and weighted is not None:
-            raise ValueError("GeneratorLossFn: row weights and teacher soft targets do not combine")
-        unlikely = _unlikelihood(spec, rows)
-        if unlikely is not None and (teachers is not None or weighted is not None):
-            raise ValueError("GeneratorLossFn: unlikelihood does not combine with %s" % ("teacher soft targets" if teachers is not None
-                                                                                         else "row weights"))
-        rdrop = _rdrop(spec, rows)
-        if rdrop is not None and (teachers is not None or weighted is not None or unlikely is not None):
-            raise ValueError("GeneratorLossFn: R-Drop does not combine with %s" % ("teacher soft targets" if teachers is not None
-                                                                                   else "row weights" if weighted is not None else "unlikelihood"))
-        if rdrop is not None:
-            args_cls, fwd, bwd = L.RLossHeadArgs, lib.mtn_rlosshead_fwd, lib.mtn_rlosshead_bwd
-        elif unlikely is not None:
-            args_cls, fwd, bwd = L.ULossHeadArgs, lib.mtn_ulosshead_fwd, lib.mtn_ulosshead_bwd
-        elif weighted is not None:
-            args_cls, fwd, bwd = L.WLossHeadArgs, lib.mtn_wlosshead_fwd, lib.mtn_wlosshead_bwd
-        elif teachers is not None:
-            args_cls, fwd, bwd = L.DistillHeadArgs, lib.mtn_distill_fwd, lib.mtn_distill_bwd
-        else:
-            args_cls, fwd, bwd = L.LossHeadArgs, lib.mtn_losshead_fwd, lib.mtn_losshead_bwd
-        A = args_cls()
+        params = {kind: p for kind, h in LOSS_HEADS.items() if h.check is not None for p in [h.check(spec, rows, V, dev)] if p is not None}
+        head = LOSS_HEADS[one_loss_head(list(params), "GeneratorLossFn: ")]
+        params = next(iter(params.values()), None)
+        A = getattr(L, head.args)()
         A.n_seg = len(xs)
         norms = [n.float().reshape(1) if n.dtype != torch.float32 or n.dim() == 0 else n for n in spec["norms"]]
         targets = [t.contiguous().view(-1) for t in spec["targets"]]
@@ -1838,35 +1861,12 @@ class GeneratorLossFn(torch.autograd.Function):
         lse = torch.empty(R, device=dev, dtype=torch.float32)
         rowloss = torch.empty(R, device=dev, dtype=torch.float32)
         A.logits, A.lse, A.rowloss = logits.data_ptr(), lse.data_ptr(), rowloss.data_ptr()
-        if weighted is not None:
-            for i, (w, sm) in enumerate(zip(*weighted)):
-                A.roww[i], A.smoothing_seg[i] = L.ptr(w), sm
-        elif teachers is not None:
-            rowkd = torch.empty(R, device=dev, dtype=torch.float32)
-            for i, q in enumerate(teachers):
-                if q is not None:
-                    A.teacher[i], A.ldq[i] = q.data_ptr(), q.stride(0)
-            A.alpha, A.temperature, A.rowkd = float(spec.get("alpha", 0.5)), float(spec.get("temperature", 1.0)), rowkd.data_ptr()
-        elif unlikely is not None:
-            rowul = torch.empty(R, device=dev, dtype=torch.float32)
-            for i, T in enumerate(unlikely[1]):
-                A.seq_len[i] = T
-            A.ul_alpha, A.rowul = unlikely[0], rowul.data_ptr()
-        elif rdrop is not None:
-            rowrd = torch.empty(R, device=dev, dtype=torch.float32)
-            rowkl = torch.empty(R, device=dev, dtype=torch.float32)
-            for i, N in enumerate(rdrop[1]):
-                A.pair[i] = N
-            A.rd_alpha, A.rowrd, A.rowkl = rdrop[0], rowrd.data_ptr(), rowkl.data_ptr()
-        L.check(fwd(C.byref(A), L.stream_ptr()))
-        if teachers is not None:
-            spec["kd_sum"] = rowkd.sum()
-        if unlikely is not None:
-            spec["ul_sum"] = rowul.sum()
-        if rdrop is not None:
-            spec["rd_sum"] = rowrd.sum()
-        ctx.args, ctx.bwd = A, bwd
-        ctx.keep = (x_lp, logits, lse, norms, targets, teachers if weighted is None else weighted, rowkl if rdrop is not None else None)
+        made = head.fill(A, params, R, dev) if head.fill is not None else []
+        L.check(getattr(lib, "mtn_%s_fwd" % head.entry)(C.byref(A), L.stream_ptr()))
+        if head.sum_key is not None:
+            spec[head.sum_key] = made[0].sum()
+        ctx.args, ctx.bwd = A, getattr(lib, "mtn_%s_bwd" % head.entry)
+        ctx.keep = (x_lp, logits, lse, norms, targets, params, made)      # (everything ctx.args points to: the form's inputs and its rows)
         ctx.meta = (spec, segs, rows, offs, d, V, R, code, [x.shape for x in xs])
         return rowloss.sum()
 

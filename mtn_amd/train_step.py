@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -123,6 +123,63 @@ class SchedConfig:
         return float(f(self.prob) * min(f(1.0), f(d / f(self.ramp))))
 
 
+_NAMES = {"teacher": "a teacher (distillation)", "scst": "scst", "unlikelihood": "unlikelihood", "sched": "sched (scheduled sampling)",
+          "rdrop": "rdrop"}
+
+
+def check_objectives(who, *, teacher=None, distill_alpha=0.5, distill_temperature=1.0, scst=None, unlikelihood=0.0, rdrop=0.0, sched=None,
+                     clip_grad_norm=0.0, clipping=False, accumulating=False, grad_sync=None):
+    """What a step's keywords may hold and which of them combine, for TrainStep and BucketedTrainer (``who``: the message's prefix).
+    Conflicts are reported in the order of the lines below.  ``clipping`` / ``accumulating``: what the step's optimiser has enabled."""
+    def fail(msg):
+        raise ValueError("%s: %s" % (who, msg))
+
+    def alpha(name, a):
+        if not (a >= 0.0 and math.isfinite(a)):
+            fail("%s is finite and >= 0" % name)
+        return a > 0.0
+
+    on = dict(teacher=teacher is not None, scst=scst is not None, sched=sched is not None, unlikelihood=float(unlikelihood) > 0.0)
+
+    def alone(name, *others):
+        for o in others:
+            if on[o]:
+                fail("%s does not combine with %s" % (_NAMES[name], _NAMES[o]))
+
+    if alpha("rdrop", float(rdrop)):
+        alone("rdrop", "teacher", "scst", "unlikelihood", "sched")      # (sched keys rows by batch index: the halves would see different inputs)
+    if on["sched"]:
+        alone("sched", "teacher", "scst")                               # (a teacher would have to see the mixed inputs)
+    if not float(clip_grad_norm) >= 0.0:                                # (nan fails the comparison)
+        fail("clip_grad_norm is 0 (off) or > 0 (inf allowed)")
+    if alpha("unlikelihood", float(unlikelihood)):
+        alone("unlikelihood", "teacher", "scst")
+    if on["teacher"]:
+        if not (0.0 <= float(distill_alpha) <= 1.0):
+            fail("distill_alpha in [0, 1]")
+        if not (0.0 < float(distill_temperature) < float("inf")):
+            fail("distill_temperature is finite and > 0")
+    if on["scst"] and accumulating:
+        fail("scst does not combine with gradient accumulation: rl_step is one update per call")
+    if on["scst"] and (on["teacher"] or grad_sync is not None):
+        fail("scst does not combine with a teacher (distillation) or with data parallelism")
+    if grad_sync is not None and os.environ.get("MTN_DP_SHARDED", "0") != "0":      # asked for explicitly: the default gives way instead
+        for flag, what, why in ((clipping, "gradient clipping", "the norm needs every slice reduced before any shard is updated"),
+                                (accumulating, "gradient accumulation", "the update runs once per window, from the whole window gradient")):
+            if flag:
+                fail("%s does not combine with the sharded data-parallel optimiser (MTN_DP_SHARDED): %s; leave MTN_DP_SHARDED unset or 0"
+                     % (what, why))
+
+
+class _Stage(NamedTuple):
+    """One stage of a step's schedule.  ``unit``: a callable whose launches are ONE graph of the captured step (None: nothing to capture);
+    ``after``: what runs eagerly behind it, captured or not — the accumulate launch, a gradient exchange; ``closing``: the stage runs
+    only in the call that closes an accumulation window."""
+    unit: Optional[Callable] = None
+    after: Optional[Callable] = None
+    closing: bool = False
+
+
 class TrainStep:
     def __init__(self, model, batch, vocab: int, pad: int = 1, warmup: int = 4000, factor: float = 1.0, lam: float = 1.0,
                  smoothing: float = 0.1, grad_sync=None, use_graph: bool = True, overlap: Optional[bool] = None, opt=None,
@@ -130,7 +187,8 @@ class TrainStep:
                  distill_temperature: float = 1.0, ema_decay: float = 0.0, scst: Optional[ScstConfig] = None, unlikelihood: float = 0.0,
                  clip_grad_norm: float = 0.0, accumulate: bool = False, sched: Optional[SchedConfig] = None, rdrop: float = 0.0,
                  rdrop_paired: bool = False):
-        """``opt``: share an existing NoamOpt (several TrainSteps over one model, e.g. one per batch shape).
+        """Which of the keywords below combine, and what they may hold, is check_objectives' to say.
+        ``opt``: share an existing NoamOpt (several TrainSteps over one model, e.g. one per batch shape).
         ``dynamic_norms``: the batch tensors are refilled in place between steps, so the loss normalisers (token counts,
         train.py:35-39) are recomputed from them inside the step instead of once at construction.
         ``fuse_optimizer``: None = on one rank, apply Adam to the sublayer weight matrices inside their parameter-gradient
@@ -163,18 +221,16 @@ class TrainStep:
         ``unlikelihood``: alpha of token-level unlikelihood training (Welleck et al. 2019) on the MAIN decoder stream: its loss becomes
         label-smoothed KL + alpha * sum over each target row of -log(clamp(1 - p_c, 1e-5)) over the set of its sequence's earlier targets
         (mtn_ulosshead_fwd / _bwd in the place of the two loss-head launches, inside the captured graph; the head is local to the rank, so
-        data parallelism needs nothing new).  0 = the plain step, launch for launch and bit for bit.  Not together with a teacher or
-        scst.  ``last_ul``: device scalar, the step's summed ul over its target-token normaliser.
+        data parallelism needs nothing new).  0 = the plain step, launch for launch and bit for bit.  ``last_ul``: device scalar, the
+        step's summed ul over its target-token normaliser.
         ``clip_grad_norm``: C > 0 (inf allowed: measure, never clip) = the optimiser built here clips the gradient's global L2 norm at C
         as torch.nn.utils.clip_grad_norm_ does (FusedAdam.enable_clip: mtn_grad_sumsq + mtn_clip_scale ahead of mtn_adam_step, the
         coefficient never leaves the device); a shared ``opt`` keeps whatever its owner enabled.  0 = off: the step is what it is
         without the keyword, launch for launch.  Adam is not linear in g, so a clipped step takes the separate-optimiser path
         (``fuse_optimizer`` = False) in every schedule — eager, the one-graph capture, rl_step under scst — and pays for the gradient's
         HBM round trip.  Data parallelism uses the all-reduce scheme with clipping on (the layer-segmented overlap stays): after the
-        exchange every rank holds the whole reduced gradient and computes the same norm bits with no further collective.  Clipping
-        under the SHARDED optimiser is out of scope (every slice would have to be reduced before any shard is updated, which undoes
-        that schedule's point): asking for it explicitly (MTN_DP_SHARDED=1) raises.  ``last_grad_norm``: device double, the norm of
-        the step just run (None when clipping is off).
+        exchange every rank holds the whole reduced gradient and computes the same norm bits with no further collective.
+        ``last_grad_norm``: device double, the norm of the step just run (None when clipping is off).
         ``accumulate``: gradient accumulation over a window of micro-batches — the optimiser built here keeps a second flat fp32 buffer
         (FusedAdam.enable_accumulation; a shared ``opt`` keeps whatever its owner enabled) and ``__call__(last)`` is one MICRO-step:
         today's forward, loss and backward, normalised by its own token counts, then one mtn_grad_accum launch weighted by the
@@ -187,8 +243,8 @@ class TrainStep:
         ``fuse_optimizer`` = False step bit for bit.  The captured form is a forward/backward graph and an optimiser graph with the
         accumulate launch (and the exchange) between the replays; nothing in a window synchronises with the host.  The returned
         loss is the micro-step's own.  Data parallelism: the whole-buffer, non-overlapped all-reduce, once per window, after the
-        closing launch; MTN_DP_SHARDED=1 raises.  With clipping on one rank the closing launch also writes the partials of G's sum
-        of squares and the update skips its mtn_grad_sumsq launch.  Not together with scst.
+        closing launch.  With clipping on one rank the closing launch also writes the partials of G's sum of squares and the update
+        skips its mtn_grad_sumsq launch.
         ``sched``: scheduled sampling (SchedConfig).  Inside the step (and its captured graph), before the training forward, the student
         itself runs an eval() forward on the gold batch under no_grad, its generator logits go through one mtn_sched_mix launch into
         ``sched_mixed`` (allocated once), and the training forward reads a shallow copy of the batch whose ``trg`` is that buffer:
@@ -198,7 +254,7 @@ class TrainStep:
         update count on the device, so every replay draws anew, a resumed run continues the stream, and the micro-steps of an
         accumulation window share it (on a fixed batch they repeat their draws).  ``sched_stats`` (3,) int64 on the device counts
         [eligible, replaced, replaced with another token than gold] until the caller zeroes it.  None = off: nothing is allocated or
-        launched.  Not together with a teacher (it would have to see the mixed inputs) or scst.
+        launched.
         ``rdrop``: alpha of R-Drop (Liang et al. 2021) on the MAIN decoder stream.  ``batch`` is then the SOURCE of B dialogues and the
         step trains on a static batch of its own (``self.batch``) of 2 B rows, rows b and B + b the same dialogue: a dropout site's
         keep-mask is a counter hash of (seed, salt, flat element index), so the two copies draw different masks in ONE forward pass.
@@ -211,42 +267,24 @@ class TrainStep:
         parallelism needs nothing new.  ``rdrop_paired``: ``batch`` already holds 2 N rows in pair layout and is used as it is (checked
         once: trg_y[:N] == trg_y[N:]).  0 = off: nothing is allocated or launched, the step is the plain step launch for launch and bit
         for bit.  Combines with clip_grad_norm, ema_decay, accumulate, both optimiser paths, graph and eager and both data-parallel
-        schedules.  Not together with a teacher, scst, unlikelihood or sched (the mix keys rows by batch index: the halves would
-        see different inputs)."""
+        schedules."""
+        shared = None if opt is None else opt.optimizer
+        check_objectives("TrainStep", teacher=teacher, distill_alpha=distill_alpha, distill_temperature=distill_temperature, scst=scst,
+                         unlikelihood=unlikelihood, rdrop=rdrop, sched=sched, clip_grad_norm=clip_grad_norm, grad_sync=grad_sync,
+                         clipping=bool(clip_grad_norm) if shared is None else getattr(shared, "clip_max_norm", None) is not None,
+                         accumulating=bool(accumulate) or getattr(shared, "accum", None) is not None)
         self.model, self.batch = model, batch
         self.rdrop, self.last_rd, self._rd_src = float(rdrop), None, None
-        if not (self.rdrop >= 0.0 and math.isfinite(self.rdrop)):
-            raise ValueError("TrainStep: rdrop is finite and >= 0")
         if self.rdrop > 0.0:
-            for on, what in ((teacher is not None, "a teacher (distillation)"), (scst is not None, "scst"),
-                             (float(unlikelihood) > 0.0, "unlikelihood"), (sched is not None, "sched (scheduled sampling)")):
-                if on:
-                    raise ValueError("TrainStep: rdrop does not combine with %s" % what)
             if rdrop_paired:
                 self._check_paired(batch)
             else:
                 self._init_rdrop(batch, pad)
                 batch = self.batch
-        self.sched = sched
-        if sched is not None and (teacher is not None or scst is not None):
-            raise ValueError("TrainStep: sched (scheduled sampling) does not combine with %s" % ("a teacher (distillation)" if teacher is not None
-                                                                                                  else "scst"))
-        clip_grad_norm = float(clip_grad_norm)
-        if not clip_grad_norm >= 0.0:              # (nan fails the comparison)
-            raise ValueError("TrainStep: clip_grad_norm is 0 (off) or > 0 (inf allowed)")
+        self.sched, self.scst = sched, scst
         self.unlikelihood, self.last_ul = float(unlikelihood), None
-        if not (self.unlikelihood >= 0.0 and math.isfinite(self.unlikelihood)):
-            raise ValueError("TrainStep: unlikelihood is finite and >= 0")
-        if self.unlikelihood > 0.0 and (teacher is not None or scst is not None):
-            raise ValueError("TrainStep: unlikelihood does not combine with %s" % ("a teacher (distillation)" if teacher is not None
-                                                                                   else "scst"))
         self._init_teacher(teacher, distill_alpha, distill_temperature, vocab)
-        self.scst = scst
-        if scst is not None and (accumulate or (opt is not None and getattr(opt.optimizer, "accum", None) is not None)):
-            raise ValueError("TrainStep: scst does not combine with gradient accumulation (accumulate=True): rl_step is one update per call")
         if scst is not None:
-            if teacher is not None or grad_sync is not None:
-                raise ValueError("TrainStep: scst does not combine with a teacher (distillation) or with data parallelism")
             self._init_scst(batch, pad)
             batch, dynamic_norms = self.batch, True
         if opt is None:
@@ -266,20 +304,27 @@ class TrainStep:
         self.grad_sync = grad_sync
         self.pad = pad
         self.use_graph = use_graph
-        self._g_fb = self._g_opt = None
+        self._g_fb = self._g_opt = self._replays = None
         self._loss = None
+        self._closing = True
+        # the main stream's objective as SimpleLossCompute.loss keywords (the teacher's rows join them per step), and the pair
+        # (attribute here, the loss computer's row sum) behind last_kd / last_ul / last_rd
+        if scst is not None:
+            self._loss_kw, self._last = dict(row_weights=self._roww, smoothing=0.0), None
+        elif self.rdrop > 0.0:
+            self._loss_kw, self._last = dict(rdrop=self.rdrop), ("last_rd", "last_rd_sum")
+        elif self.unlikelihood > 0.0:
+            self._loss_kw, self._last = dict(unlikelihood=self.unlikelihood), ("last_ul", "last_ul_sum")
+        elif teacher is not None:
+            self._loss_kw, self._last = dict(alpha=self.distill_alpha, temperature=self.distill_temperature), ("last_kd", "last_kd_sum")
+        else:
+            self._loss_kw, self._last = {}, None
         if overlap is None:
             overlap = os.environ.get("MTN_DP_OVERLAP", "1") != "0"
         self.overlap = bool(overlap) and grad_sync is not None and not self.accumulating     # (accumulation: the whole-buffer exchange)
         # data parallel: reduce-scatter + optimiser on this rank's shard + all-gather of the master weights
         # (dp.ShardedOptimizerSync) instead of all-reduce + the full optimiser pass on every rank; MTN_DP_SHARDED=0 = the latter
         self.sharded = None
-        if self.clipping and grad_sync is not None and os.environ.get("MTN_DP_SHARDED", "0") != "0":
-            raise ValueError("TrainStep: gradient clipping does not combine with the sharded data-parallel optimiser (MTN_DP_SHARDED): "
-                             "the norm needs every slice reduced before any shard is updated; leave MTN_DP_SHARDED unset or 0")
-        if self.accumulating and grad_sync is not None and os.environ.get("MTN_DP_SHARDED", "0") != "0":
-            raise ValueError("TrainStep: gradient accumulation does not combine with the sharded data-parallel optimiser (MTN_DP_SHARDED): "
-                             "the update runs once per window, from the whole window gradient; leave MTN_DP_SHARDED unset or 0")
         if (grad_sync is not None and not self.clipping and not self.accumulating and os.environ.get("MTN_DP_SHARDED", "1") != "0"
                 and hasattr(self.opt.optimizer, "step_range")):
             from .dp import ShardedOptimizerSync
@@ -345,10 +390,6 @@ class TrainStep:
         if teacher is None:
             return
         members, _, _ = teacher_members(teacher)
-        if not (0.0 <= self.distill_alpha <= 1.0):
-            raise ValueError("TrainStep: distill_alpha in [0, 1]")
-        if not (0.0 < self.distill_temperature < float("inf")):
-            raise ValueError("TrainStep: distill_temperature is finite and > 0")
         dev = next(self.model.parameters()).device
         for m in members:
             if m is self.model:
@@ -633,35 +674,32 @@ class TrainStep:
 
     def _loss_of(self, out, ae_out, teacher_rows):
         """The step's loss, for both schedules (monolithic _fwd_bwd, the segmented top())."""
-        if self.scst is not None:
-            return self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], row_weights=self._roww,
-                                smoothing=0.0)
-        if self.rdrop > 0.0:
-            loss = self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], rdrop=self.rdrop)
-            self.last_rd = self.lc.last_rd_sum / self._norms[0]
-            return loss
-        if self.unlikelihood > 0.0:
-            loss = self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], unlikelihood=self.unlikelihood)
-            self.last_ul = self.lc.last_ul_sum / self._norms[0]
-            return loss
-        if teacher_rows is None:
-            return self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1])
-        loss = self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], teacher_logp=teacher_rows,
-                            alpha=self.distill_alpha, temperature=self.distill_temperature)
-        kd = self.lc.last_kd_sum
-        self.last_kd = kd / self._norms[0] if kd is not None else torch.zeros_like(self._norms[0])
+        kw = self._loss_kw if teacher_rows is None else dict(self._loss_kw, teacher_logp=teacher_rows)
+        loss = self.lc.loss(out, self.batch.trg_y, self._norms[0], ae_out, self._ae_y, self._norms[1], **kw)
+        if self._last is not None:
+            attr, of = self._last
+            s = getattr(self.lc, of)             # (None: a teacher at alpha 0 on the composed path)
+            setattr(self, attr, s / self._norms[0] if s is not None else torch.zeros_like(self._norms[0]))
         return loss
 
-    def _fwd_bwd(self, fuse: bool = False):
-        m, b = self.model, self.batch
+    def _begin_step(self):
+        """The head of a step in every schedule: the R-Drop refill, the in-step normalisers, the scheduled-sampling and teacher passes,
+        the glue gradients zeroed, and whatever a step that raised left queued or in exchange dropped (never mixed into this one; nothing
+        happens on a clean state).  Returns the teacher's rows (None without a teacher)."""
+        m, sh = self.model, self.sharded
         self._rdrop_refill()
         self._refresh_norms()
         teacher_rows = self._teacher_pass()
         m.zero_glue_grads()
         if m._queue is not None and (m._queue.gemm or m._queue.ln or m._queue._armed):
-            m._queue.reset()               # left over from a step that raised: never mix it into this one
-        if getattr(self, "sharded", None) is not None and (self.sharded._pending is not None or self.sharded._works):
-            self.sharded.abort()           # ... nor its deferred shard update / gather
+            m._queue.reset()
+        if sh is not None and (sh._pending is not None or sh._works):
+            sh.abort()
+        return teacher_rows
+
+    def _fwd_bwd(self, fuse: bool = False):
+        m = self.model
+        teacher_rows = self._begin_step()
         if fuse:
             self.opt.begin_fused_step()
         try:
@@ -669,12 +707,16 @@ class TrainStep:
             loss = self._loss_of(out, ae_out, teacher_rows)
             loss.backward(self._unit_grad(loss))          # (a kept ones scalar: autograd would launch a fill for the implicit one)
         except BaseException:
-            if m._queue is not None:
-                m._queue.reset()
-            if getattr(self, "sharded", None) is not None:
-                self.sharded.abort()
+            self._drop_step()
             raise
         return loss.detach()
+
+    def _drop_step(self):
+        """After a step that raised: its queued parameter-gradient work and its deferred shard update / gather never reach the next one."""
+        if self.model._queue is not None:
+            self.model._queue.reset()
+        if self.sharded is not None:
+            self.sharded.abort()
 
     def _unit_grad(self, loss):
         g = getattr(self, "_one", None)
@@ -698,13 +740,10 @@ class TrainStep:
 
     # ---- layer-segmented backward (data parallel, overlapped exchange)
     def _segments(self):
-        """[(callable, (lo, hi) slice of the flat gradient buffer that is final once the callable has run)]"""
+        """[(callable, the (lo, hi, mat_hi) slice of _slices() that is final once the callable has run)]"""
         m = self.model
-        m.prepare()
-        sl = m._layer_slices
-        total = m._flat_grad.numel()
-        N = len(sl)
-        assert all(sl[k][1] == sl[k + 1][0] for k in range(N - 1)), "layer slices not contiguous"
+        slices = self._slices()
+        N = len(m._layer_slices)
 
         def bwd(outs, leaves):
             # An auto-encoder output is BOTH the next layer's chain input (across the cut: its gradient arrives as leaf.grad) and the
@@ -730,18 +769,14 @@ class TrainStep:
                 torch.autograd.backward(roots, grads)
 
         def top():
-            b = self.batch
-            self._rdrop_refill()
-            self._refresh_norms()
-            teacher_rows = self._teacher_pass()
-            m.zero_glue_grads()
+            teacher_rows = self._begin_step()
             st = m.forward_segmented(self._fwd_batch)
             self._st = st
             loss = self._loss_of(st["out"], st["ae_out"], teacher_rows)
             loss.backward(self._unit_grad(loss))                # loss head + final LayerNorms
             ins, outs = st["layers"][N - 1]
             bwd(outs, st["top_in"])                             # top decoder layer
-            self._loss_t = loss.detach()
+            self._loss = self._loss_t = loss.detach()
 
         def layer(k):
             def run():
@@ -755,39 +790,73 @@ class TrainStep:
             bwd(st["enc_out"], st["enc_leaf"])                  # embeddings, feature Linears, Encoder LayerNorms
             self._st = None
 
-        # a layer's slice is its weight matrices (mtn.py _ordered_params): mat_hi = hi -> they travel in the compute dtype; the last
-        # slice = glue parameters + every vector (biases, all LayerNorms): fp32 throughout, complete once the last segment has run
-        assert sl[N - 1][1] == total, "the last layer's matrices end the flat buffer"
-        segs = [(top, (sl[N - 1][0], total, total))]
-        segs += [(layer(k), sl[k] + (sl[k][1],)) for k in range(N - 2, -1, -1)]
-        segs.append((enc, (0, sl[0][0], None)))
-        return segs
+        return list(zip([top] + [layer(k) for k in range(N - 2, -1, -1)] + [enc], slices))
 
-    def _run_segmented(self, runners):
-        if self.sharded is not None:
-            if self.sharded._pending is not None or self.sharded._works:
-                self.sharded.abort()                    # left over from a step that raised between reduce_update() and finish()
+    def _exchanged(self, runners):
+        """Segment runners [(callable, (lo, hi, mat_hi))] as stages: each slice's exchange goes out eagerly, asynchronously, right behind
+        the callable (or graph) that finished it, and the step waits for them after the last."""
+        sh, gs = self.sharded, self.grad_sync
+        if sh is None:
+            works = []
+            reduce = lambda lo, hi: lambda: works.append(gs.reduce_range(lo, hi))
+            return ([_Stage(after=works.clear)] + [_Stage(run, reduce(lo, hi)) for run, (lo, hi, _) in runners]
+                    + [_Stage(after=lambda: gs.wait(works))])
+
+        def begin():
+            if sh._pending is not None or sh._works:
+                sh.abort()                              # left over from a step that raised between reduce_update() and finish()
             self.opt.begin_sharded_step()
-            try:
-                for run, (lo, hi, mat_hi) in runners:
-                    run()
-                    self.sharded.reduce_update(lo, hi, mat_hi)
-            except BaseException:
-                self.sharded.abort()                    # never let this step's deferred shard update run against the next step's gradients
-                if self.model._queue is not None:
-                    self.model._queue.reset()
-                raise
-            if self.sharded.timeline is not None and torch.cuda.is_available():
+
+        def finish():
+            if sh.timeline is not None and torch.cuda.is_available():
                 e = torch.cuda.Event(enable_timing=True)
                 e.record()                              # the compute chain (every segment graph) ends here; what follows is exposed exchange
-                self.sharded.timeline.append({"chain_end": e})
-            self.sharded.finish()
-            return
-        works = []
-        for run, (lo, hi, _) in runners:
-            run()
-            works.append(self.grad_sync.reduce_range(lo, hi))
-        self.grad_sync.wait(works)
+                sh.timeline.append({"chain_end": e})
+            sh.finish()
+
+        return [_Stage(after=begin)] + [_Stage(run, lambda rng=rng: sh.reduce_update(*rng)) for run, rng in runners] + [_Stage(after=finish)]
+
+    def _run_segmented(self, runners):
+        """The layer-segmented forward / backward with its exchanges (no optimiser): ``runners`` = _segments(), or their graphs' replays."""
+        self._run(self._exchanged(runners))
+
+    def _stages(self):
+        """The step as a list of _Stage in launch order, from (accumulating, overlap, sharded, grad_sync, _fused()).  Eager steps run it
+        as it is; a captured step is the same list with every unit replaced by its graph's replay (_capture_schedule)."""
+        update = self._refresh_after_exchange if self.sharded is not None else self._optim    # (sharded: the updates ran shard by shard)
+        if self.accumulating:            # the accumulate launch (and, closing the window, the exchange) sit between the two graphs
+            adam, sync = self.opt.optimizer, self.grad_sync
+            return ([_Stage(self._unit_fwd_bwd, lambda: adam.accumulate(self._norms[0], self._closing, sumsq=sync is None))]
+                    + ([_Stage(after=sync, closing=True)] if sync is not None else []) + [_Stage(self._optim, closing=True)])
+        if self.overlap:
+            return self._exchanged(self._segments()) + [_Stage(update)]
+        if self.grad_sync is None:
+            return [_Stage(self._unit_step)]
+        return [_Stage(self._unit_fwd_bwd, self._whole_buffer_sharded if self.sharded is not None else self.grad_sync), _Stage(update)]
+
+    def _unit_fwd_bwd(self):
+        self._loss = self._fwd_bwd()
+
+    def _unit_step(self):
+        """One rank: the whole step is one unit."""
+        if self._fused():
+            self._loss = self._step_fused()
+        else:
+            self._loss = self._fwd_bwd()
+            self._optim()
+
+    def _run(self, stages):
+        try:
+            for st in stages:
+                if st.closing and not self._closing:
+                    break
+                if st.unit is not None:
+                    st.unit()
+                if st.after is not None:
+                    st.after()
+        except BaseException:
+            self._drop_step()
+            raise
 
     def _capture(self):
         """Warm-up and capture.  The warm-up passes launch scheduled sampling's mix like any step: its counters are put back after."""
@@ -812,7 +881,14 @@ class TrainStep:
         if self.overlap:
             err = None
             try:
-                self._capture_segmented(side)
+                stages = self._stages()
+                with torch.cuda.stream(side):
+                    for st in stages[:-1]:          # warm-up of the segmented schedule (no exchange: gradients are discarded)
+                        if st.unit is not None:
+                            st.unit()
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                self._capture_stages(stages)
             except Exception as e:      # never lose the run to the more elaborate schedule: fall back to the simple one
                 err = e
             # the decision is COLLECTIVE: a rank that fell back alone would issue a different sequence of collectives
@@ -823,56 +899,31 @@ class TrainStep:
             import logging
             logging.getLogger("mtn_amd").warning("layer-segmented capture failed on %d rank(s) (%s); using the two-graph schedule",
                                                  int(failed.item()), err)
-            self.overlap, self._g_seg, self._st = False, None, None
+            self.overlap, self._g_seg, self._st, self._replays = False, None, None, None
             torch.cuda.synchronize()
-        self._capture_simple()
-
-    def _capture_segmented(self, side):
-        segs = self._segments()
-        with torch.cuda.stream(side):
-            for fn, _ in segs:                      # warm-up of the segmented schedule (no exchange: gradients are discarded)
-                fn()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self._g_seg, pool = [], None
-        for fn, rng in segs:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=CAPTURE_MODE):
-                fn()
-            pool = g.pool()
-            self._g_seg.append((g.replay, rng))
-        self._loss = self._loss_t
-        self._g_opt = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._g_opt, pool=pool, capture_error_mode=CAPTURE_MODE):
-            if self.sharded is not None:
-                self._refresh_after_exchange()          # the updates ran shard by shard between the segment graphs
-            else:
-                self._optim()
-        self._g_fb = self._g_seg[0]
-
-    def _capture_simple(self):
-        self._g_fb = torch.cuda.CUDAGraph()
-        if self.accumulating:                     # the accumulate launch (and the exchange) sit between the two replays
-            with torch.cuda.graph(self._g_fb, capture_error_mode=CAPTURE_MODE):
-                self._loss = self._fwd_bwd()
-            self._g_opt = self._capture_optim(False)
-        elif self.grad_sync is None:
-            with torch.cuda.graph(self._g_fb, capture_error_mode=CAPTURE_MODE):
-                if self._fused():
-                    self._loss = self._step_fused()
-                else:
-                    self._loss = self._fwd_bwd()
-                    self._optim()
-        else:
-            with torch.cuda.graph(self._g_fb, capture_error_mode=CAPTURE_MODE):
-                self._loss = self._fwd_bwd()
-            self._g_opt = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g_opt, pool=self._g_fb.pool(), capture_error_mode=CAPTURE_MODE):
-                if self.sharded is not None:
-                    self._refresh_after_exchange()
-                else:
-                    self._optim()
+        if self.accumulating:
+            self.opt.optimizer._accum_sumsq = False       # (read by FusedAdam._clip inside the capture: this graph holds the norm launch)
+        self._capture_stages(self._stages())
+        if self.accumulating:                             # the optimiser stage picks between two graphs: see _replay_optim
+            self._replays[-1] = self._replays[-1]._replace(unit=self._replay_optim)
         # the warm-up/capture passes did not run the optimiser outside capture: parameters are untouched
+
+    def _capture_stages(self, stages):
+        """One graph per unit, in order, all in the first one's memory pool; ``_replays`` = the stages with the replays for units."""
+        graphs, replays, pool = [], [], None
+        for st in stages:
+            if st.unit is not None:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, pool=pool, capture_error_mode=CAPTURE_MODE):
+                    st.unit()
+                pool = g.pool()
+                graphs.append(g)
+                st = st._replace(unit=g.replay)
+            replays.append(st)
+        self._g_fb, self._g_opt = graphs[0], graphs[-1] if len(graphs) > 1 else None
+        if self.overlap:                # [(replay, slice)] of the segment graphs, as _run_segmented takes them
+            self._g_seg = [(g.replay, rng) for g, rng in zip(graphs[:-1], self._slices())]
+        self._replays = replays
 
     def _capture_optim(self, have_sumsq: bool):
         """The optimiser graph of the accumulating step.  ``have_sumsq``: clipping reads the partials the closing mtn_grad_accum launch
@@ -883,69 +934,25 @@ class TrainStep:
             self._optim()
         return g
 
-    def _micro_step(self, last: bool) -> torch.Tensor:
-        """__call__ under accumulation: forward + backward, the accumulate launch, and on the window's last micro-step the exchange and
-        the optimiser.  Nothing synchronises with the host."""
-        adam = self.opt.optimizer
-        if self.use_graph:
-            if self._g_fb is None:
-                self._capture()
-            self._g_fb.replay()
-            loss = self._loss
-        else:
-            loss = self._fwd_bwd()
-        adam.accumulate(self._norms[0], last, sumsq=self.grad_sync is None)
-        if not last:
-            return loss
-        if self.grad_sync is not None:
-            self.grad_sync()
-        if not self.use_graph:
-            self._optim()
-        elif adam._accum_sumsq:
-            if self._g_opt_sumsq is None:
-                self._g_opt_sumsq = self._capture_optim(True)
-            self._g_opt_sumsq.replay()
-        else:
+    def _replay_optim(self):
+        """The accumulating step's optimiser graph: the one without the norm launch when the closing accumulate launch wrote its partials
+        (captured the first time that happens)."""
+        if not self.opt.optimizer._accum_sumsq:
             self._g_opt.replay()
-        return loss
+            return
+        if self._g_opt_sumsq is None:
+            self._g_opt_sumsq = self._capture_optim(True)
+        self._g_opt_sumsq.replay()
 
     def __call__(self, last: bool = True) -> torch.Tensor:
         """Runs one step; returns the device tensor of the NORMALISED loss (main KL / global target tokens + lambda * sum of the
         auto-encoder KLs / global query tokens: the `loss` of data_utils.py:135-144, before the `* norm` of :156), without
-        synchronising.  ``last`` matters under accumulation only (``accumulate``): the call is one micro-step, and ``last`` closes the
-        window."""
-        if self.accumulating:
-            return self._micro_step(bool(last))
-        if not self.use_graph:
-            if self.overlap:
-                self._run_segmented(self._segments())
-                loss = self._loss_t
-            elif self._fused():
-                return self._step_fused()
-            else:
-                loss = self._fwd_bwd()
-                if self.sharded is not None:
-                    self._whole_buffer_sharded()
-                elif self.grad_sync is not None:
-                    self.grad_sync()
-            if self.sharded is not None:
-                self._refresh_after_exchange()
-            else:
-                self._optim()
-            return loss
-        if self._g_fb is None:
+        synchronising.  ``last`` matters under accumulation only (``accumulate``): the call is one micro-step — forward + backward, the
+        accumulate launch — and ``last`` closes the window: the exchange and the optimiser follow."""
+        self._closing = bool(last) or not self.accumulating
+        if self.use_graph and self._replays is None:
             self._capture()
-        if self.overlap:
-            self._run_segmented(self._g_seg)
-            self._g_opt.replay()
-            return self._loss
-        self._g_fb.replay()
-        if self.sharded is not None:
-            self._whole_buffer_sharded()
-            self._g_opt.replay()
-        elif self.grad_sync is not None:
-            self.grad_sync()
-            self._g_opt.replay()
+        self._run(self._replays if self.use_graph else self._stages())
         return self._loss
 
     def _refresh_after_exchange(self):
@@ -962,6 +969,10 @@ class TrainStep:
         m.prepare()
         sl = m._layer_slices
         total, N = m._flat_grad.numel(), len(sl)
+        # a layer's slice is its weight matrices (mtn.py _ordered_params): mat_hi = hi -> they travel in the compute dtype; the last
+        # slice = glue parameters + every vector (biases, all LayerNorms): fp32 throughout, complete once the last segment has run
+        assert all(sl[k][1] == sl[k + 1][0] for k in range(N - 1)), "layer slices not contiguous"
+        assert sl[N - 1][1] == total, "the last layer's matrices end the flat buffer"
         return [(sl[N - 1][0], total, total)] + [sl[k] + (sl[k][1],) for k in range(N - 2, -1, -1)] + [(0, sl[0][0], None)]
 
     def _whole_buffer_sharded(self):
@@ -992,38 +1003,22 @@ class BucketedTrainer:
         ``accum_steps``: K > 1 = gradient accumulation (TrainStep's ``accumulate``): step() is one micro-step and every K-th one, or
         one called with ``last=True``, closes the window and updates.  The accumulator belongs to the shared optimiser, so the
         micro-steps of one window may fall into different padded shapes.  ``micro_steps`` / ``updates``: counted on the host.
-        1 = off: today's step, launch for launch.  Not together with scst.
+        1 = off: today's step, launch for launch.
         ``sched``: scheduled sampling (TrainStep's ``sched``) for every shape: the rows' hash keys are the batch's QA ids, refilled
         before every step, and ``sched_stats`` is the one (3,) int64 device counter block all shapes add to (zero it to start a count).
-        ``use_graph`` = False runs these steps eagerly.  Not together with a teacher or scst.
+        ``use_graph`` = False runs these steps eagerly.
         ``rdrop``: TrainStep's R-Drop alpha for every shape: each padded shape's static Batch is the source its step doubles inside the
-        (captured) step; ``last_rd``: the last step's device scalar (None at 0).  Not together with a teacher, scst, unlikelihood or
-        sched."""
-        self.rdrop, self.last_rd = float(rdrop), None
-        if not (self.rdrop >= 0.0 and math.isfinite(self.rdrop)):
-            raise ValueError("BucketedTrainer: rdrop is finite and >= 0")
-        if self.rdrop > 0.0:
-            for on, what in ((teacher is not None, "a teacher (distillation)"), (scst is not None, "scst"),
-                             (float(unlikelihood) > 0.0, "unlikelihood"), (sched is not None, "sched (scheduled sampling)")):
-                if on:
-                    raise ValueError("BucketedTrainer: rdrop does not combine with %s" % what)
-        if sched is not None and (teacher is not None or scst is not None):
-            raise ValueError("BucketedTrainer: sched (scheduled sampling) does not combine with %s" % ("a teacher (distillation)" if teacher is not None
-                                                                                                        else "scst"))
-        self.sched, self.sched_stats = sched, None
+        (captured) step; ``last_rd``: the last step's device scalar (None at 0).
+        What combines with what: check_objectives."""
         if int(accum_steps) != accum_steps or int(accum_steps) < 1:
             raise ValueError("BucketedTrainer: accum_steps is an integer >= 1")
+        check_objectives("BucketedTrainer", teacher=teacher, distill_alpha=distill_alpha, distill_temperature=distill_temperature, scst=scst,
+                         unlikelihood=unlikelihood, rdrop=rdrop, sched=sched, clip_grad_norm=clip_grad_norm, grad_sync=grad_sync,
+                         clipping=bool(clip_grad_norm), accumulating=int(accum_steps) > 1)
+        self.rdrop, self.last_rd = float(rdrop), None
+        self.sched, self.sched_stats = sched, None
         self.accum_steps, self.micro_steps, self.updates, self._in_window = int(accum_steps), 0, 0, 0
-        if self.accum_steps > 1 and scst is not None:
-            raise ValueError("BucketedTrainer: scst does not combine with gradient accumulation (accum_steps > 1): rl_step is one update per call")
         self.unlikelihood, self.last_ul = float(unlikelihood), None
-        if not (self.unlikelihood >= 0.0 and math.isfinite(self.unlikelihood)):
-            raise ValueError("BucketedTrainer: unlikelihood is finite and >= 0")
-        if self.unlikelihood > 0.0 and (teacher is not None or scst is not None):
-            raise ValueError("BucketedTrainer: unlikelihood does not combine with %s" % ("a teacher (distillation)" if teacher is not None
-                                                                                         else "scst"))
-        if scst is not None and (teacher is not None or grad_sync is not None):
-            raise ValueError("BucketedTrainer: scst does not combine with a teacher (distillation) or with data parallelism")
         self.scst, self.use_graph, self.rl_steps = scst, use_graph, 0
         self.last_reward = self.last_baseline = None
         self.model, self.corpus, self.vocab, self.pad, self.lam = model, corpus, vocab_size, pad, lam
@@ -1035,9 +1030,6 @@ class BucketedTrainer:
         if clip_grad_norm:
             self.opt.optimizer.enable_clip(clip_grad_norm)
         if self.accum_steps > 1:
-            if grad_sync is not None and os.environ.get("MTN_DP_SHARDED", "0") != "0":
-                raise ValueError("BucketedTrainer: gradient accumulation does not combine with the sharded data-parallel optimiser "
-                                 "(MTN_DP_SHARDED): leave MTN_DP_SHARDED unset or 0")
             self.opt.optimizer.enable_accumulation()
         self.steps = {}
         self.last_kd = None

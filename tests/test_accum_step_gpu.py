@@ -24,7 +24,8 @@ from oracle import fixtures as fx
 from tests import accum_refs as R
 from tests import average_refs as AR
 from tests import clip_refs as CR
-from tests.test_distill_step_gpu import _config, _student, deterministic_embed, dev  # noqa: F401  (fixtures)
+from tests.step_helpers import _student, deterministic_embed  # noqa: F401  (fixture)
+from tests.test_distill_step_gpu import _config, dev  # noqa: F401  (fixture)
 from tests.test_model_gpu import dev_batch, raw_batch
 
 pytestmark = pytest.mark.gpu

@@ -7,7 +7,6 @@ tests/test_model_gpu.py, with its helpers and its bars:
   (c) a two-member Ensemble teacher with weights 2:1, both modes, held as (b);
   (d) eager and captured steps give the same loss bits;
   (e) the layer-segmented schedule (one-rank gloo group, child process) gives the monolithic step's first loss within 1e-5 relative."""
-import ctypes as C
 import os
 import socket
 import sys
@@ -18,6 +17,7 @@ import torch.nn.functional as F
 
 from oracle import fixtures as fx
 from oracle.mtn_oracle import label_smoothing_kl
+from tests.step_helpers import _census, _student, deterministic_embed  # noqa: F401  (fixture)
 from tests.test_model_gpu import build_model, dev_batch, raw_batch
 from tests.util import DTYPES, TOL, relmax
 
@@ -42,47 +42,8 @@ def dev():
     return torch.device("cuda:0")
 
 
-@pytest.fixture
-def deterministic_embed(monkeypatch):
-    """The atomic-free embedding-table gradient: the whole step is bitwise reproducible (tests/test_model_gpu.py)."""
-    from mtn_amd import lib
-    monkeypatch.setenv("MTN_EMBED_DETERMINISTIC", "1")
-    lib.reload_env()
-    yield
-    monkeypatch.delenv("MTN_EMBED_DETERMINISTIC")
-    lib.reload_env()
-
-
-def _student(c, dtype, dev, dropout):
-    model = build_model(c, dtype, dev, dropout=dropout, attn_dropout=dropout).train()
-    for mod in model.modules():                 # the feature streams' dropout is PyTorch's (its own RNG): keep it out
-        if isinstance(mod, torch.nn.Dropout):
-            mod.p = 0.0
-    model.prepare()
-    if model._seed is not None:
-        model._seed.fill_(4242)
-    return model
-
-
 def _teacher(c, dtype, dev, seed):
     return build_model(c, dtype, dev, seed=seed).eval()
-
-
-def _census(fn):
-    """[(kernel variant, workgroups, problems, first problem's M x N x K)] of every GEMM launch of fn(), and the fused-group counters."""
-    from mtn_amd import lib as L
-    lib = L.load()
-    f0 = L.fused_counters()
-    lib.mtn_census_begin()
-    fn()
-    torch.cuda.synchronize()
-    n = lib.mtn_census_end()
-    rows = []
-    for i in range(n):
-        info = L.CensusLaunch()
-        L.check(lib.mtn_census_info(i, C.byref(info)))
-        rows.append((lib.mtn_census_variant_name(info.variant).decode(), info.workgroups, info.count, (info.M[0], info.N[0], info.K[0])))
-    return rows, tuple(a - b for a, b in zip(L.fused_counters(), f0))
 
 
 # ------------------------------------------------------------------------------------------ (a)

@@ -16,7 +16,8 @@ import torch
 
 from oracle import fixtures as fx
 from tests import average_refs as R
-from tests.test_distill_step_gpu import _config, _free_port, _student, deterministic_embed, dev  # noqa: F401  (fixtures)
+from tests.step_helpers import _student, deterministic_embed  # noqa: F401  (fixture)
+from tests.test_distill_step_gpu import _config, _free_port, dev  # noqa: F401  (fixture)
 from tests.test_model_gpu import build_model, dev_batch, raw_batch
 from tests.util import DTYPES
 

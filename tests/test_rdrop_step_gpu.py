@@ -21,7 +21,8 @@ import torch
 
 from oracle import fixtures as fx
 from tests import rdrop_refs as rd
-from tests.test_distill_step_gpu import NAMES, _census, _config, _student, _teacher
+from tests.step_helpers import _census, _student, deterministic_embed  # noqa: F401  (fixture)
+from tests.test_distill_step_gpu import NAMES, _config, _teacher
 from tests.test_model_gpu import dev_batch, raw_batch
 from tests.util import TOL, relmax
 
@@ -34,17 +35,6 @@ SEED = 4242
 def dev():
     assert torch.cuda.is_available(), "GPU tests need a MI355X"
     return torch.device("cuda:0")
-
-
-@pytest.fixture
-def deterministic_embed(monkeypatch):
-    """The atomic-free embedding-table gradient: the whole step is bitwise reproducible (tests/test_model_gpu.py)."""
-    from mtn_amd import lib
-    monkeypatch.setenv("MTN_EMBED_DETERMINISTIC", "1")
-    lib.reload_env()
-    yield
-    monkeypatch.delenv("MTN_EMBED_DETERMINISTIC")
-    lib.reload_env()
 
 
 def _doubled(raw):
@@ -321,7 +311,7 @@ def test_conflicts_raise_and_name_what_conflicts(dev):
         ts.lc._fused_loss(out, ts.batch.trg_y, ts._norms[0], None, None, None, row_weights=torch.ones(rows, device=dev), rdrop=1.0)
     with pytest.raises(ValueError, match="R-Drop does not combine with unlikelihood"):
         ts.lc._fused_loss(out, ts.batch.trg_y, ts._norms[0], None, None, None, unlikelihood=1.0, rdrop=1.0)
-    assert hasattr(ops, "_rdrop")
+    assert "rdrop" in ops.LOSS_HEADS
 
 
 # ------------------------------------------------------------------------------------------ (g)

@@ -18,7 +18,8 @@ import torch
 
 from oracle import fixtures as fx
 from tests import sched_refs as R
-from tests.test_distill_step_gpu import _census, _config, _free_port, _student, deterministic_embed, dev  # noqa: F401  (fixtures)
+from tests.step_helpers import _census, _student, deterministic_embed  # noqa: F401  (fixture)
+from tests.test_distill_step_gpu import _config, _free_port, dev  # noqa: F401  (fixture)
 from tests.test_model_gpu import dev_batch, raw_batch
 
 pytestmark = pytest.mark.gpu

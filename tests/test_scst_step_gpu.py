@@ -7,7 +7,6 @@ of tests/test_model_gpu.py, with its helpers and its bars:
   (c) eager and captured steps give the same loss bits, two runs from one seed the same weights — with fixed rows and with drawn ones;
   (d) the weighted step's launch census is the plain step's on the replicated batch (a step without scst runs no new code);
   (e) rl_step draws, scores and trains: finite rewards, the gold rows ride along, the greedy baseline is one value per dialogue."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -15,7 +14,8 @@ import torch
 
 from oracle import fixtures as fx
 from oracle.mtn_oracle import label_smoothing_kl
-from tests.test_model_gpu import build_model, dev_batch, raw_batch
+from tests.step_helpers import _census, _student, deterministic_embed  # noqa: F401  (fixture)
+from tests.test_model_gpu import dev_batch, raw_batch
 from tests.util import DTYPES, TOL, relmax
 
 pytestmark = pytest.mark.gpu
@@ -37,27 +37,6 @@ def dev():
     return torch.device("cuda:0")
 
 
-@pytest.fixture
-def deterministic_embed(monkeypatch):
-    from mtn_amd import lib
-    monkeypatch.setenv("MTN_EMBED_DETERMINISTIC", "1")
-    lib.reload_env()
-    yield
-    monkeypatch.delenv("MTN_EMBED_DETERMINISTIC")
-    lib.reload_env()
-
-
-def _student(c, dtype, dev, dropout):
-    model = build_model(c, dtype, dev, dropout=dropout, attn_dropout=dropout).train()
-    for mod in model.modules():
-        if isinstance(mod, torch.nn.Dropout):
-            mod.p = 0.0
-    model.prepare()
-    if model._seed is not None:
-        model._seed.fill_(4242)
-    return model
-
-
 def _replicated(raw, times):
     """The raw batch with every dialogue ``times`` times in a row (row d * times + s), as the step's static batch holds it."""
     out = dict(raw)
@@ -70,22 +49,6 @@ def _replicated(raw, times):
 def _cfg(c, **kw):
     from mtn_amd.train_step import ScstConfig
     return ScstConfig(samples=S, max_length=c["T"], sos=SOS, eos=EOS, **kw)
-
-
-def _census(fn):
-    from mtn_amd import lib as L
-    lib = L.load()
-    f0 = L.fused_counters()
-    lib.mtn_census_begin()
-    fn()
-    torch.cuda.synchronize()
-    n = lib.mtn_census_end()
-    rows = []
-    for i in range(n):
-        info = L.CensusLaunch()
-        L.check(lib.mtn_census_info(i, C.byref(info)))
-        rows.append((lib.mtn_census_variant_name(info.variant).decode(), info.workgroups, info.count, (info.M[0], info.N[0], info.K[0])))
-    return rows, tuple(a - b for a, b in zip(L.fused_counters(), f0))
 
 
 # ------------------------------------------------------------------------------------------ (a)
