@@ -958,6 +958,54 @@ typedef struct {
     long* tokens; int* pos; int* anc;             /* as mtn_decode_args, or NULL */
 } mtn_sample_args;
 int mtn_sample_rows(const mtn_sample_args* args /* host */, void* stream);
+/* Contrastive search (csrc/contrastive.hip; detected by symbol, mtn_version() stays 125; Su et al. 2022, "A Contrastive Framework for
+ * Neural Text Generation"; not in the reference): among the k most probable next tokens, take the one whose decoder state is least similar
+ * to the states of the prefix.  This call is the selection and bookkeeping of ONE generated token; it reads the output of the decoder's
+ * final norm, which no other entry point looks at.
+ * A dialogue owns k consecutive session rows (rows dialogue * k ..).  At position l = step[dialogue] >= 1 every row r holds the common
+ * prefix <sos>, y_1 .. y_{l-1} at positions 0 .. l-1 of tokens and its own candidate token v_r at position l; v_r was the r-th admitted
+ * entry of the previous step's head and cand_logp[r] is that entry's log-probability.  With h[r][j] = hidden[row r][position j][0..d):
+ *   pen_r = max over 0 <= j < l of  dot(h[r][l], h[r][j]) / ( sqrt(|h[r][l]|^2) * sqrt(|h[r][j]|^2) )     (0 when either norm is 0)
+ *   s_r   = fl32( fl32((1 - alpha) * expf(cand_logp[r])) - fl32(alpha * pen_r) )        (two multiplies and a subtract, never an fma)
+ *   r*    = the row of largest s_r, ties to the lowest row
+ * A row whose s_r is NaN (a NaN cosine makes pen_r NaN), or whose cand_logp is -inf, never wins; if no row can win, r* is row 0.
+ * Everything is fp32, and the order of every sum is a pure function of d (the same on the 16-byte and the scalar path), so two launches
+ * give the same bytes.  y_l = v_{r*}; the step logs, at [l][dialogue] of the [L][dialogues] logs, y_l, cand_logp[r*] (the model's own
+ * log-probability, with the bits of the head entry), pen_{r*} and r*.  Then:
+ *   - y_l is stored at position l of all k rows; y_l == eos sets done[dialogue];
+ *   - otherwise, while l + 1 < L, the candidates for position l + 1 are the first k ADMITTED entries of row r*'s head, in the head's
+ *     order.  The head is what mtn_topk_rows leaves in top for the next-token row of row r*: k_top values, k_top columns (as floats), one
+ *     more word.  An entry is not admitted if its id is one of banned[0..n_banned), or if it is eos while l < min_len.  Row r gets the r-th
+ *     admitted entry's column at position l + 1 and its value as cand_logp[r]; with fewer than k admitted entries the remaining rows
+ *     repeat the last admitted column with cand_logp = -inf (k_top >= min(16, k + n_banned + 1) admits at least one; were none admitted,
+ *     they would repeat the head's first column);
+ *   - step[dialogue] = l + 1, and workgroup 0 stores *pos = min(max(l + 1, 0), L - 1), what the next decoder pass reads.
+ * l == 0 is the bootstrap: nothing is scored or logged, r* is the dialogue's first row, and candidates for position 1 are dealt from its
+ * head.  A dialogue that is done, or whose step is outside [0, L), only advances its step.
+ * The response is y_1 .. up to eos, at most L - 1 tokens without one.  alpha = 0 is greedy (the head is sorted: row 0 wins), and so is
+ * k = 1 for every alpha.
+ * One launch, one workgroup per dialogue, which reads and writes only its own dialogue's words; no atomics, nothing allocated, no host
+ * read: capturable.  16-byte loads where d and both strides are multiples of 4 and hidden is 16-byte aligned, scalar loads otherwise.
+ * MTN_ERR_ARG, nothing launched: a null pointer; hidden, top, cand_logp, step, done or a log not 4-byte aligned, tokens or pos not 8-byte
+ * aligned; k outside 1..16, k_top outside min(16, k + n_banned + 1)..16, d outside 1..1024, L outside 1..2^20, n_banned outside 0..4;
+ * alpha outside [0, 1] or not finite; pos_stride < d or row_stride < (L - 1) * pos_stride + d (the dense strides, d and L * d, at
+ * least); dialogues < 0 or dialogues * k overflowing int.  dialogues == 0 returns MTN_OK with nothing launched. */
+typedef struct {
+    int dialogues, k, L, d, k_top;
+    float alpha;
+    int eos, min_len;
+    int n_banned; int banned[4];
+    const float* hidden;        /* device: [dialogues * k][L][d] through the strides below */
+    long row_stride, pos_stride;    /* in elements */
+    const float* top;           /* device: [dialogues * k][2 * k_top + 1], as mtn_topk_rows leaves it */
+    long* tokens;               /* device: [dialogues * k][L] */
+    long* pos;                  /* device: 1 */
+    float* cand_logp;           /* device: [dialogues * k] */
+    int* step;                  /* device: [dialogues] */
+    int* done;                  /* device: [dialogues] */
+    int* log_tok; float* log_logp; float* log_pen; int* log_rank;   /* device: [L][dialogues] */
+} mtn_contrastive_args;
+int mtn_contrastive_advance(const mtn_contrastive_args* args /* host */, void* stream);
 /* Candidate scoring (version 116): how likely the model finds GIVEN tokens.  logits [n_seq * L, ldz] (fp32, row stride ldz >= V; columns
  * V..ldz-1 are never read; 2 <= V < 2^24) are the generator's rows of a teacher-forced pass, target [n_seq, L] the token each position
  * should produce.  One launch, no atomics; per position (s, l), with z its row and t = target[s][l]:

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libmtn_hip.so")
-SOURCES = ["gemm.hip", "layernorm.hip", "attention.hip", "fused.hip", "fused_bwd.hip", "elementwise.hip", "sublayer.hip", "losshead.hip", "assemble.hip", "select.hip", "diverse.hip", "sample.hip", "score.hip", "constrain.hip", "ensemble.hip", "mbr.hip", "eval.hip", "scst.hip", "average.hip", "gradnorm.hip", "gradaccum.hip", "sched.hip", "gemm_k512.hip", "decode.hip"]
+SOURCES = ["gemm.hip", "layernorm.hip", "attention.hip", "fused.hip", "fused_bwd.hip", "elementwise.hip", "sublayer.hip", "losshead.hip", "assemble.hip", "select.hip", "diverse.hip", "contrastive.hip", "sample.hip", "score.hip", "constrain.hip", "ensemble.hip", "mbr.hip", "eval.hip", "scst.hip", "average.hip", "gradnorm.hip", "gradaccum.hip", "sched.hip", "gemm_k512.hip", "decode.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # The fused attention kernels wait with COUNTED s_waitcnt vmcnt(N) (N = the loads the compiler emits behind the LDS-DMA today).  The same
 # library with full waits instead is the reference tests/test_counted_waits_gpu.py compares the shipped one with, bit for bit.

@@ -48,7 +48,7 @@ def _capture(body):
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
+    with L.capturing(g):
         body()
     return g
 
@@ -81,6 +81,9 @@ class DecodeSession:
         self._static = None                   # load(): a private copy of the dialogue's inputs that a captured encoder-side pass reads
         self._load_graph = None
         self._loads = 0
+        # contrastive_log: the search's settings (frozen into its captured body), its device state [cand_logp | step | done | logs], the
+        # views of it and the captured body; a search with other settings replaces all four
+        self._cs_key = self._cs_state = self._cs_views = self._cs_graph = None
         self.load(batch)
         if self.kv_cache:
             # Prefix K/V cache of the target self-attention (the reference recomputes the whole prefix for every hypothesis and
@@ -131,7 +134,7 @@ class DecodeSession:
             try:
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with L.capturing(g):
                     self._load_body(self._static)
                 self._load_graph = g
             except Exception as e:                          # never lose a decode to the faster path
@@ -380,6 +383,64 @@ class DecodeSession:
                     self._score_graph = _capture(self._pass_score)
                 self._score_graph.replay()
         return tuple(t.cpu().numpy() for t in self._score_out)
+
+    def contrastive_log(self, start, k, alpha, eos, min_len, banned=(), trace=None):
+        """A whole contrastive search (Su et al. 2022; include/mtn_hip.h mtn_contrastive_advance holds the definition) for every dialogue
+        of the session, whose ``width`` = k rows are the dialogue's candidates.  The body of one token is the full-prefix pass up to the
+        decoder's final norm — the (rows, max_len, d) states the degeneration penalty is taken from —, the generator on position ``pos``,
+        the rows' heads (ops.topk_rows) and mtn_contrastive_advance (csrc/contrastive.hip), which scores the candidates, logs the choice
+        and writes ``tokens`` / ``pos`` for the next pass in place.  The body is captured once per session and replayed max_len times
+        (use_graph=False: run eagerly); no token is read on the host, the log is copied out once at the end.  The state is reset by device
+        fills, so the session serves further searches after ``load``.
+        Returns the numpy logs (tokens int32, log-probabilities fp32, penalties fp32, ranks int32), each (max_len, D); row 0 is the
+        bootstrap and holds nothing.  ``trace`` (eager runs only): a list that receives, per step, a dict of host copies of what the kernel
+        read — hidden, top, tokens, cand_logp, step, done."""
+        k, banned = int(k), tuple(int(b) for b in banned)
+        if self.kv_cache or isinstance(self.model, Ensemble) or isinstance(self, MegaDecodeSession):
+            raise ValueError("contrastive_log: the search runs on the full-prefix launch-per-sublayer pass of one model")
+        if k != self.width or not 1 <= k <= ops.CONTRASTIVE_MAX_K or len(banned) > 4:
+            raise ValueError("contrastive_log: k is the session's width, 1..16; at most 4 banned tokens")
+        if trace is not None and self.use_graph:
+            raise ValueError("contrastive_log: the per-step trace needs an eager session (use_graph=False)")
+        D, Lm, dev = self.D, self.max_len, self.tokens.device
+        k_top = min(SELECT_MAX_K, k + len(banned) + 1)
+        key = (k, float(alpha), int(eos), int(min_len), banned)
+        if self._cs_key != key:               # (first search, or other settings: kernel arguments are frozen into the captured body)
+            # [cand_logp (rows) | step (D) | done (D) | the four logs (4 x L x D)]: one block of 32-bit words, one fill per search
+            W = D * k
+            self._cs_state = torch.zeros(W + 2 * D + 4 * Lm * D, device=dev, dtype=torch.int32)
+            o = W + 2 * D
+            logs = self._cs_state[o:].view(4, Lm, D)
+            self._cs_views = (self._cs_state[:W].view(torch.float32), self._cs_state[W:W + D], self._cs_state[W + D:o],
+                              (logs[0], logs[1].view(torch.float32), logs[2].view(torch.float32), logs[3]))
+            self._cs_graph, self._cs_key = None, key
+        cand, step, done, log = self._cs_views
+        kw = dict(k=k, alpha=float(alpha), eos=int(eos), min_len=int(min_len), banned=banned)
+
+        def body():
+            hidden = self._decoder_rows()
+            if hidden.dtype != torch.float32:
+                hidden = hidden.float()
+            top = ops.topk_rows(self._generate(hidden.index_select(1, self.pos).squeeze(1)), k_top, -1)
+            if trace is not None:
+                snap = lambda t: t.detach().cpu().numpy().copy()
+                trace.append(dict(hidden=snap(hidden), top=snap(top), tokens=snap(self.tokens), cand_logp=snap(cand), step=snap(step), done=snap(done)))
+            ops.contrastive_advance(hidden, top, self.tokens, self.pos, cand, step, done, log, **kw)
+
+        with torch.no_grad():
+            if self.use_graph and self._cs_graph is None:
+                self._cs_graph = _capture(body)          # (runs the body twice on whatever the state holds: the reset comes after it)
+            self.tokens.fill_(self.pad)
+            self.tokens[:, 0].fill_(int(start))
+            self.pos.zero_()
+            self._cs_state.zero_()
+            for _ in range(Lm):
+                if self.use_graph:
+                    self._cs_graph.replay()
+                else:
+                    body()
+        host = self._cs_state[D * k + 2 * D:].view(4, Lm, D).cpu().numpy()         # the one synchronisation of the search
+        return host[0].copy(), host[1].view(np.float32).copy(), host[2].view(np.float32).copy(), host[3].copy()
 
 
 class MegaDecodeSession(DecodeSession):
@@ -1417,6 +1478,51 @@ def _sample_search(model, batch, max_len, start, pad, S, seed, row_keys, params,
     if on_device:
         return log
     return tuple(t.cpu().numpy() for t in log)
+
+
+def _contrastive(k, alpha, banned=()):
+    """(k, alpha, banned ids) of a contrastive search's keywords, checked."""
+    kk, a = int(k), float(alpha)
+    if kk != k or not 1 <= kk <= ops.CONTRASTIVE_MAX_K:
+        raise ValueError("contrastive search: k is an integer in 1..%d" % ops.CONTRASTIVE_MAX_K)
+    if not 0.0 <= a <= 1.0:                      # (a NaN fails both comparisons)
+        raise ValueError("contrastive search: alpha is in [0, 1]")
+    banned = tuple(int(b) for b in banned)
+    if len(banned) > 4:
+        raise ValueError("contrastive search: at most 4 banned tokens")
+    return kk, a, banned
+
+
+def contrastive_decode_many(model, batch, max_len, start, eos, pad, *, k=5, alpha=0.6, banned=(), min_len=1, penalty=0.0, use_graph=True,
+                            trace=None):
+    """Contrastive search (Su et al. 2022) for a Batch of D dialogues: at every position the next token is, among the ``k`` most probable
+    ones, the one that maximises (1 - alpha) * p(token) - alpha * max cosine between the decoder's final-norm state of that token and the
+    states of the prefix (include/mtn_hip.h mtn_contrastive_advance holds the definition).  Deterministic; alpha = 0 or k = 1 is greedy.
+    <eos> is no candidate before ``min_len`` tokens, ``banned`` ids never; a response ends at its <eos>, or at max_len - 1 tokens.
+    Dialogue d's k candidates are rows d * k .. of ONE full-prefix launch-per-sublayer pass per token (the persistent step keeps no hidden
+    rows, and the prefix-K/V pass would need a history of them), and the whole search is one captured body replayed max_len times with the
+    selection on the device: the host synchronises once (DecodeSession.contrastive_log).  One model only: no Ensemble.
+    Returns per dialogue (tokens up to <eos>, score, log-probabilities, penalties, ranks): score = sum of the chosen tokens'
+    log-probabilities (the model's own, <eos> included) + penalty * (len + 1), a finished sample's formula; the three lists hold, per
+    chosen token (<eos> included), its log-probability, its degeneration penalty and its rank among the k candidates (0: the most probable).
+    ``trace``: a list that receives the numpy logs (tokens, log-probabilities, penalties, ranks), each (max_len, D), and — eager runs only
+    (use_graph=False) — after them the per-step dicts of what the kernel read (hidden, top, tokens, cand_logp, step, done)."""
+    k, alpha, banned = _contrastive(k, alpha, banned)
+    if isinstance(model, Ensemble):
+        raise ValueError("contrastive_decode_many: one model (the degeneration penalty reads ONE decoder's states), not an Ensemble")
+    sess = _session(model, batch, max_len, k, pad, use_graph, False, select=None, mega=False, mode="contrastive")
+    steps = [] if (trace is not None and not sess.use_graph) else None
+    tok, lp, pen, rank = sess.contrastive_log(start, k, alpha, eos, min_len, banned, trace=steps)
+    if trace is not None:
+        trace.append((tok, lp, pen, rank) + ((steps,) if steps is not None else ()))
+    results = []
+    for d in range(sess.D):
+        col = [int(t) for t in tok[1:, d]]
+        n = col.index(eos) if eos in col else len(col)
+        used = n + 1 if eos in col else n
+        results.append((col[:n], float(lp[1:1 + used, d].astype("float64").sum()) + penalty * (n + 1), [float(v) for v in lp[1:1 + used, d]],
+                        [float(v) for v in pen[1:1 + used, d]], [int(v) for v in rank[1:1 + used, d]]))
+    return results
 
 
 def mbr_weights(scores, temperature=1.0):

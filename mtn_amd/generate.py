@@ -34,6 +34,7 @@ FRAME_STEP = 64          # bucket grid: frame counts of every feature type round
 TEXT_STEP = 32           # ... history, question and caption lengths to a multiple of this
 MAX_SAMPLES = 16         # --samples: the samples of a QA ride in one search (decode.MegaDecodeSession.MAX_W rows)
 MBR_MAX_HYP, MBR_MAX_LEN = 16, 128       # --mbr: hypotheses per QA and tokens per hypothesis (include/mtn_hip.h mtn_mbr_select)
+CONTRASTIVE_MAX_K = 12   # --contrastive-k: with the three ids the CLI bans and <eos>, the candidates fit a row head of 16 entries
 LAUNCH_PASS_D = 8        # dialogues per search where the persistent decode step does not apply (launch-per-sublayer pass)
 
 # the reference train.py's defaults (train.py:57-96) for fields a conf may lack (confs written by older versions)
@@ -56,7 +57,7 @@ def parse(argv=None):
     p.add_argument("--nbest", default=5, type=int, help="Number of n-best hypotheses")
     p.add_argument("--output", "-o", default="", type=str, help="Output generated responses in a json file")
     p.add_argument("--verbose", "-v", default=0, type=int, help="verbose level")
-    p.add_argument("--decode-style", default="greedy", type=str, help="greedy, beam_search, sample or score")
+    p.add_argument("--decode-style", default="greedy", type=str, help="greedy, beam_search, sample, contrastive or score")
     p.add_argument("--undisclosed-only", default=0, type=int, help="")
     # (nargs="?": run.sh passes `--labeled-test ${labeled_test}` with labeled_test='' by default, i.e. the bare flag)
     p.add_argument("--labeled-test", default=None, nargs="?", type=str, help="directory to labelled data")
@@ -71,6 +72,11 @@ def parse(argv=None):
     p.add_argument("--top-p", default=1.0, type=float, help="sample: nucleus, the smallest set of tokens with this mass (1 = off)")
     p.add_argument("--samples", default=1, type=int, help="sample: responses drawn per QA (at most %d); the best-scoring one is the answer" % MAX_SAMPLES)
     p.add_argument("--sample-seed", default=1, type=int, help="sample: seed of the random streams (a QA's stream depends on the seed and its qa_id only)")
+    # --decode-style contrastive: contrastive search (Su et al. 2022) — among the K most probable tokens the one whose decoder state is
+    # least similar to the prefix' states (csrc/contrastive.hip); deterministic, one answer per QA
+    p.add_argument("--contrastive-k", default=5, type=int, help="contrastive: candidates per position (1..%d; 1 = greedy)" % CONTRASTIVE_MAX_K)
+    p.add_argument("--contrastive-alpha", default=0.6, type=float,
+                   help="contrastive: weight of the degeneration penalty against the model's probability (0..1; 0 = greedy)")
     # --decode-style score: nothing is generated — given responses are scored (teacher-forced log-likelihood) and ranked
     p.add_argument("--candidates", default=None, type=str,
                    help='score: JSON {"<image_id>_<turn>": {"candidates": ["text", ...], "gt_index": k}} (gt_index optional); a QA '
@@ -107,8 +113,19 @@ def parse(argv=None):
                    help="one QA per search at its own padded shape, as the reference decodes (baseline / debugging)")
     args = p.parse_args(argv)
     args.undisclosed_only = bool(args.undisclosed_only)
-    if args.decode_style not in ("greedy", "beam_search", "sample", "score"):
-        p.error("--decode-style must be greedy, beam_search, sample or score")
+    if args.decode_style not in ("greedy", "beam_search", "sample", "contrastive", "score"):
+        p.error("--decode-style must be greedy, beam_search, sample, contrastive or score")
+    if not 1 <= args.contrastive_k <= CONTRASTIVE_MAX_K:
+        p.error("--contrastive-k must be in [1, %d]" % CONTRASTIVE_MAX_K)
+    if not 0.0 <= args.contrastive_alpha <= 1.0:
+        p.error("--contrastive-alpha must be in [0, 1]")
+    if args.decode_style == "contrastive":
+        # the search reads ONE decoder's states and takes no row constraint: what it does not combine with ends the run by name
+        for on, flag in ((bool(args.ensemble_model), "--ensemble-model"), (args.mbr != 0, "--mbr"), (args.beam_groups > 1, "--beam-groups"),
+                         (args.no_repeat_ngram != 0, "--no-repeat-ngram"), (args.repetition_penalty != 1.0, "--repetition-penalty"),
+                         (args.candidates is not None, "--candidates")):
+            if on:
+                p.error("%s does not go with --decode-style contrastive" % flag)
     if args.candidates is not None and args.decode_style != "score":
         p.error("--candidates goes with --decode-style score")
     if not 1 <= args.samples <= MAX_SAMPLES:
@@ -322,10 +339,10 @@ def greedy_text(ys, vocablist, eos):
     return detokenize(list(ys)[1:], vocablist, eos)
 
 
-def build_result(original, undisclosed_only, answers, scores=None, mbr=None):
+def build_result(original, undisclosed_only, answers, scores=None, mbr=None, contrastive=None):
     """{'dialogs': [{'image_id', 'dialog'}]} in file order (generate.py:27-38): every turn, or the last one with undisclosed-only;
     ``answers[qa_id]`` replaces the answer of the qa_id-th output turn; ``scores[qa_id]`` (--decode-style score) becomes its "scores",
-    ``mbr[qa_id]`` (--mbr) its "mbr"."""
+    ``mbr[qa_id]`` (--mbr) its "mbr", ``contrastive[qa_id]`` (--decode-style contrastive) its "contrastive"."""
     dialogs, qa = [], 0
     for dialog in original["dialogs"]:
         out = copy.deepcopy(dialog["dialog"][-1:] if undisclosed_only else dialog["dialog"])
@@ -335,6 +352,8 @@ def build_result(original, undisclosed_only, answers, scores=None, mbr=None):
                 turn["scores"] = scores[qa]
             if mbr is not None:
                 turn["mbr"] = mbr[qa]
+            if contrastive is not None:
+                turn["contrastive"] = contrastive[qa]
             qa += 1
         dialogs.append({"image_id": dialog["image_id"], "dialog": out})
     return {"dialogs": dialogs}
@@ -421,8 +440,9 @@ def candidate_order(scores):
 # ---------------------------------------------------------------------------------------------------------------- decoding
 def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=None, scoring=None,
                     no_repeat_ngram=0, repetition_penalty=1.0, min_len=1, beam_groups=1, diversity_penalty=0.0, mbr=0, mbr_weights="uniform",
-                    mbr_temperature=1.0):
+                    mbr_temperature=1.0, contrastive=None):
     """Run the planned searches; returns per qa_id the (n-best list, best score) of beam search, the greedy token list, the
+    (tokens, score, log-probabilities, penalties, ranks) of contrastive search (``contrastive``: k / alpha), the
     samples' (tokens, score) pairs, best first (``sampling``: samples / temperature / top_k / top_p / seed), or the candidates'
     score dicts in input order (``scoring``: tokens = per qa_id its candidates' token lists, max_len, width — one session shape
     per bucket).  ``no_repeat_ngram`` / ``repetition_penalty`` constrain beam search, greedy and sample (decode.py; off by default);
@@ -456,6 +476,10 @@ def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, 
                                             **sampling, **con, **in_search)
             if mbr and not in_search:
                 res = decode.mbr_rerank(res, mbr, weights=mbr_weights, temperature=mbr_temperature)
+        elif decode_style == "contrastive":
+            # the ids `sample` bans; the row constraints and ensembles do not apply to this search (generate_response refuses them)
+            res = decode.contrastive_decode_many(model, batch, maxlen, sos, eos, pad, k=contrastive["k"], alpha=contrastive["alpha"],
+                                                 banned=(unk, pad, sos), min_len=min_len, penalty=penalty)
         elif decode_style == "score":
             # (a padding copy of the last QA rides with one candidate: its rows are dropped)
             cands = [scoring["tokens"][i] if k < n_real else scoring["tokens"][i][:1] for k, i in enumerate(ids)]
@@ -469,7 +493,8 @@ def decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, 
 
 def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0, nbest=5, decode_style="greedy", undisclosed_only=False,
                       ref_data=None, dialogues_per_search=0, buckets=True, sampling=None, candidates=None, no_repeat_ngram=0,
-                      repetition_penalty=1.0, min_len=1, beam_groups=1, diversity_penalty=0.0, mbr=0, mbr_weights="uniform", mbr_temperature=1.0):
+                      repetition_penalty=1.0, min_len=1, beam_groups=1, diversity_penalty=0.0, mbr=0, mbr_weights="uniform", mbr_temperature=1.0,
+                      contrastive=None):
     """Decode every QA of ``data`` (data_handler.load) and return the reference's result dict, logging the reference's
     QS / REF / HYP lines per QA.  decode_style "score" generates nothing: every QA's ``candidates`` (load_candidates' ``spec``; its
     own answer without one) are scored and logged as CAND lines, best first; the answer is the best-scoring candidate, every turn
@@ -480,7 +505,11 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
     plain beam search, and so is the number of dialogues per search.  ``mbr`` = N in 1..4 (decode_style "beam_search" or "sample";
     ValueError elsewhere): minimum-Bayes-risk selection — the HYP lines come in its order, so HYP[1] is the answer, one line
     "MBR: e_1 e_2 ..." (the expected utilities, in that order) follows them, and every turn gains "mbr"; ``mbr_weights`` "uniform" or
-    "score" with ``mbr_temperature`` > 0 (decode.mbr_rerank)."""
+    "score" with ``mbr_temperature`` > 0 (decode.mbr_rerank).  decode_style "contrastive" (``contrastive``: dict(k, alpha), defaults 5 and
+    0.6; decode.contrastive_decode_many): one answer per QA, logged as greedy's HYP line; every turn gains "contrastive" — its score and,
+    per chosen token (<eos> included), the log-probability, degeneration penalty and rank.  The search is k rows wide on the
+    launch-per-sublayer pass; it takes ``min_len`` but no Ensemble, mbr, row constraints or candidates, and — as every style but beam_search —
+    no beam_groups / diversity_penalty (ValueError each)."""
     if not 0 <= int(mbr) <= 4 or mbr_weights not in ("uniform", "score") or not mbr_temperature > 0:
         raise ValueError("generate_response: mbr in 0..4, mbr_weights 'uniform' or 'score', mbr_temperature > 0")
     if mbr and decode_style not in ("beam_search", "sample"):
@@ -489,6 +518,12 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
         raise ValueError("generate_response: mbr takes at most %d hypotheses of at most %d tokens" % (MBR_MAX_HYP, MBR_MAX_LEN))
     if decode_style == "score" and (no_repeat_ngram != 0 or repetition_penalty != 1.0):
         raise ValueError("generate_response: no_repeat_ngram / repetition_penalty constrain a search; a scoring run has none")
+    if decode_style == "contrastive":
+        from .decode import Ensemble, _contrastive
+        contrastive = dict(dict(k=5, alpha=0.6), **(contrastive or {}))
+        _contrastive(contrastive["k"], contrastive["alpha"])
+        if isinstance(model, Ensemble) or mbr or no_repeat_ngram != 0 or repetition_penalty != 1.0 or candidates is not None:
+            raise ValueError("generate_response: decode_style contrastive takes one model and no mbr, no_repeat_ngram, repetition_penalty or candidates")
     if decode_style == "beam_search":
         from .decode import _diverse
         _diverse(beam, beam_groups, diversity_penalty)
@@ -500,6 +535,8 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
     if decode_style == "sample":
         sampling = dict(dict(samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=1), **(sampling or {}))
     width = beam if decode_style == "beam_search" else (sampling["samples"] if decode_style == "sample" else 1)
+    if decode_style == "contrastive":
+        width = contrastive["k"]
     cands = scoring = None
     if decode_style == "score":
         cands = load_candidates(candidates, data["original"], vocab, undisclosed_only, ref_data)
@@ -509,8 +546,8 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
         scoring = dict(tokens=[c["tokens"] for c in cands], max_len=_up(longest + 1, 8), width=min(32, max(len(c["tokens"]) for c in cands)))
     if dialogues_per_search > 0:
         per = dialogues_per_search
-    elif decode_style == "score":
-        per = LAUNCH_PASS_D              # (scoring runs on the launch-per-sublayer pass)
+    elif decode_style in ("score", "contrastive"):
+        per = LAUNCH_PASS_D              # (scoring and contrastive search run on the launch-per-sublayer pass)
     else:
         per = lambda shape: auto_dialogues(model, corpus.device, shape, maxlen, width)
     searches = plan_searches(lens, per, buckets=buckets)
@@ -520,10 +557,12 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
     mbr_kw = dict(mbr=int(mbr), mbr_weights=mbr_weights, mbr_temperature=float(mbr_temperature)) if mbr else {}
     res = decode_searches(model, corpus, searches, vids, vocab, decode_style, maxlen, beam, penalty, nbest, sampling=sampling,
                           scoring=scoring, no_repeat_ngram=no_repeat_ngram, repetition_penalty=repetition_penalty, min_len=min_len,
-                          beam_groups=beam_groups, diversity_penalty=diversity_penalty, **mbr_kw)
+                          beam_groups=beam_groups, diversity_penalty=diversity_penalty, **mbr_kw,
+                          **(dict(contrastive=contrastive) if decode_style == "contrastive" else {}))
     answers = []
     scores = [] if decode_style == "score" else None
     mbr_out = [] if mbr else None
+    cs_out = [] if decode_style == "contrastive" else None
     qa_id = 0
     for idx, dialog in enumerate(data["original"]["dialogs"]):
         vid = dialog["image_id"]
@@ -559,6 +598,10 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
                 if mbr:
                     logging.info("MBR: " + " ".join(repr(h["expected"]) for h in shown))
                     mbr_out.append(shown)
+            elif decode_style == "contrastive":
+                hyp = detokenize(r[0], vocablist, eos)
+                logging.info("HYP: {}".format(hyp))
+                cs_out.append(dict(score=r[1], logp=r[2], penalty=r[3], rank=r[4]))
             else:
                 hyp = greedy_text(r, vocablist, eos)
                 logging.info("HYP: {}".format(hyp))
@@ -573,7 +616,7 @@ def generate_response(model, data, corpus, vocab, maxlen=30, beam=3, penalty=2.0
         if m["n_ranked"]:
             logging.info("MRR = %.6f  R@1 = %.6f  R@5 = %.6f  R@10 = %.6f  mean rank = %.4f  ( %d QAs with gt_index )"
                          % (m["mrr"], m["r1"], m["r5"], m["r10"], m["mean_rank"], m["n_ranked"]))
-    return build_result(data["original"], undisclosed_only, answers, scores, mbr_out)
+    return build_result(data["original"], undisclosed_only, answers, scores, mbr_out, cs_out)
 
 
 def evaluate_result(result, reference, last=False, stopwords=""):
@@ -603,6 +646,8 @@ def write_result(args, result, original, labeled_test=None):
 def main(argv=None):
     args = parse(argv)
     for arg in vars(args):
+        if arg in ("contrastive_k", "contrastive_alpha") and args.decode_style != "contrastive":
+            continue                                                        # (a run of another style prints what it always did)
         if args.evaluate or arg not in ("evaluate", "stopwords"):           # (a run without --evaluate prints what it always did)
             print("{}={}".format(arg, getattr(args, arg)))
     logging.basicConfig(level=logging.DEBUG if args.verbose >= 1 else logging.INFO, format="%(asctime)s %(levelname)s: %(message)s")
@@ -662,7 +707,8 @@ def main(argv=None):
                                              seed=args.sample_seed), candidates=args.candidates,
                                no_repeat_ngram=args.no_repeat_ngram, repetition_penalty=args.repetition_penalty, min_len=args.min_length,
                                beam_groups=args.beam_groups, diversity_penalty=args.diversity_penalty, mbr=args.mbr,
-                               mbr_weights=args.mbr_weights, mbr_temperature=args.mbr_temperature)
+                               mbr_weights=args.mbr_weights, mbr_temperature=args.mbr_temperature,
+                               **(dict(contrastive=dict(k=args.contrastive_k, alpha=args.contrastive_alpha)) if args.decode_style == "contrastive" else {}))
     wall = time.time() - start_time
     n_qa = len(test_data["dialogs"])
     logging.info("----------------")

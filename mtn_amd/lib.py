@@ -5,8 +5,11 @@ CPU or PyTorch fallback behind these calls.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import gc
 import os
+import threading
 
 import torch
 
@@ -185,6 +188,14 @@ class SampleArgs(C.Structure):
                 ("log_logp", C.c_void_p), ("log_u", C.c_void_p), ("tokens", C.c_void_p), ("pos", C.c_void_p), ("anc", C.c_void_p)]
 
 
+class ContrastiveArgs(C.Structure):
+    _fields_ = [("dialogues", C.c_int), ("k", C.c_int), ("L", C.c_int), ("d", C.c_int), ("k_top", C.c_int), ("alpha", C.c_float),
+                ("eos", C.c_int), ("min_len", C.c_int), ("n_banned", C.c_int), ("banned", C.c_int * 4), ("hidden", C.c_void_p),
+                ("row_stride", C.c_long), ("pos_stride", C.c_long), ("top", C.c_void_p), ("tokens", C.c_void_p), ("pos", C.c_void_p),
+                ("cand_logp", C.c_void_p), ("step", C.c_void_p), ("done", C.c_void_p), ("log_tok", C.c_void_p), ("log_logp", C.c_void_p),
+                ("log_pen", C.c_void_p), ("log_rank", C.c_void_p)]
+
+
 class ScoreArgs(C.Structure):
     _fields_ = [("n_seq", C.c_int), ("L", C.c_int), ("V", C.c_int), ("pad", C.c_int), ("ldz", C.c_long), ("logits", C.c_void_p),
                 ("target", C.c_void_p), ("tok_logp", C.c_void_p), ("tok_rank", C.c_void_p), ("seq_logp", C.c_void_p), ("seq_len", C.c_void_p)]
@@ -285,6 +296,7 @@ SYMBOLS = {
     "mtn_beam_advance": (C.c_int, [C.POINTER(BeamArgs), _P]),
     "mtn_diverse_advance": (C.c_int, [C.POINTER(DiverseArgs), _P]),
     "mtn_sample_rows": (C.c_int, [C.POINTER(SampleArgs), _P]),
+    "mtn_contrastive_advance": (C.c_int, [C.POINTER(ContrastiveArgs), _P]),
     "mtn_score_rows": (C.c_int, [C.POINTER(ScoreArgs), _P]),
     "mtn_constrain_rows": (C.c_int, [C.POINTER(ConstrainArgs), _P]),
     "mtn_ensemble_rows": (C.c_int, [C.POINTER(EnsembleArgs), _P]),
@@ -399,6 +411,34 @@ def check(rc: int):
 
 def stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+_capture_lock = threading.Lock()
+_captures = [0, False]          # captures open in any thread; whether the collector was on when the first of them began
+
+
+@contextlib.contextmanager
+def capturing(graph, **kw):
+    """A ``torch.cuda.graph`` capture into ``graph`` (keywords passed on) with Python's cyclic garbage collector off while it lasts.
+    A collection can start at any allocation, on any thread (the autograd worker that runs the deferred parameter-gradient flush
+    included), and it runs the destructors of whatever dead cycles exist — among them captured graphs of trainers and sessions no
+    longer in use.  The ROCm build's CUDAGraph destructor synchronises the device, which is forbidden while a stream is capturing: the
+    error is raised inside a destructor and the process aborts.  Nothing is lost by waiting: the cycles are collected after the capture.
+    The switch is process-wide, so captures are counted under a lock: the collector comes back when the LAST open capture ends, and
+    only if it was on when the first began."""
+    with _capture_lock:
+        if _captures[0] == 0:
+            _captures[1] = gc.isenabled()
+            gc.disable()
+        _captures[0] += 1
+    try:
+        with torch.cuda.graph(graph, **kw):
+            yield
+    finally:
+        with _capture_lock:
+            _captures[0] -= 1
+            if _captures[0] == 0 and _captures[1]:
+                gc.enable()
 
 
 def ptr(t) -> int:

@@ -972,6 +972,68 @@ def sample_rows(logp, seed, keys, step, log=None, max_len=1, **kw):
     return log
 
 
+CONTRASTIVE_MAX_K = 16        # csrc/contrastive.hip CS_MAX_K: rows of a dialogue, and entries of a row's head
+CONTRASTIVE_MAX_D = 1024      # csrc/contrastive.hip CS_MAX_D
+
+
+def contrastive_args(hidden, top, tokens, pos, cand_logp, step, done, log, *, k, alpha, eos=-1, min_len=0, banned=()):
+    """The argument block of mtn_contrastive_advance (include/mtn_hip.h) for hidden (rows, L, d) fp32 — the decoder's final-norm states,
+    unit element stride, any row / position strides at least the dense ones —, top (rows, 2 * k_top + 1) fp32 as topk_rows leaves it,
+    tokens (rows, L) int64, pos (1,) int64, cand_logp (rows,) fp32, step / done (rows / k,) int32 and log = (tokens int32,
+    log-probabilities fp32, penalties fp32, ranks int32), each (L, rows / k); all but hidden contiguous."""
+    lt, ll, lpn, lr = log
+    _require_cuda(hidden, top, tokens, pos, cand_logp, step, done, *log)
+    k, banned = int(k), [int(b) for b in banned]
+    if hidden.dtype != torch.float32 or hidden.dim() != 3 or (hidden.size(2) > 1 and hidden.stride(2) != 1):
+        raise ValueError("contrastive_advance: hidden is (rows, L, d) fp32 with unit element stride")
+    rows, Lm, d = hidden.shape
+    if not 1 <= k <= CONTRASTIVE_MAX_K or rows % k:
+        raise ValueError("contrastive_advance: 1 <= k <= 16 rows per dialogue, and rows is a multiple of k")
+    D = rows // k
+    if not 1 <= d <= CONTRASTIVE_MAX_D or Lm < 1:
+        raise ValueError("contrastive_advance: 1 <= d <= %d, L >= 1" % CONTRASTIVE_MAX_D)
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:                       # (a NaN fails both comparisons)
+        raise ValueError("contrastive_advance: alpha is in [0, 1]")
+    if len(banned) > 4:
+        raise ValueError("contrastive_advance: at most 4 banned tokens")
+    if top.dtype != torch.float32 or top.dim() != 2 or top.size(0) != rows or not top.is_contiguous() or top.size(1) % 2 != 1:
+        raise ValueError("contrastive_advance: top is a contiguous (rows, 2 * k_top + 1) fp32 tensor")
+    k_top = (top.size(1) - 1) // 2
+    if not min(CONTRASTIVE_MAX_K, k + len(banned) + 1) <= k_top <= CONTRASTIVE_MAX_K:
+        raise ValueError("contrastive_advance: min(16, k + banned + 1) <= k_top <= 16")
+    if tokens.dtype != torch.int64 or tuple(tokens.shape) != (rows, Lm) or not tokens.is_contiguous() or pos.dtype != torch.int64 or pos.numel() != 1:
+        raise ValueError("contrastive_advance: tokens is a contiguous (rows, L) int64 tensor, pos one int64")
+    if cand_logp.dtype != torch.float32 or cand_logp.numel() != rows or not cand_logp.is_contiguous():
+        raise ValueError("contrastive_advance: cand_logp is a contiguous (rows,) fp32 tensor")
+    if any(t.dtype != torch.int32 or t.numel() != D or not t.is_contiguous() for t in (step, done)):
+        raise ValueError("contrastive_advance: step and done are contiguous (dialogues,) int32 tensors")
+    if not (lt.dtype == lr.dtype == torch.int32 and ll.dtype == lpn.dtype == torch.float32 and all(tuple(t.shape) == (Lm, D) and t.is_contiguous() for t in log)):
+        raise ValueError("contrastive_advance: the log is (int32, fp32, fp32, int32), each contiguous (L, dialogues)")
+    a = L.ContrastiveArgs()
+    a.dialogues, a.k, a.L, a.d, a.k_top, a.alpha = D, k, Lm, d, k_top, alpha
+    a.eos, a.min_len, a.n_banned = int(eos), int(min_len), len(banned)
+    for i, b in enumerate(banned):
+        a.banned[i] = b
+    a.hidden = hidden.data_ptr()
+    a.row_stride = hidden.stride(0) if rows > 1 else max(hidden.stride(0), (Lm - 1) * max(hidden.stride(1), d) + d)
+    a.pos_stride = hidden.stride(1) if Lm > 1 else max(hidden.stride(1), d)
+    a.top, a.tokens, a.pos, a.cand_logp, a.step, a.done = (t.data_ptr() for t in (top, tokens, pos, cand_logp, step, done))
+    a.log_tok, a.log_logp, a.log_pen, a.log_rank = lt.data_ptr(), ll.data_ptr(), lpn.data_ptr(), lr.data_ptr()
+    return a
+
+
+def contrastive_advance(hidden, top, tokens, pos, cand_logp, step, done, log, **kw):
+    """One token of a contrastive search for every dialogue of k rows (csrc/contrastive.hip; include/mtn_hip.h mtn_contrastive_advance
+    gives the definition): scores the rows' candidates by probability and degeneration penalty, logs the choice at [step, dialogue] of
+    ``log``, stores it into ``tokens`` and deals the winner's head to the rows as the next candidates — all in place, one launch.
+    Keywords: k, alpha, eos, min_len, banned.  Returns the log."""
+    a = contrastive_args(hidden, top, tokens, pos, cand_logp, step, done, log, **kw)
+    if a.dialogues:
+        L.check(L.load().mtn_contrastive_advance(C.byref(a), L.stream_ptr()))
+    return log
+
+
 SCHED_PICKS = {"argmax": L.MTN_SCHED_ARGMAX, "sample": L.MTN_SCHED_SAMPLE}
 
 

@@ -17,6 +17,7 @@ from typing import Callable, NamedTuple, Optional
 
 import torch
 
+from . import lib as L
 from .data_utils import FusedAdam, LabelSmoothing, NoamOpt, SimpleLossCompute
 
 # Stream capture checks "potentially unsafe" runtime calls; in the default (global) mode a call from ANY thread invalidates the
@@ -914,7 +915,7 @@ class TrainStep:
         for st in stages:
             if st.unit is not None:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, capture_error_mode=CAPTURE_MODE):
+                with L.capturing(g, pool=pool, capture_error_mode=CAPTURE_MODE):
                     st.unit()
                 pool = g.pool()
                 graphs.append(g)
@@ -930,7 +931,7 @@ class TrainStep:
         wrote (no mtn_grad_sumsq in this graph); False: the norm launch is part of it (a window of one, a gradient exchange, no clipping)."""
         self.opt.optimizer._accum_sumsq = bool(have_sumsq)       # (consumed by FusedAdam._clip inside the capture)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self._g_fb.pool(), capture_error_mode=CAPTURE_MODE):
+        with L.capturing(g, pool=self._g_fb.pool(), capture_error_mode=CAPTURE_MODE):
             self._optim()
         return g
 
